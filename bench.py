@@ -13,7 +13,13 @@ Multi-GPU: every rank decodes its own 1024-frame batch (image-parallel shards,
 no collective on the data path; weak scaling); value = all ranks' pixels /
 max-over-ranks time.
 
-Printed JSON line fields beyond the driver contract:
+A run without --full does only what the headline needs: set up, W warmup + K
+timed launches, --dump-outputs DIR if given (dump_outputs), one JSON line.
+--full adds, after the timed launches, everything else below (oracle check of
+every frame, same-run stage and ceiling measurements, the configs[3] and
+configs[1] legs, the CPU legs, the config-5 stream legs) and the detail file.
+
+Printed JSON line fields beyond the driver contract (--full):
   roofline      achieved GB/s = algorithmic bytes per launch (int16 coefs in +
                 BGRX out, 7 B/px at 4:2:0, 10 B/px at 4:4:4) / mean launch time
                 measured with HIP events on the launch stream; peak 8.0 TB/s.
@@ -1104,11 +1110,54 @@ def stage_times(torch, plan, coefs, out, stream, product_ms, reps):
     return res
 
 
-def pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, steps, warmup, measure=True):
+DUMP_SAMPLE_BYTES = 1 << 22   # --dump-outputs: sampled output bytes (4 Mi float32 = 16 MiB)
+DUMP_ROWS = 64                # --dump-outputs: whole rows kept of the first and of the last frame
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, out, row_bytes, dump_dir, rank):
+    """--dump-outputs: what the last timed launch left in `out` [frames, rows,
+    pitch] uint8 (the batch a caller of plan.launch receives), written as
+    float arrays of at most 64 MB in all:
+      frame_byte_sums.npy  float64 [frames]: the sum of every frame's bytes
+                           (exact: < 2^53), so every byte of the batch counts;
+      sample_bytes.npy     float32 [DUMP_SAMPLE_BYTES]: bytes at positions
+                           (frame, row, column) drawn once from a seeded
+                           generator, the same for every run of this shape;
+      first_rows.npy, last_rows.npy
+                           float32 [DUMP_ROWS, row_bytes]: the top rows of
+                           the first frame and the bottom rows of the last.
+    Row padding (pitch > row_bytes) is never read.  Ranks other than 0 write
+    into DIR/rank<r>/."""
+    nf, h, _ = out.shape
+    if rank:
+        dump_dir = os.path.join(dump_dir, f"rank{rank}")
+    os.makedirs(dump_dir, exist_ok=True)
+    sums = torch.empty(nf, dtype=torch.int64, device=out.device)
+    for i in range(0, nf, 32):
+        sums[i:i + 32] = out[i:i + 32, :, :row_bytes].sum(dim=(1, 2), dtype=torch.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = [torch.from_numpy(rng.integers(0, n, DUMP_SAMPLE_BYTES, dtype=np.int64)).to(out.device)
+           for n in (nf, h, row_bytes)]
+    rows = min(DUMP_ROWS, h)
+    arrays = {"frame_byte_sums": sums.to(torch.float64),
+              "sample_bytes": out[idx[0], idx[1], idx[2]].to(torch.float32),
+              "first_rows": out[0, :rows, :row_bytes].to(torch.float32),
+              "last_rows": out[nf - 1, h - rows:, :row_bytes].to(torch.float32)}
+    for name, t in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), t.cpu().numpy())
+    return sorted(arrays)
+
+
+def pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, steps, warmup, measure=True, lean=False,
+                dump_dir=None):
     """One pixel workload on this rank: inputs resident in HBM, W untimed + K
     timed launches of one plan over the whole batch (barrier + synchronize on
     both sides, max over ranks), then every frame of the last launch checked
-    against the oracle.  Frees its device buffers before returning."""
+    against the oracle.  lean=True (a run without --full) stops after the timed
+    launches: no copy-bandwidth figure, no oracle check, no same-run
+    measurements.  dump_dir: the last timed launch's output goes there
+    (dump_outputs).  Frees its device buffers before returning."""
     from ocljpegdecoder_amd import shard
     w, h, s, nf = wl["width"], wl["height"], wl["sampling"], wl["frames"]
     mw, mh, bpm, _ = hjd.mcu_geometry(w, h, s)
@@ -1180,6 +1229,17 @@ def pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, steps, warmup,
     value = total_px / wall_max / 1e6
     achieved = bytes_per_launch / (kernel_ms / 1e3) / 1e9
 
+    dumped = None
+    if dump_dir:
+        dumped = dump_outputs(torch, out, hjd.OUT_BYTES[ofmt] * w, dump_dir, rank)
+    if lean:
+        tasks = plan.tasks
+        plan.close()
+        del coefs, out, pool16, plan
+        return {"value": round(value, 1), "launch": launch, "dumped": dumped, "_wall_max": wall_max,
+                "_kernel_ms": kernel_ms, "_achieved": achieved, "_bytes_per_launch": bytes_per_launch,
+                "_tasks": tasks, "_npool": npool}
+
     # device-to-device copy bandwidth for context (same-size read+write)
     copy_gbps = None
     try:
@@ -1213,7 +1273,7 @@ def pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, steps, warmup,
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return {"value": round(value, 1), "output_check": checked, "device_copy_GBps": copy_gbps,
-            "stages": stages, "box": box, "clock": clock, "launch": launch,
+            "stages": stages, "box": box, "clock": clock, "launch": launch, "dumped": dumped,
             "_pool_host": pool_host, "_wall_max": wall_max, "_kernel_ms": kernel_ms, "_achieved": achieved,
             "_bytes_per_launch": bytes_per_launch, "_tasks": tasks}
 
@@ -1310,12 +1370,58 @@ def emit(res, detail_path):
     print(json.dumps(compact_line(res, detail_path)), flush=True)
 
 
+def run_lean(args, wl, hjd, torch, dist, world, rank, dev, qt):
+    """A pixel workload without --full: set up, warm up, time the K launches,
+    write the outputs if asked, print the line.  The headline fields (metric,
+    value, unit, higher_is_better, dtype, ms_per_step) and the roofline
+    fraction are those of the --full line: they come from the same timed
+    launches.  Nothing is checked against the oracle here."""
+    r = pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, args.steps, args.warmup, measure=False,
+                    lean=True, dump_dir=args.dump_outputs)
+    w, h, s, nf = wl["width"], wl["height"], wl["sampling"], wl["frames"]
+    if rank == 0:
+        i32 = wl.get("input") == "i32"
+        ofmt = wl.get("out_format", hjd.OUT_BGRX)
+        res = {
+            "metric": "Mpixels/s decoded (dequant+IDCT+colour) at 1/2/4/8 GPUs; % HBM roofline",
+            "value": r["value"], "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(r["_wall_max"] / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "int32", "full": False,
+            "data": "synthetic (device-generated FDCT+quantised smooth+noise blocks, pool of "
+                    f"{r['_npool']} distinct frames replicated to {nf}); inputs resident in HBM",
+            "config": {"workload": wl["desc"], "frames_per_gpu": nf, "width": w, "height": h,
+                       "sampling": SAMPLING_NAMES[s],
+                       "input": "int32 natural-order dequantised (idct.h format)" if i32
+                                else "int16 quantised zigzag + qtables",
+                       "output": "BGRX 4 B/px in HBM" if ofmt == hjd.OUT_BGRX else "BGR24 3 B/px in HBM",
+                       "parallelism": f"image-parallel x{world} (no collective)",
+                       "tasks_per_launch": r["_tasks"]},
+            "roofline": roofline_obj(r["_achieved"], r["_bytes_per_launch"], r["_kernel_ms"],
+                                     committed_traffic(args.workload, nf)),
+            "launch": r["launch"],
+            "output_checked_vs_oracle": None,
+            "outputs_dumped": r["dumped"] and {"dir": args.dump_outputs, "arrays": r["dumped"]},
+            "cpu_baseline": None,
+        }
+        print(json.dumps(res), flush=True)
+    if world > 1 and dist.is_initialized():
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="4k420", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="pixel workloads: after the timed steps also run everything else this benchmark measures "
+                         "and checks (oracle check of every frame, stage ablation and box ceiling, configs[3] and "
+                         "configs[1] legs, CPU baselines, the config-5 stream legs) and write the detail file; "
+                         "without it a run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pixel workloads: write what the last timed step computed to DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--frames", type=int, default=0, help="override batch size")
     ap.add_argument("--grid", type=int, default=0, help="persistent grid (workgroups), 0 = default")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
@@ -1380,12 +1486,18 @@ def main():
     w, h, s, nf = wl["width"], wl["height"], wl["sampling"], wl["frames"]
     qt = std_qtables(1.0)
 
+    if args.dump_outputs and (args.workload.startswith("stream") or wl.get("jpeg")):
+        ap.error("--dump-outputs is implemented for the pixel-batch workloads only")
     if args.workload.startswith("stream"):
         return run_stream(args, wl, hjd, torch, dist, world, rank, dev)
     if wl.get("jpeg"):
         return run_jpeg_single(args, wl, hjd, torch, dist, world, rank, dev)
 
-    res_px = pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, args.steps, args.warmup)
+    if not args.full:
+        return run_lean(args, wl, hjd, torch, dist, world, rank, dev, qt)
+
+    res_px = pixel_batch(args, wl, hjd, torch, dist, world, rank, dev, qt, args.steps, args.warmup,
+                         dump_dir=args.dump_outputs)
     checked = res_px["output_check"]
     value = res_px["value"]
     pool_host = res_px.pop("_pool_host")
@@ -1467,6 +1579,7 @@ def main():
             "roofline": roofline_obj(achieved, bytes_per_launch, kernel_ms, traffic, res_px["box"]),
             "stages": res_px["stages"], "box_ceiling": res_px["box"], "clock_under_load": res_px["clock"],
             "launch": res_px["launch"],
+            "outputs_dumped": res_px["dumped"] and {"dir": args.dump_outputs, "arrays": res_px["dumped"]},
             "box": box_identity(torch),
             "cpu_baseline": cpu,
             "device_copy_GBps": res_px["device_copy_GBps"],

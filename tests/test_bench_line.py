@@ -57,6 +57,37 @@ def test_compact_line_reports_a_failed_leg():
     assert d["summary"]["c5_d2h"] == {"error": "rc 1"}
 
 
+def test_dump_outputs_arrays(tmp_path):
+    """--dump-outputs: float arrays of the output batch; row padding never
+    counts, the sampled positions are the same from call to call."""
+    import numpy as np
+    import torch
+    b = _bench()
+    rng = np.random.default_rng(5)
+    nf, h, pitch, row = 3, 70, 40, 36
+    a = rng.integers(0, 256, (nf, h, pitch), dtype=np.uint8)
+    names = b.dump_outputs(torch, torch.from_numpy(a), row, str(tmp_path / "a"), 0)
+    assert names == ["first_rows", "frame_byte_sums", "last_rows", "sample_bytes"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["frame_byte_sums"].dtype == np.float64
+    assert all(got[n].dtype == np.float32 for n in names if n != "frame_byte_sums")
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    np.testing.assert_array_equal(got["frame_byte_sums"], a[:, :, :row].sum(axis=(1, 2), dtype=np.int64))
+    np.testing.assert_array_equal(got["first_rows"], a[0, :b.DUMP_ROWS, :row])
+    np.testing.assert_array_equal(got["last_rows"], a[-1, h - b.DUMP_ROWS:, :row])
+    assert got["sample_bytes"].shape == (b.DUMP_SAMPLE_BYTES,)
+    # other padding, one payload byte changed: only what covers that byte moves
+    a2 = a.copy()
+    a2[:, :, row:] ^= 0xFF
+    a2[1, 40, 7] ^= 0x10
+    b.dump_outputs(torch, torch.from_numpy(a2), row, str(tmp_path / "b"), 1)
+    got2 = {n: np.load(tmp_path / "b" / "rank1" / (n + ".npy")) for n in names}
+    assert np.flatnonzero(got2["frame_byte_sums"] != got["frame_byte_sums"]).tolist() == [1]
+    np.testing.assert_array_equal(got2["first_rows"], got["first_rows"])
+    changed = np.flatnonzero(got2["sample_bytes"] != got["sample_bytes"])
+    assert 0 < len(changed) < b.DUMP_SAMPLE_BYTES // 1000    # ~1 in nf*h*row positions
+
+
 def test_emit_writes_detail(tmp_path, capsys):
     b = _bench()
     res = _full()

@@ -58,7 +58,7 @@ def test_two_ranks_pixel_bench():
     extra_env = {"HJD_BENCH_STREAM_FRAMES": "12", "HJD_STREAM_POOL": "8"}
     os.environ.update(extra_env)
     try:
-        r = _run("4k420", 8, extra=("--stream-frame-ids", "72", "--stream-host-frame-ids", "48"), timeout=300)
+        r = _run("4k420", 8, extra=("--full", "--stream-frame-ids", "72", "--stream-host-frame-ids", "48"), timeout=300)
     finally:
         for k in extra_env:
             os.environ.pop(k, None)
@@ -90,6 +90,33 @@ def test_two_ranks_pixel_bench():
     sm = r["_line"]["summary"]
     assert sm["4k444"]["Mpx_s"] == c4["value"] and sm["c5_host_huffman"]["Mpx_s"] == sh["value"]
     assert r["_line"]["output_checked_vs_oracle"] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: the contract line only (no other leg, no detail file),
+    and --dump-outputs writes the last timed launch's output -- the same
+    arrays from another run with another launch shape (no autotune)."""
+    import numpy as np
+    runs = []
+    for tag, extra in (("a", ()), ("b", ("--no-autotune",))):
+        d = str(tmp_path / tag)
+        r = _run("4k420", 8, extra=("--dump-outputs", d, *extra), ranks=1)
+        assert "_line" not in r and r["full"] is False and "summary" not in r and "config4_444" not in r
+        assert r["n_gpus"] == 1 and r["steps"] == 3 and r["unit"] == "Mpixels/s" and r["dtype"] == "int32"
+        assert r["higher_is_better"] is True and r["value"] > 0 and r["ms_per_step"] > 0
+        px = 3 * 8 * 3840 * 2160
+        assert abs(r["value"] - px / (r["ms_per_step"] * 3 / 1e3) / 1e6) / r["value"] < 0.02
+        assert r["outputs_dumped"]["dir"] == d
+        arrays = {n: np.load(os.path.join(d, n + ".npy")) for n in r["outputs_dumped"]["arrays"]}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        runs.append(arrays)
+    assert runs[0]["frame_byte_sums"].shape == (8,) and runs[0]["first_rows"].shape == (64, 4 * 3840)
+    assert len(set(runs[0]["frame_byte_sums"].tolist())) == 8         # 8 distinct pool frames
+    assert runs[0]["sample_bytes"].std() > 10                          # decoded content, not a constant fill
+    for n in runs[0]:
+        np.testing.assert_array_equal(runs[0][n], runs[1][n])
 
 
 @pytest.mark.gpu

@@ -1,5 +1,5 @@
 """tools/ktrace_dispatch.py picks the bench line's own timed launches out of a
-kernel trace of `python bench.py`: after the launch autotune's candidate
+kernel trace of `python bench.py --full`: after the launch autotune's candidate
 launches of the same kernel, before the clock probe and the stage variants
 (bench.py pixel_batch), for the exact instantiation the line ran (launch
 variant bits, plus the d16 gather bit at 4:4:4 when present)."""

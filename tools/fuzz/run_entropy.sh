@@ -4,7 +4,7 @@
 # on damaged sequential JPEGs, one scan or several (tools/fuzz/entropy_emulate_fuzz.cpp).
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
-O=${TMPDIR:-/tmp}/hjd_efuzz
+O=$R/build/efuzz   # in the tree (git-ignored): a shared temp directory may belong to another user
 mkdir -p $O
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined"
 FLAGS="-std=c++17 -O1 -g -fno-omit-frame-pointer -I$R/include -I$R/ocljpegdecoder_amd/csrc"

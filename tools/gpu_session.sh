@@ -7,11 +7,11 @@
 # Output goes to gpurun_out/<tag>/ (merged back by gpurun).  Steps:
 #   tests[:<pytest -k expr>]     the GPU suite (python -m pytest -m gpu), tests.log
 #   smoke                        __graft_entry__.smoke(), smoke.log
-#   bench[:<bench args>]         python bench.py <args> (default: the driver's
-#                                command), bench.json + bench.err + bench_detail.json
+#   bench[:<bench args>]         python bench.py --full <args> (default: every leg of the
+#                                benchmark), bench.json + bench.err + bench_detail.json
 #   ktrace:<workload>[:<args>]   rocprofv3 --kernel-trace --stats of bench.py
 #                                --workload <workload> --no-cpu --no-stream <args>;
-#                                ktrace:default traces the driver's own command (python bench.py)
+#                                ktrace:default traces python bench.py --full
 #   pmc:<workload>               HBM bytes: FETCH_SIZE / WRITE_SIZE passes (tools/pmc/traffic.txt)
 #   ent:<workload>[:<args>]      SQ counters of the entropy kernels (tools/pmc/entropy.txt)
 #   htrace:<workload>[:<variant>]  HIP API + kernel + copy trace (no counters) of bench.py --workload
@@ -47,19 +47,19 @@ for step in "$@"; do
           || fail smoke "$O/smoke.log"
       tail -1 "$O/smoke.log" ;;
     bench)
-      (cd "$R" && timeout -k 10 900 python -u bench.py ${a1//,/ } --detail-out "$O/bench_detail.json" \
+      (cd "$R" && timeout -k 10 900 python -u bench.py --full ${a1//,/ } --detail-out "$O/bench_detail.json" \
           > "$O/bench.json" 2> "$O/bench.err") || fail bench "$O/bench.err"
       cat "$O/bench.json" ;;
     ktrace)
-      # ktrace:default = the driver's own command (python bench.py), every leg
-      if [ "$a1" = default ]; then BA=(); else BA=(--workload "$a1" --no-cpu --no-stream); fi
+      # ktrace:default = python bench.py --full, every leg
+      if [ "$a1" = default ]; then BA=(--full); else BA=(--full --workload "$a1" --no-cpu --no-stream); fi
       (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/ktrace_$a1" -o bench -- \
           python3 "$R/bench.py" "${BA[@]}" ${a2//,/ } --detail-out "$O/ktrace_$a1.detail.json" \
           > "$O/ktrace_$a1.json" 2> "$O/ktrace_$a1.err") || fail ktrace "$O/ktrace_$a1.err"
       tail -c 400 "$O/ktrace_$a1.json" ;;
     pmc)
       (cd /tmp && timeout -k 10 900 rocprofv3 -i "$R/tools/pmc/traffic.txt" --output-format csv -d "$O/pmc_$a1" -o pmc -- \
-          python3 "$R/bench.py" --workload "$a1" --steps 3 --warmup 1 --no-cpu --no-stream --no-stages --no-autotune \
+          python3 "$R/bench.py" --full --workload "$a1" --steps 3 --warmup 1 --no-cpu --no-stream --no-stages --no-autotune \
           --no-444 --no-fhd --detail-out "$O/pmc_$a1.detail.json" > "$O/pmc_$a1.json" 2> "$O/pmc_$a1.err") \
           || fail pmc "$O/pmc_$a1.err"
       tail -c 300 "$O/pmc_$a1.json" ;;
@@ -80,7 +80,7 @@ for step in "$@"; do
       tail -c 300 "$O/ent_$a1.json" ;;
     sq)
       (cd /tmp && timeout -k 10 300 rocprofv3 -i "$R/tools/pmc/pixel.txt" --output-format csv -d "$O/sq_$a1" -o px -- \
-          python3 "$R/bench.py" --workload "$a1" --frames 256 --steps 2 --warmup 1 --no-cpu --no-stream --no-stages \
+          python3 "$R/bench.py" --full --workload "$a1" --frames 256 --steps 2 --warmup 1 --no-cpu --no-stream --no-stages \
           --no-444 --no-fhd --no-autotune ${a2//,/ } --detail-out "$O/sq_$a1.detail.json" \
           > "$O/sq_$a1.json" 2> "$O/sq_$a1.err") || fail sq "$O/sq_$a1.err"
       tail -c 300 "$O/sq_$a1.json" ;;
@@ -89,7 +89,7 @@ for step in "$@"; do
       for rep in $(seq 1 "$N"); do
         for lib in product "$V"; do
           if [ "$lib" = product ]; then unset HJD_LIB; else export HJD_LIB=$R/build/variants/$V/libhjd.so; fi
-          (cd "$R" && timeout -k 10 600 python -u bench.py --workload "$WL" --no-cpu --no-stream --no-fhd --no-444 \
+          (cd "$R" && timeout -k 10 600 python -u bench.py --full --workload "$WL" --no-cpu --no-stream --no-fhd --no-444 \
               ${a4//,/ } --detail-out "$O/ab_${WL}_${lib}_$rep.detail.json" \
               > "$O/ab_${WL}_${lib}_$rep.json" 2> "$O/ab_${WL}_${lib}_$rep.err") \
               || fail "ab $lib $rep" "$O/ab_${WL}_${lib}_$rep.err"

@@ -4,7 +4,7 @@ dispatches of the pixel kernel, per workload.
 
     python tools/ktrace_dispatch.py <rocprof_dir> <bench_json> <name> [--warmup 3 --steps 20]
 
-bench.py (default command) launches, in this order: W warmup + K timed
+bench.py --full launches, in this order: W warmup + K timed
 launches of the 4:2:0 batch (decode_kernel<1,...>), then W + K of the 4:4:4
 batch (decode_kernel<0,...>), then (config-5 leg) the stream's kernels in a
 child process.  The first W + K dispatches of each decode_kernel
@@ -36,7 +36,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=1024)
-    ap.add_argument("--command", default="python bench.py")
+    ap.add_argument("--command", default="python bench.py --full")
     args = ap.parse_args()
     rows = []
     for p in sorted(glob.glob(os.path.join(args.dir, "**", "*kernel_trace.csv"), recursive=True)):
