@@ -57,7 +57,25 @@ enum hjd_out_format {
     /* 3 bytes per pixel: B, G, R (a 24-bpp BMP row; extension, SURVEY.md
      * s8(f) rank 4).  Same values as BGRX without the pad byte; the kernel
      * writes 25 % fewer bytes. */
-    HJD_OUT_BGR24 = 1
+    HJD_OUT_BGR24 = 1,
+    /* 3 bytes per pixel: R, G, B, interleaved (HWC: what PIL / numpy callers
+     * hold).  Same values as BGR24 with R and B exchanged. */
+    HJD_OUT_RGB24 = 2,
+    /* Three uint8 planes R, G, B, each `height` rows of `out_pitch` bytes
+     * (CHW: what tensor pipelines hold).  Plane c of a frame starts at
+     * out_offset + c * out_pitch * height; with out_pitch == width a frame is
+     * a contiguous (3, H, W) array, and equal frames at consecutive offsets
+     * form (N, 3, H, W).  HJD_GRAY frames write three identical planes.
+     *
+     * HJD_OUT_RGB24 and HJD_OUT_RGB_PLANAR take ANY out_pitch >= 3*width
+     * (planar: >= width), any out_offset and any per-image output pointer, so
+     * a contiguous array of any width can be the destination.  A frame whose
+     * out_pitch, out_offset (and output pointer) are all multiples of 4 is
+     * written with full-width vector stores; any other frame takes the
+     * guarded byte-store path for every strip: correct, but slower.  (The
+     * buffer passed to hjd_plan_launch stays 16-byte aligned for every
+     * format; frames sit in it at any out_offset.) */
+    HJD_OUT_RGB_PLANAR = 3
 };
 
 /* Kernel selection of a plan (hjd_plan_set_kernel).  Both kernels produce
@@ -91,10 +109,11 @@ typedef struct hjd_frame {
     uint64_t out_offset;  /* byte offset of pixel (0,0) in the output buffer */
     int32_t width;        /* visible pixels (output is cropped to W x H) */
     int32_t height;
-    int32_t out_pitch;    /* bytes per output row, >= 4*width (BGR24: 3*width), multiple of 4 */
+    int32_t out_pitch;    /* bytes per output row, >= 4*width (BGR24: 3*width), multiple of 4;
+                           * RGB24: >= 3*width, planar RGB: >= width, any value (see hjd_out_format) */
     int32_t sampling;     /* enum hjd_sampling (not HJD_OTHER) */
     int32_t qt_index[3];  /* per component (Y, Cb, Cr): index into the qtable set */
-    int32_t out_format;   /* HJD_OUT_BGRX (0) or HJD_OUT_BGR24; the same for all frames of a plan */
+    int32_t out_format;   /* enum hjd_out_format (HJD_OUT_BGRX = 0); the same for all frames of a plan */
 } hjd_frame;
 
 typedef struct hjd_ctx hjd_ctx;
@@ -126,7 +145,8 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
 int hjd_plan_destroy(hjd_plan* plan);
 /* Tuning hook: kernel variant bits (0 = default).  bit 0: plain instead of
  * non-temporal output stores; bit 1: workgroup-interleaved task order.
- * Results are identical for every variant. */
+ * Results are identical for every variant.  BGRX only: a BGR24 plan fails at
+ * launch, an RGB24 / planar RGB plan here (HJD_E_INVALID). */
 int hjd_plan_set_variant(hjd_plan* plan, int variant);
 int hjd_plan_set_kernel(hjd_plan* plan, int mode);   /* hjd_kernel_mode */
 /* Pin the persistent kernel's task chunk without hjd_plan_autotune: exactly

@@ -117,8 +117,10 @@ int hjd_stream_busy(hjd_stream* s, int64_t* h2d_busy_ns, int64_t* kernel_busy_ns
  * (0: unknown topology, no binding). */
 int hjd_debug_worker_cpus(const char* sysfs_root, const char* bus, const char* const* gpus, int ngpus,
                           int only_allowed, int32_t* cpus, int capacity, int32_t* ncpus);
-/* Pixel format of subsequent submits: HJD_OUT_BGRX (default) or HJD_OUT_BGR24
- * (d_out 4-byte aligned, pitch >= 3*width); jobs already queued keep theirs. */
+/* Pixel format of subsequent submits: HJD_OUT_BGRX (default), HJD_OUT_BGR24
+ * (d_out 4-byte aligned, pitch >= 3*width), HJD_OUT_RGB24 (any d_out, any
+ * pitch >= 3*width) or HJD_OUT_RGB_PLANAR (any d_out, any pitch >= width; the
+ * three planes at d_out + c * pitch * height); jobs already queued keep theirs. */
 int hjd_stream_set_output_format(hjd_stream* s, int out_format);
 
 /* ---- GPU entropy decoding ----------------------
@@ -164,9 +166,13 @@ int hjd_gdec_decode_coefs(hjd_gdec* g, const uint8_t* const* datas, const size_t
  * Returns HJD_E_INVALID if any frame's entropy data was corrupt. */
 int hjd_gdec_sync(hjd_gdec* g, int32_t* status);
 
-/* Pixel format of the following hjd_gdec_decode calls: HJD_OUT_BGRX (default)
- * or HJD_OUT_BGR24 (include/hjd.h; 3-byte pixels, d_outs 4-byte aligned,
- * pitches >= 3*width, multiple of 4). */
+/* Pixel format of the following hjd_gdec_decode calls: HJD_OUT_BGRX (default),
+ * HJD_OUT_BGR24 (include/hjd.h; 3-byte pixels, d_outs 4-byte aligned,
+ * pitches >= 3*width, multiple of 4), HJD_OUT_RGB24 (any d_outs, any pitches
+ * >= 3*width) or HJD_OUT_RGB_PLANAR (any d_outs, any pitches >= width; image
+ * i's planes at d_outs[i] + c * pitches[i] * height).  The two RGB formats
+ * take vector stores where pointer and pitch are multiples of 4 and byte
+ * stores otherwise (include/hjd.h). */
 int hjd_gdec_set_output_format(hjd_gdec* g, int out_format);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
@@ -199,8 +205,10 @@ int hjd_gstream_submit_host(hjd_gstream* s, const uint8_t* data, size_t size, vo
  * {images, pixels, host_prep_ns, h2d_bytes, batches}. */
 int hjd_gstream_sync(hjd_gstream* s, int64_t stats[5]);
 /* Pixel format of the stream's outputs (device and host sinks alike):
- * HJD_OUT_BGRX (default) or HJD_OUT_BGR24; with BGR24 the D2H sink moves
- * 3 bytes per pixel.  Only between hjd_gstream_sync and the next submit
+ * HJD_OUT_BGRX (default), HJD_OUT_BGR24, HJD_OUT_RGB24 or
+ * HJD_OUT_RGB_PLANAR; with the 3-byte formats the D2H sink moves 3 bytes per
+ * pixel (planar: 3 * height rows of width bytes, the planes out_pitch *
+ * height apart in h_out).  Only between hjd_gstream_sync and the next submit
  * (HJD_E_STATE otherwise). */
 int hjd_gstream_set_output_format(hjd_gstream* s, int out_format);
 /* Scan bytes the host CPU has read + written so far (destuffing into pinned

@@ -20,6 +20,8 @@ from .backend import (  # noqa: E402
     OUT_BGR24,
     OUT_BGRX,
     OUT_BYTES,
+    OUT_RGB24,
+    OUT_RGB_PLANAR,
     GRAY,
     YUV411_H4V1,
     YUV420,
@@ -52,5 +54,5 @@ __all__ = [
     "parse", "pinned_bytes",
     "Context", "FrameSpec", "Plan", "autotune_cache_clear", "decode_frame", "device_count", "frame_blocks", "mcu_geometry", "worker_cpus", "cpu_share",
     "device_worker_cpus", "stream_worker_threads",
-    "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
+    "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -33,12 +33,24 @@ KERNEL_AUTO, KERNEL_PERSISTENT, KERNEL_LATENCY = 0, 1, 2   # include/hjd.h hjd_k
 
 OUT_BGRX = 0    # 4 B/px: B, G, R, 0 (the reference's RGB32 / 32-bpp BMP rows)
 OUT_BGR24 = 1   # 3 B/px: B, G, R (extension: 24-bpp BMP rows)
-OUT_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3}
+OUT_RGB24 = 2   # 3 B/px: R, G, B interleaved (extension: an (H, W, 3) uint8 array)
+OUT_RGB_PLANAR = 3   # three uint8 planes R, G, B at pitch * height (extension: a (3, H, W) uint8 array)
+OUT_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3, OUT_RGB24: 3, OUT_RGB_PLANAR: 3}   # bytes per pixel overall
+_ROW_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3, OUT_RGB24: 3, OUT_RGB_PLANAR: 1}  # bytes per pixel within a row
 
 
 def default_pitch(width: int, out_format: int = OUT_BGRX) -> int:
-    """Tightest legal row pitch: bytes of one row rounded up to 4."""
+    """Tightest legal row pitch: bytes of one row rounded up to 4 (BGRX,
+    BGR24); the RGB formats take any pitch, so theirs is the contiguous one
+    (3*width, planar: width)."""
+    if out_format in (OUT_RGB24, OUT_RGB_PLANAR):
+        return _ROW_BYTES[out_format] * width
     return (OUT_BYTES[out_format] * width + 3) & ~3
+
+
+def out_rows(height: int, out_format: int) -> int:
+    """Rows of `pitch` bytes a frame occupies (planar: three planes)."""
+    return 3 * height if out_format == OUT_RGB_PLANAR else height
 
 
 def mcu_geometry(width: int, height: int, sampling: int):
@@ -202,8 +214,8 @@ class Plan:
         self.coef_elem_bytes = 2 if input_format == IN_Q16_ZIGZAG else 4
         self.coef_elems_needed = max([64 * (f.coef_offset + frame_blocks(f.width, f.height, f.sampling))
                                       for f in self.frames] or [0])
-        self.out_bytes_needed = max([f.out_offset + (f.height - 1) * f.pitch + OUT_BYTES[f.out_format] * f.width
-                                     for f in self.frames] or [0])
+        self.out_bytes_needed = max([f.out_offset + (out_rows(f.height, f.out_format) - 1) * f.pitch +
+                                     _ROW_BYTES[f.out_format] * f.width for f in self.frames] or [0])
 
     def _check_tensor(self, t, what, elem_bytes, nbytes_needed):
         if isinstance(t, int):

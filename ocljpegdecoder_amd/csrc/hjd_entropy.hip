@@ -2645,15 +2645,16 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
     if (d_outs) {   // pixel-kernel records grouped by sampling class (one launch each)
         FrameRecord* recs = reinterpret_cast<FrameRecord*>(h_stage + o.recs);
         int32_t* qtn = reinterpret_cast<int32_t*>(h_stage + o.qt);
-        const int obytes = hjd_internal::out_format_bytes(out_format);
-        const uintptr_t amask = out_format == HJD_OUT_BGRX ? 15 : 3;
+        const int obytes = hjd_internal::out_format_row_bytes(out_format);
+        const uintptr_t amask = hjd_internal::out_format_align_mask(out_format);
+        const int pmask = hjd_internal::out_format_any_alignment(out_format) ? 0 : 3;
         for (int i = 0; i < n; ++i) {
             const Prepared& p = frames[i];
-            if (!d_outs[i] || !pitches || pitches[i] < obytes * p.width || (pitches[i] & 3) ||
+            if (!d_outs[i] || !pitches || pitches[i] < obytes * p.width || (pitches[i] & pmask) ||
                 (reinterpret_cast<uintptr_t>(d_outs[i]) & amask))
                 return set_error(HJD_E_INVALID,
                                  "frame %d: bad output buffer or pitch (BGRX: 16-byte aligned, >= 4*width; "
-                                 "BGR24: 4-byte aligned, >= 3*width)", i);
+                                 "BGR24: 4-byte aligned, >= 3*width; RGB24: >= 3*width; planar RGB: >= width)", i);
             ++nrec[sampling_class(p.sampling)];
         }
         int r[kClasses];
@@ -2667,7 +2668,7 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
             const int64_t t = hjd_internal::make_frame_record(
                 p.width, p.height, p.sampling, static_cast<int64_t>(ef[i].coef_off),
                 static_cast<int64_t>(static_cast<uint8_t*>(d_outs[i]) - out_base[sidx]), pitches[i], qti, &rec,
-                out_format);
+                out_format, reinterpret_cast<uintptr_t>(out_base[sidx]));
             if (t < 0) return static_cast<int>(t);
             rec.task_begin = tasks[sidx];
             tasks[sidx] += t;
@@ -3078,10 +3079,13 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
     if (host && d_outs) {   // D2H sink: pixels of host-output frames back to the caller's memory
         for (int i = 0; i < n; ++i) {
             if (!host[i].host) continue;
-            HJD_HIP(hipMemcpy2DAsync(host[i].host, static_cast<size_t>(host[i].host_pitch), d_outs[i],
-                                     static_cast<size_t>(pitches[i]),
-                                     static_cast<size_t>(host[i].width) * hjd_internal::out_format_bytes(g->out_format),
-                                     static_cast<size_t>(host[i].height), hipMemcpyDeviceToHost, s));
+            // planar: the planes are contiguous at pitch * height on both
+            // sides, so one copy of 3 * height rows moves all three
+            HJD_HIP(hipMemcpy2DAsync(
+                host[i].host, static_cast<size_t>(host[i].host_pitch), d_outs[i], static_cast<size_t>(pitches[i]),
+                static_cast<size_t>(host[i].width) * hjd_internal::out_format_row_bytes(g->out_format),
+                static_cast<size_t>(hjd_internal::out_format_rows(g->out_format, host[i].height)),
+                hipMemcpyDeviceToHost, s));
         }
     }
     if (!b.host_status)
@@ -3706,8 +3710,9 @@ void hjd_gstream::issue_locked(GBatch* b)
         if (b->host_outs[i]) {
             host.push_back(HostCopy{b->host_outs[i], b->pitches[i], p.width, p.height});
             outs.push_back(reinterpret_cast<void*>(scratch_need));   // offset, rebased below
-            pitches.push_back(align_up(static_cast<size_t>(hjd_internal::out_format_bytes(out_format)) * p.width, 16));
-            scratch_need += align_up(static_cast<size_t>(pitches.back()) * p.height, 256);
+            pitches.push_back(align_up(static_cast<size_t>(hjd_internal::out_format_row_bytes(out_format)) * p.width, 16));
+            scratch_need += align_up(static_cast<size_t>(pitches.back()) *
+                                         static_cast<size_t>(hjd_internal::out_format_rows(out_format, p.height)), 256);
         } else {
             host.push_back(HostCopy{nullptr, 0, p.width, p.height});
             outs.push_back(b->outs[i]);
@@ -3819,7 +3824,7 @@ static int gstream_submit(hjd_gstream* st, const uint8_t* data, size_t size, voi
     hjd_internal::ScanHeader h;
     int rc = hjd_internal::parse_scan_header(data, size, &h);
     if (rc) return rc;
-    if (out_pitch < hjd_internal::out_format_bytes(st->out_format) * h.width)
+    if (out_pitch < hjd_internal::out_format_row_bytes(st->out_format) * h.width)
         return set_error(HJD_E_INVALID, "output pitch too small");
     const size_t need = h.extra_scans > 0 ? data_need(size) : align_up(size + kDataPad, 16);
     std::lock_guard<std::mutex> api(st->api_mu);
@@ -3871,8 +3876,10 @@ static int gstream_submit(hjd_gstream* st, const uint8_t* data, size_t size, voi
 
 int hjd_gstream_submit(hjd_gstream* st, const uint8_t* data, size_t size, void* d_out, int32_t out_pitch)
 {
-    const uintptr_t amask = st && st->out_format == HJD_OUT_BGR24 ? 3 : 15;
-    if (!st || !data || !d_out || out_pitch <= 0 || (out_pitch & 3) || (reinterpret_cast<uintptr_t>(d_out) & amask))
+    const int fmt = st ? st->out_format : HJD_OUT_BGRX;
+    const uintptr_t amask = hjd_internal::out_format_align_mask(fmt);
+    const int pmask = hjd_internal::out_format_any_alignment(fmt) ? 0 : 3;
+    if (!st || !data || !d_out || out_pitch <= 0 || (out_pitch & pmask) || (reinterpret_cast<uintptr_t>(d_out) & amask))
         return set_error(HJD_E_INVALID, "invalid submit arguments (d_out must be 16-byte (BGR24: 4-byte) aligned)");
     return gstream_submit(st, data, size, d_out, nullptr, out_pitch);
 }

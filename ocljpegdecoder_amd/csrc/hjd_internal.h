@@ -43,9 +43,10 @@ struct FrameRecord {
 };
 
 // Fill a one-frame record (task_begin 0); returns the frame's task count, or
-// a negative status for an unsupported geometry.  out_format: HJD_OUT_*.
+// a negative status for an unsupported geometry.  out_format: HJD_OUT_*;
+// base_bits: low bits of the address out_base is relative to (out_vector_ok).
 int64_t make_frame_record(int width, int height, int sampling, int64_t coef_base, int64_t out_base, int pitch,
-                          const int qt_index[3], FrameRecord* rec, int out_format = 0);
+                          const int qt_index[3], FrameRecord* rec, int out_format = 0, uintptr_t base_bits = 0);
 
 // Launch the fused kernel on device-resident frame records / natural-order
 // qtables (no host synchronisation, safe to call from any host thread).
@@ -53,13 +54,39 @@ int launch_decode(int device, int num_cu, int sampling, int input_format, int va
                   const int32_t* d_qt_nat, const FrameRecord* d_frames, int nframes, int64_t tasks, void* d_out,
                   void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0);
 
-// Bytes per output pixel of an HJD_OUT_* format (0 if unknown).
-inline int out_format_bytes(int out_format) { return out_format == 0 ? 4 : out_format == 1 ? 3 : 0; }
+// Bytes per output pixel of an HJD_OUT_* format overall (0 if unknown).
+inline int out_format_bytes(int out_format)
+{
+    return out_format == 0 ? 4 : out_format >= 1 && out_format <= 3 ? 3 : 0;
+}
+
+// Bytes per pixel within one output row: planar rows hold one component.
+inline int out_format_row_bytes(int out_format) { return out_format == 3 ? 1 : out_format_bytes(out_format); }
+
+// Rows of `out_pitch` bytes a frame of `height` pixel rows occupies (planar:
+// the three planes follow each other at out_pitch * height).
+inline int64_t out_format_rows(int out_format, int height)
+{
+    return out_format == 3 ? 3 * static_cast<int64_t>(height) : height;
+}
+
+// HJD_OUT_RGB24 / HJD_OUT_RGB_PLANAR: any pitch, offset and pointer are legal
+// (the others need 4-byte pitches and 4- or 16-byte aligned rows).
+inline bool out_format_any_alignment(int out_format) { return out_format == 2 || out_format == 3; }
+
+// Required alignment mask of an output pointer / offset of this format.
+inline uintptr_t out_format_align_mask(int out_format)
+{
+    return out_format == 0 ? 15 : out_format == 1 ? 3 : 0;
+}
 
 // Rows of this format can take the kernel's full-width vector stores.
-inline bool out_vector_ok(int out_format, int64_t pitch, int64_t out_base)
+// out_base: the frame's offset; base_bits: low bits of the address out_base
+// is relative to, where that address is not known to be 16-byte aligned.
+inline bool out_vector_ok(int out_format, int64_t pitch, int64_t out_base, uintptr_t base_bits = 0)
 {
-    return out_format == 1 ? ((pitch | out_base) & 3) == 0 : ((pitch | out_base) & 15) == 0;
+    const int64_t bits = pitch | out_base | static_cast<int64_t>(base_bits & 15);
+    return out_format == 0 ? (bits & 15) == 0 : (bits & 3) == 0;
 }
 
 // Parsed header of one sequential scan as the GPU entropy path needs it

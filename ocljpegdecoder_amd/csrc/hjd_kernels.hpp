@@ -48,7 +48,7 @@ struct FrameDev {
     int32_t mcu_w;       // MCUs per MCU row
     int32_t strips;      // tasks per MCU row
     int32_t qt[3];       // natural-order table index per component
-    int32_t vec_ok;      // 1: 16-byte aligned rows -> dwordx4 stores
+    int32_t vec_ok;      // 1: 16-byte aligned rows -> dwordx4 stores (3-byte and planar formats: 4-byte aligned)
 };
 static_assert(sizeof(FrameDev) == 64, "FrameDev layout");
 
@@ -191,8 +191,14 @@ constexpr int kVarD16 = 128;
 // block read the same words: no LDS bank conflicts), the same instructions as
 // the product -- what the zigzag gather's conflicts cost.
 constexpr int kAblGatherBroadcast = 256;
+// Output format bits (HJD_OUT_RGB24, HJD_OUT_RGB_PLANAR): 3-byte R,G,B
+// pixels, or three byte planes R, G, B whose rows lie `plane` bytes apart
+// (plane = pitch * height, wave-uniform, 64-bit).
+constexpr int kOutRgb24 = 512;
+constexpr int kOutPlanar = 1024;
+// Bytes per pixel within one output row (planar: of one plane's row).
 template <int kVariant>
-constexpr int kOutBytes = (kVariant & kOutBgr24) != 0 ? 3 : 4;
+constexpr int kOutBytes = (kVariant & kOutPlanar) != 0 ? 1 : (kVariant & (kOutBgr24 | kOutRgb24)) != 0 ? 3 : 4;
 
 // 4 horizontally adjacent pixels (BGRX words p0..p3) at row + loff.  `row` is wave-uniform
 // (SGPRs) and loff a 32-bit per-lane byte offset, so the store uses the
@@ -202,10 +208,15 @@ constexpr int kOutBytes = (kVariant & kOutBgr24) != 0 ? 3 : 4;
 // re-read by the kernel); otherwise per-pixel guarded dword stores (x = the
 // first pixel's column).  BGR24: the four pixels are repacked into 12 bytes
 // (three v_perm) and stored as one dwordx3 (rows 4-byte aligned), or as
-// guarded bytes on edge strips.
+// guarded bytes on edge strips.  RGB24: the same with the selectors that
+// exchange R and B.  Planar: the four pixels' R bytes are packed into one
+// dword, likewise G and B (seven v_perm), and stored as one dword to each of
+// the three plane rows row + c * plane (each base wave-uniform, in SGPRs); or
+// guarded bytes.  kFull of the RGB formats needs 4-byte aligned rows (and
+// planes) only; their edge path stores bytes and takes any alignment.
 template <bool kFull, int kVariant = 0>
 __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff, int x, int width, uint32_t p0,
-                                       uint32_t p1, uint32_t p2, uint32_t p3)
+                                       uint32_t p1, uint32_t p2, uint32_t p3, int64_t plane = 0)
 {
     // Pin the row base in SGPRs as a global (addrspace 1) pointer and the lane
     // offset as a 32-bit VGPR in this block: otherwise LLVM hoists
@@ -222,7 +233,52 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff,
         asm volatile("" ::"v"(p0), "v"(p1), "v"(p2), "v"(p3));
         return;
     }
-    if constexpr ((kVariant & kOutBgr24) != 0) {
+    if constexpr ((kVariant & kOutPlanar) != 0) {
+        gbyte* grow_g = grow + plane;
+        gbyte* grow_b = grow_g + plane;
+        asm("" : "+s"(grow_g));
+        asm("" : "+s"(grow_b));
+        if constexpr (kFull) {
+            const uint32_t bg01 = perm(p1, p0, 0x05010400u);   // b0 b1 g0 g1
+            const uint32_t bg23 = perm(p3, p2, 0x05010400u);   // b2 b3 g2 g3
+            const uint32_t r01 = perm(p1, p0, 0x0c0c0602u);    // r0 r1 0 0
+            const uint32_t r23 = perm(p3, p2, 0x0c0c0602u);    // r2 r3 0 0
+            __builtin_nontemporal_store(perm(r23, r01, kSelLoLo), (gword*)(grow + loff));     // r0 r1 r2 r3
+            __builtin_nontemporal_store(perm(bg23, bg01, kSelHiHi), (gword*)(grow_g + loff)); // g0 g1 g2 g3
+            __builtin_nontemporal_store(perm(bg23, bg01, kSelLoLo), (gword*)(grow_b + loff)); // b0 b1 b2 b3
+        } else {
+            gbyte* dr = grow + loff;
+            gbyte* dg = grow_g + loff;
+            gbyte* db = grow_b + loff;
+            const uint32_t px[4] = {p0, p1, p2, p3};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < width) {
+                    dr[k] = static_cast<uint8_t>(px[k] >> 16);
+                    dg[k] = static_cast<uint8_t>(px[k] >> 8);
+                    db[k] = static_cast<uint8_t>(px[k]);
+                }
+        }
+    } else if constexpr ((kVariant & kOutRgb24) != 0) {
+        if constexpr (kFull) {
+            typedef unsigned int u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+            typedef __attribute__((address_space(1))) u32x3 gvec3;
+            const u32x3 v = {perm(p1, p0, 0x06000102u),    // r0 g0 b0 r1
+                             perm(p2, p1, 0x05060001u),    // g1 b1 r2 g2
+                             perm(p3, p2, 0x04050600u)};   // b2 r3 g3 b3
+            __builtin_nontemporal_store(v, (gvec3*)dst);
+        } else {
+            gbyte* d8 = (gbyte*)dst;
+            const uint32_t px[4] = {p0, p1, p2, p3};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < width) {
+                    d8[3 * k] = static_cast<uint8_t>(px[k] >> 16);
+                    d8[3 * k + 1] = static_cast<uint8_t>(px[k] >> 8);
+                    d8[3 * k + 2] = static_cast<uint8_t>(px[k]);
+                }
+        }
+    } else if constexpr ((kVariant & kOutBgr24) != 0) {
         if constexpr (kFull) {
             typedef unsigned int u32x3 __attribute__((ext_vector_type(3), aligned(4)));
             typedef __attribute__((address_space(1))) u32x3 gvec3;
@@ -271,12 +327,12 @@ template <bool kCheck, int kVariant, bool kFull>
 __device__ __forceinline__ void emit_row4(uint8_t* __restrict__ row, uint32_t loff, int xa, int width, uint32_t y01,
                                           uint32_t y23, const ChromaPair& p01, const ChromaPair& p23,
                                           const ChromaTerms* c0, const ChromaTerms* c1, const ChromaTerms* c2,
-                                          const ChromaTerms* c3)
+                                          const ChromaTerms* c3, int64_t plane)
 {
     uint32_t q0, q1, q2, q3;
     pixels2<kCheck>(y01, p01, c0, c1, q0, q1);
     pixels2<kCheck>(y23, p23, c2, c3, q2, q3);
-    store4<kFull, kVariant>(row, loff, xa, width, q0, q1, q2, q3);
+    store4<kFull, kVariant>(row, loff, xa, width, q0, q1, q2, q3, plane);
 }
 
 // kStride / u0: this wave converts colour units u0, u0 + kStride, ... of the
@@ -293,6 +349,8 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
     const int ylane = 2 * (lane >> 5);   // this half-wave's row offset
     const uint32_t loff = static_cast<uint32_t>(x0 * kPx) + static_cast<uint32_t>(ylane) * static_cast<uint32_t>(pitch);
     uint8_t* const strip = out + static_cast<int64_t>(y_base) * pitch + static_cast<int64_t>(x_base) * kPx;
+    // planar: bytes between the planes' rows (wave-uniform, 64-bit: 2 * plane can pass 2^32)
+    const int64_t plane = (kVariant & kOutPlanar) != 0 ? static_cast<int64_t>(pitch) * height : 0;
     if constexpr (kSampling == 1) {
         const int m = cg >> 2;        // MCU within strip
         const int xm = x0 & 15;       // x within MCU: 0,4,8,12
@@ -320,16 +378,16 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int ya0 = y_base + y0;
             if (__builtin_amdgcn_ballot_w64((p0.flagged | p1.flagged) != 0)) {   // wave-uniform, rare
                 if (kFull || ya0 < height)
-                    emit_row4<true, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1);
+                    emit_row4<true, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane);
                 if (kFull || ya0 + 1 < height)
                     emit_row4<true, kVariant, kFull>(row0 + pitch, loff, xa, width, yb.x, yb.y, p0, p1, &c0, &c0, &c1,
-                                                     &c1);
+                                                     &c1, plane);
             } else {
                 if (kFull || ya0 < height)
-                    emit_row4<false, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1);
+                    emit_row4<false, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane);
                 if (kFull || ya0 + 1 < height)
                     emit_row4<false, kVariant, kFull>(row0 + pitch, loff, xa, width, yb.x, yb.y, p0, p1, &c0, &c0,
-                                                      &c1, &c1);
+                                                      &c1, &c1, plane);
             }
         }
     } else if constexpr (kSampling == 0) {
@@ -362,10 +420,10 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
                 if (kFull || ya < height) {
                     if (__builtin_amdgcn_ballot_w64((p01.flagged | p23.flagged) != 0))
                         emit_row4<true, kVariant, kFull>(row, loff, xa, width, sy.x, sy.y, p01, p23, &c0, &c1, &c2,
-                                                         &c3);
+                                                         &c3, plane);
                     else
                         emit_row4<false, kVariant, kFull>(row, loff, xa, width, sy.x, sy.y, p01, p23, &c0, &c1, &c2,
-                                                          &c3);
+                                                          &c3, plane);
                 }
             }
         }
@@ -398,9 +456,9 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const bool flagged = __builtin_amdgcn_ballot_w64((p0.flagged | p1.flagged) != 0) != 0;
             if (kFull || y_base + y < height) {
                 if (flagged)
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane);
             }
         }
     } else if constexpr (kSampling == 4) {
@@ -427,9 +485,9 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int xu = x_base + lane * 4;
             if (kFull || y_base + y < height) {
                 if (__builtin_amdgcn_ballot_w64(p0.flagged != 0))
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane);
             }
         }
     } else if constexpr (kSampling == 5) {
@@ -466,17 +524,17 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int ya = y_base + y0;
             if (__builtin_amdgcn_ballot_w64((p01.flagged | p23.flagged) != 0)) {   // wave-uniform, rare
                 if (kFull || ya < height)
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2, &c3);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2, &c3, plane);
                 if (kFull || ya + 1 < height)
                     emit_row4<true, kVariant, kFull>(strip, lo + static_cast<uint32_t>(pitch), xu, width, syb.x,
-                                                     syb.y, p01, p23, &c0, &c1, &c2, &c3);
+                                                     syb.y, p01, p23, &c0, &c1, &c2, &c3, plane);
             } else {
                 if (kFull || ya < height)
                     emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2,
-                                                      &c3);
+                                                      &c3, plane);
                 if (kFull || ya + 1 < height)
                     emit_row4<false, kVariant, kFull>(strip, lo + static_cast<uint32_t>(pitch), xu, width, syb.x,
-                                                      syb.y, p01, p23, &c0, &c1, &c2, &c3);
+                                                      syb.y, p01, p23, &c0, &c1, &c2, &c3, plane);
             }
         }
     } else {
@@ -499,7 +557,7 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             if (kFull || y_base + y < height)
                 store4<kFull, kVariant>(strip, lo, x_base + cu4 * 4, width, perm(g01, g01, 0x0c000000u),
                                         perm(g01, g01, 0x0c010101u), perm(g23, g23, 0x0c000000u),
-                                        perm(g23, g23, 0x0c010101u));
+                                        perm(g23, g23, 0x0c010101u), plane);
         }
     }
 }

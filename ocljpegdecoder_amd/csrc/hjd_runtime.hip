@@ -134,7 +134,8 @@ constexpr int kStageShift = 8;
 int hjd_internal::ctx_num_cu(const hjd_ctx* ctx) { return ctx->num_cu; }
 
 int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int64_t coef_base, int64_t out_base,
-                                        int pitch, const int qt_index[3], FrameRecord* rec, int out_format)
+                                        int pitch, const int qt_index[3], FrameRecord* rec, int out_format,
+                                        uintptr_t base_bits)
 {
     int mw, mh, bpm, tasks_mcus;
     int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
@@ -152,7 +153,7 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
     d.mcu_w = mw;
     d.strips = (mw + tasks_mcus - 1) / tasks_mcus;
     for (int c = 0; c < 3; ++c) d.qt[c] = qt_index ? qt_index[c] : 0;
-    d.vec_ok = out_vector_ok(out_format, pitch, out_base) ? 1 : 0;
+    d.vec_ok = out_vector_ok(out_format, pitch, out_base, base_bits) ? 1 : 0;
     memcpy(rec, &d, sizeof(d));
     return static_cast<int64_t>(d.strips) * mh;
 }
@@ -168,7 +169,7 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
     SamplingGeom sg;
     if (!sampling_geom(sampling, &sg)) return set_error(HJD_E_INVALID, "unsupported sampling %d", sampling);
     const int grid = grid_blocks > 0 ? grid_blocks : grid_for_chunk(tasks, default_per_wave(sampling, fmt));
-    if (out_format != HJD_OUT_BGRX && out_format != HJD_OUT_BGR24)
+    if (out_format < HJD_OUT_BGRX || out_format > HJD_OUT_RGB_PLANAR)
         return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
     using K = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*);   // latency kernels
     using KP = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*, int64_t, int64_t);
@@ -186,28 +187,30 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
                   hjd::decode_kernel_lat<3, 0, V>, hjd::decode_kernel_lat<3, 1, V>, \
                   hjd::decode_kernel_lat<4, 0, V>, hjd::decode_kernel_lat<4, 1, V>, \
                   hjd::decode_kernel_lat<5, 0, V>, hjd::decode_kernel_lat<5, 1, V>
-        static const K kLat[24] = {HJD_KL(0), HJD_KL(hjd::kOutBgr24)};
+        static const K kLat[48] = {HJD_KL(0), HJD_KL(hjd::kOutBgr24), HJD_KL(hjd::kOutRgb24),
+                                   HJD_KL(hjd::kOutPlanar)};
 #undef HJD_KL
         if (tasks > (int64_t(1) << 31) - 1) return set_error(HJD_E_INVALID, "too many tasks for the latency kernel");
-        const K k = kLat[(out_format == HJD_OUT_BGR24 ? 12 : 0) + ((sg.index << 1) | fmt)];
+        const K k = kLat[12 * out_format + ((sg.index << 1) | fmt)];
         hipLaunchKernelGGL(k, dim3(static_cast<uint32_t>(tasks)), dim3(hjd::kLatThreads), 0,
                            static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
                            reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out));
         HJD_HIP(hipGetLastError());
         return HJD_OK;
     }
-    if (out_format == HJD_OUT_BGR24) {   // [sampling index][input format], default variant
-        static const KP kTable24[12] = {
-            hjd::decode_kernel<0, 0, hjd::kOutBgr24>, hjd::decode_kernel<0, 1, hjd::kOutBgr24>,
-            hjd::decode_kernel<1, 0, hjd::kOutBgr24>, hjd::decode_kernel<1, 1, hjd::kOutBgr24>,
-            hjd::decode_kernel<2, 0, hjd::kOutBgr24>, hjd::decode_kernel<2, 1, hjd::kOutBgr24>,
-            hjd::decode_kernel<3, 0, hjd::kOutBgr24>, hjd::decode_kernel<3, 1, hjd::kOutBgr24>,
-            hjd::decode_kernel<4, 0, hjd::kOutBgr24>, hjd::decode_kernel<4, 1, hjd::kOutBgr24>,
-            hjd::decode_kernel<5, 0, hjd::kOutBgr24>, hjd::decode_kernel<5, 1, hjd::kOutBgr24>};
+    if (out_format != HJD_OUT_BGRX) {   // [output format - 1][sampling index][input format], default variant
+#define HJD_KF(V) hjd::decode_kernel<0, 0, V>, hjd::decode_kernel<0, 1, V>, hjd::decode_kernel<1, 0, V>, \
+                  hjd::decode_kernel<1, 1, V>, hjd::decode_kernel<2, 0, V>, hjd::decode_kernel<2, 1, V>, \
+                  hjd::decode_kernel<3, 0, V>, hjd::decode_kernel<3, 1, V>, hjd::decode_kernel<4, 0, V>, \
+                  hjd::decode_kernel<4, 1, V>, hjd::decode_kernel<5, 0, V>, hjd::decode_kernel<5, 1, V>
+        static const KP kTable24[36] = {HJD_KF(hjd::kOutBgr24), HJD_KF(hjd::kOutRgb24), HJD_KF(hjd::kOutPlanar)};
+#undef HJD_KF
+        static const KP kD16[3] = {hjd::decode_kernel<0, 0, hjd::kOutBgr24 | hjd::kVarD16>,
+                                   hjd::decode_kernel<0, 0, hjd::kOutRgb24 | hjd::kVarD16>,
+                                   hjd::decode_kernel<0, 0, hjd::kOutPlanar | hjd::kVarD16>};
         if ((variant & 3) != 0) return set_error(HJD_E_INVALID, "kernel variants are BGRX-only");
-        KP k24 = kTable24[(sg.index << 1) | fmt];
-        if (sampling == HJD_YUV444 && fmt == 0 && device_d16_gather(device))
-            k24 = hjd::decode_kernel<0, 0, hjd::kOutBgr24 | hjd::kVarD16>;
+        KP k24 = kTable24[12 * (out_format - 1) + ((sg.index << 1) | fmt)];
+        if (sampling == HJD_YUV444 && fmt == 0 && device_d16_gather(device)) k24 = kD16[out_format - 1];
         hipLaunchKernelGGL(k24, dim3(grid), dim3(hjd::kGroupThreads), 0,
                            static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
                            reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out),
@@ -350,6 +353,9 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
     const int out_format = nframes > 0 ? frames[0].out_format : HJD_OUT_BGRX;
     const int obytes = hjd_internal::out_format_bytes(out_format);
     if (!obytes) return fail(HJD_E_INVALID, "unknown output format %d", out_format);
+    const int rbytes = hjd_internal::out_format_row_bytes(out_format);
+    // BGRX / BGR24: 4-byte pitches and offsets; the RGB formats take any
+    const uint64_t amask = hjd_internal::out_format_any_alignment(out_format) ? 0 : 3;
     for (int i = 0; i < nframes; ++i) {
         const hjd_frame& f = frames[i];
         int mw, mh, bpm, tasks_mcus;
@@ -359,7 +365,7 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
             return fail(HJD_E_INVALID, "frame %d: mixed sampling in one plan (use one plan per sampling)", i);
         if (f.out_format != out_format)
             return fail(HJD_E_INVALID, "frame %d: mixed output formats in one plan (use one plan per format)", i);
-        if (f.out_pitch < static_cast<int64_t>(obytes) * f.width || (f.out_pitch & 3) || (f.out_offset & 3))
+        if (f.out_pitch < static_cast<int64_t>(rbytes) * f.width || (f.out_pitch & amask) || (f.out_offset & amask))
             return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
         FrameDev& d = fd[i];
         if (input_format == HJD_IN_Q16_ZIGZAG) {
@@ -431,6 +437,8 @@ int hjd_plan_set_variant(hjd_plan* plan, int variant)
 {
     if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
     if (variant < 0 || variant > 3) return fail(HJD_E_INVALID, "unknown kernel variant %d", variant);
+    if (variant != 0 && hjd_internal::out_format_any_alignment(plan->out_format))
+        return fail(HJD_E_INVALID, "kernel variants are BGRX-only");
     plan->variant = variant;
     return HJD_OK;
 }

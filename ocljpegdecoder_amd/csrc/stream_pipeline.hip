@@ -135,7 +135,7 @@ int hjd_stream::issue(const Job& job, int rc, const hjd_jpeg_info& info)
 {
     const int s = static_cast<int>(job.index % nslots);
     uint8_t* h = host[s];
-    if (rc == HJD_OK && job.pitch < hjd_internal::out_format_bytes(job.out_format) * info.width)
+    if (rc == HJD_OK && job.pitch < hjd_internal::out_format_row_bytes(job.out_format) * info.width)
         rc = set_error(HJD_E_INVALID, "output pitch too small");
 
     const size_t coef_bytes = rc == HJD_OK ? static_cast<size_t>(info.nblocks) * 128 : 0;
@@ -144,7 +144,8 @@ int hjd_stream::issue(const Job& job, int rc, const hjd_jpeg_info& info)
         FrameRecord rec;
         const int qti[3] = {0, 1, 2};
         tasks = hjd_internal::make_frame_record(info.width, info.height, info.sampling, 0,
-                                                0, job.pitch, qti, &rec, job.out_format);
+                                                0, job.pitch, qti, &rec, job.out_format,
+                                                reinterpret_cast<uintptr_t>(job.d_out));
         if (tasks < 0) rc = static_cast<int>(tasks);
         memcpy(h, &rec, sizeof(rec));
         int32_t* qn = reinterpret_cast<int32_t*>(h + kQtOffset);
@@ -339,8 +340,9 @@ int hjd_stream_destroy(hjd_stream* st)
 int hjd_stream_submit(hjd_stream* st, const uint8_t* data, size_t size, void* d_out, int32_t out_pitch)
 {
     const int fmt = st ? st->out_format.load() : HJD_OUT_BGRX;
-    const uintptr_t amask = fmt == HJD_OUT_BGR24 ? 3 : 15;
-    if (!st || !data || !d_out || out_pitch <= 0 || (out_pitch & 3) || (reinterpret_cast<uintptr_t>(d_out) & amask))
+    const uintptr_t amask = hjd_internal::out_format_align_mask(fmt);
+    const int pmask = hjd_internal::out_format_any_alignment(fmt) ? 0 : 3;
+    if (!st || !data || !d_out || out_pitch <= 0 || (out_pitch & pmask) || (reinterpret_cast<uintptr_t>(d_out) & amask))
         return set_error(HJD_E_INVALID, "invalid submit arguments (d_out must be 16-byte (BGR24: 4-byte) aligned)");
     {
         std::lock_guard<std::mutex> g(st->mu);

@@ -129,18 +129,33 @@ def decode_coefs_batch(datas: Sequence[bytes], nthreads: int = 0,
     return outs
 
 
+def _out_pitch(out, out_format: int) -> int:
+    """Row pitch in bytes of an output array (tensor or numpy): its last
+    dimension, except for an (..., W, 3) uint8 array taking OUT_RGB24 pixels,
+    whose rows are its last two."""
+    item = out.element_size() if hasattr(out, "element_size") else out.itemsize
+    if out_format == 2 and out.ndim >= 3 and out.shape[-1] == 3 and item == 1:   # OUT_RGB24, (H, W, 3)
+        return 3 * out.shape[-2]
+    return out.shape[-1] * item
+
+
 def decode_jpeg(ctx, data: bytes, stream=None, out_format: int = 0):
     """JPEG bytes -> device pixels (host Huffman, then the fused kernel on the
     device): an (H, W) int32 tensor of BGRX words, or with out_format=OUT_BGR24
     an (H, pitch) uint8 tensor of B,G,R bytes (pitch = (3W+3)&~3, the 24-bpp
-    BMP row)."""
+    BMP row), with OUT_RGB24 an (H, W, 3) uint8 tensor and with OUT_RGB_PLANAR
+    a (3, H, W) uint8 tensor (both contiguous)."""
     import torch
-    from .backend import IN_Q16_ZIGZAG, OUT_BGR24, FrameSpec, Plan, default_pitch
+    from .backend import IN_Q16_ZIGZAG, OUT_BGR24, OUT_RGB24, OUT_RGB_PLANAR, FrameSpec, Plan, default_pitch
     coefs, info = decode_coefs(data)
     dev = torch.device("cuda", ctx.device)
     d_coefs = torch.from_numpy(coefs).to(dev)
     if out_format == OUT_BGR24:
         out = torch.empty((info.height, default_pitch(info.width, OUT_BGR24)), dtype=torch.uint8, device=dev)
+    elif out_format == OUT_RGB24:
+        out = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=dev)
+    elif out_format == OUT_RGB_PLANAR:
+        out = torch.empty((3, info.height, info.width), dtype=torch.uint8, device=dev)
     else:
         out = torch.empty((info.height, info.width), dtype=torch.int32, device=dev)
     plan = Plan(ctx, [FrameSpec(info.width, info.height, info.sampling, qt_index=(0, 1, 2), out_format=out_format)],
@@ -160,12 +175,15 @@ class JpegStream:
               "hjd_stream_create")
         self.handle = h
         self._keep = []   # bytes must stay alive until sync
+        self.out_format = 0
         if out_format:
             self.set_output_format(out_format)
 
     def set_output_format(self, out_format: int):
-        """OUT_BGRX or OUT_BGR24 for subsequent submits."""
+        """OUT_BGRX, OUT_BGR24, OUT_RGB24 ((H, W, 3) uint8 outputs) or
+        OUT_RGB_PLANAR ((3, H, W) uint8 outputs) for subsequent submits."""
         check(self.lib.hjd_stream_set_output_format(self.handle, int(out_format)), "hjd_stream_set_output_format")
+        self.out_format = int(out_format)
 
     def submit(self, data: bytes, out, out_pitch: Optional[int] = None):
         src, size, keep = _src(data)
@@ -177,7 +195,7 @@ class JpegStream:
             if not (out.is_cuda and out.is_contiguous()):
                 raise ValueError("out must be a contiguous device tensor")
             ptr = out.data_ptr()
-            out_pitch = out_pitch or out.shape[-1] * out.element_size()
+            out_pitch = out_pitch or _out_pitch(out, self.out_format)
         check(self.lib.hjd_stream_submit(self.handle, src, size, ptr, int(out_pitch)), "hjd_stream_submit")
 
     def sync(self) -> dict:
@@ -269,14 +287,18 @@ class GpuDecoder:
                                        int(sub_bits), ctypes.byref(h)), "hjd_gdec_create")
         self.handle = h
         self._n = 0
+        self.out_format = 0
 
     def set_output_format(self, out_format: int):
-        """OUT_BGRX (default) or OUT_BGR24 for the following decode() calls."""
+        """OUT_BGRX (default), OUT_BGR24, OUT_RGB24 or OUT_RGB_PLANAR for the
+        following decode() calls."""
         check(self.lib.hjd_gdec_set_output_format(self.handle, int(out_format)), "hjd_gdec_set_output_format")
+        self.out_format = int(out_format)
 
     def decode(self, datas: Sequence[bytes], outs, stream=None):
         """outs: contiguous device tensors, one row per image row: (H, W) int32
-        (or (H, pitch/4)) for BGRX, (H, pitch) uint8 for BGR24."""
+        (or (H, pitch/4)) for BGRX, (H, pitch) uint8 for BGR24, (H, W, 3)
+        uint8 for RGB24, (3, H, W) uint8 for planar RGB."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         if len(outs) != n:
@@ -285,10 +307,53 @@ class GpuDecoder:
             if not (o.is_cuda and o.is_contiguous()):
                 raise ValueError("outputs must be contiguous device tensors")
         ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-        pitches = (ctypes.c_int32 * n)(*[o.shape[-1] * o.element_size() for o in outs])
+        pitches = (ctypes.c_int32 * n)(*[_out_pitch(o, self.out_format) for o in outs])
         check(self.lib.hjd_gdec_decode(self.handle, arr_d, arr_s, n, ptrs, pitches, _stream_handle(stream)),
               "hjd_gdec_decode")
         self._n = n
+
+    def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None):
+        """Decode to uint8 RGB tensors: layout "chw" gives (3, H, W) per image
+        (OUT_RGB_PLANAR), "hwc" gives (H, W, 3) (OUT_RGB24).  Without `out`,
+        one new device tensor per image is returned as a list.  With `out`, a
+        contiguous uint8 device tensor (N, 3, H, W) ("chw") or (N, H, W, 3)
+        ("hwc"), image i is decoded into out[i] and `out` is returned;
+        ValueError if an image's size differs from it.  Asynchronous like
+        decode(): call sync() before reading.  The decoder's output format is
+        restored afterwards."""
+        import torch
+        from .backend import OUT_RGB24, OUT_RGB_PLANAR
+        if layout not in ("chw", "hwc"):
+            raise ValueError('layout must be "chw" or "hwc"')
+        chw = layout == "chw"
+        infos = []
+        for d in datas:   # headers only; any input decode() takes (bytes, arrays, pinned tensors)
+            addr, size, _k = _ptr_size(d)
+            c = HjdJpegInfo()
+            check(self.lib.hjd_jpeg_parse(ctypes.cast(addr, _u8p), size, ctypes.byref(c)), "hjd_jpeg_parse")
+            infos.append(JpegInfo.from_c(c))
+        if out is None:
+            dev = torch.device("cuda", self.ctx.device)
+            outs = [torch.empty((3, i.height, i.width) if chw else (i.height, i.width, 3), dtype=torch.uint8,
+                                device=dev) for i in infos]
+        else:
+            if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.ndim == 4
+                    and out.shape[1 if chw else 3] == 3):
+                raise ValueError("out must be a contiguous uint8 device tensor (N, 3, H, W) or (N, H, W, 3)")
+            if out.shape[0] != len(infos):
+                raise ValueError(f"out holds {out.shape[0]} images, {len(infos)} JPEGs given")
+            oh, ow = (out.shape[2], out.shape[3]) if chw else (out.shape[1], out.shape[2])
+            for k, i in enumerate(infos):
+                if (i.height, i.width) != (oh, ow):
+                    raise ValueError(f"image {k} is {i.width}x{i.height}, out is {ow}x{oh}")
+            outs = [out[k] for k in range(len(infos))]
+        prev = self.out_format
+        self.set_output_format(OUT_RGB_PLANAR if chw else OUT_RGB24)
+        try:
+            self.decode(datas, outs, stream)
+        finally:
+            self.set_output_format(prev)
+        return outs if out is None else out
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
@@ -353,12 +418,16 @@ class GpuJpegStream:
                                           int(nslots), int(nthreads), ctypes.byref(h)), "hjd_gstream_create")
         self.handle = h
         self._keep = []
+        self.out_format = 0
         if out_format:
             self.set_output_format(out_format)
 
     def set_output_format(self, out_format: int):
-        """OUT_BGRX or OUT_BGR24 (between sync() and the next submit)."""
+        """OUT_BGRX, OUT_BGR24, OUT_RGB24 ((H, W, 3) uint8 outputs) or
+        OUT_RGB_PLANAR ((3, H, W) uint8 outputs), between sync() and the next
+        submit."""
         check(self.lib.hjd_gstream_set_output_format(self.handle, int(out_format)), "hjd_gstream_set_output_format")
+        self.out_format = int(out_format)
 
     def submit(self, data: bytes, out, out_pitch: Optional[int] = None):
         """out: contiguous device tensor, or a (pinned) host tensor / numpy
@@ -370,13 +439,13 @@ class GpuJpegStream:
             if not out.flags.c_contiguous:
                 raise ValueError("out must be C-contiguous")
             self._keep.append(out)
-            pitch = out_pitch or out.shape[-1] * out.itemsize
+            pitch = out_pitch or _out_pitch(out, self.out_format)
             check(self.lib.hjd_gstream_submit_host(self.handle, src, size, out.ctypes.data, int(pitch)),
                   "hjd_gstream_submit_host")
             return
         if not out.is_contiguous():
             raise ValueError("out must be contiguous")
-        out_pitch = out_pitch or out.shape[-1] * out.element_size()
+        out_pitch = out_pitch or _out_pitch(out, self.out_format)
         if out.is_cuda:
             check(self.lib.hjd_gstream_submit(self.handle, src, size, out.data_ptr(), int(out_pitch)),
                   "hjd_gstream_submit")
