@@ -268,6 +268,15 @@ int hjd_debug_clock_probe(hjd_ctx* ctx, uint64_t* d_out, int nsamples, int inter
  * (the cached probe passed, and HJD_D16 is not 0). */
 int hjd_debug_d16_gather(int device, int* probe_zeroes, int* selected);
 
+/* The library reads its HJD_* environment overrides once, at its first use
+ * (the list: INTEGRATION.md s7, and the kTuning table in csrc/hjd_runtime.hip).
+ * This switches one of them in-process, for tests and tools: `name` is the
+ * environment variable's name, `value` is parsed as that variable's string
+ * would be, and value = NULL restores what the process started with.  The
+ * overrides are process-wide; any thread may call this at any time.  An
+ * unknown name returns HJD_E_INVALID. */
+int hjd_debug_set_tuning(const char* name, const char* value);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,7 @@ SIGNATURES = {
                                         ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "hjd_debug_d16_gather": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p]),
+    "hjd_debug_set_tuning": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p]),
     "hjd_debug_clock_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_void_p]),
 }

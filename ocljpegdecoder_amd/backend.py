@@ -5,6 +5,7 @@ work runs in the HIP kernels of libhjd.so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
@@ -340,6 +341,26 @@ def stream_worker_threads(share: int, world: int, slice_cpus: int) -> int:
 def autotune_cache_clear():
     """Forget every cached hjd_plan_autotune choice of this process."""
     check(_lib.load().hjd_autotune_cache_clear(), "hjd_autotune_cache_clear")
+
+
+def _set_tuning(name: str, value):
+    fn = getattr(_lib.load(), "hjd_debug_set_tuning", None)
+    if fn is None:
+        raise RuntimeError(f"{_lib.LIB_PATH} has no hjd_debug_set_tuning: it cannot switch {name} in-process")
+    check(fn(name.encode(), None if value is None else str(value).encode()), "hjd_debug_set_tuning")
+
+
+@contextlib.contextmanager
+def debug_tuning(name: str, value):
+    """Switch one HJD_* override in-process (hjd_debug_set_tuning): `value` is
+    what the environment variable would hold (None: what the process started
+    with).  On exit the override goes back to what the process started with,
+    so blocks for one name do not nest.  The overrides are process-wide."""
+    _set_tuning(name, value)
+    try:
+        yield
+    finally:
+        _set_tuning(name, None)
 
 
 def decode_frame(ctx: Context, coefs, qt: np.ndarray, width: int, height: int, sampling: int,

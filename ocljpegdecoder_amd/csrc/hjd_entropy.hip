@@ -22,11 +22,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <mutex>
 #include <new>
+#include <thread>
 #include <vector>
 
 #include "hjd.h"
@@ -36,6 +41,7 @@
 
 using hjd_internal::FrameRecord;
 using hjd_internal::set_error;
+using hjd_internal::tuning;
 using namespace hjd::ent;
 
 #define HJD_HIP(expr)                                                                          \
@@ -2069,7 +2075,7 @@ void emulate_spec_sync(const EntBatchDev& b)
             slot = b.cmap[row * kSlotRow + slot];
         }
         if (nrepair) b.status[f] |= kStatusFallback;
-        if (getenv("HJD_EMU_ROUNDS")) {
+        if (tuning().emu_rounds.get()) {
             int novf[kOvfLevels + 2] = {};
             for (uint32_t k = 0; k < n; ++k)
                 for (uint32_t q = 0; q < F.bpm; ++q) {
@@ -2213,7 +2219,7 @@ void emulate(const EntBatchDev& b)
             }
             std::swap(cur, nxt);
             if (!changed) {
-                if (getenv("HJD_EMU_ROUNDS")) fprintf(stderr, "group %u: %d rounds\n", gl, round + 1);
+                if (tuning().emu_rounds.get()) fprintf(stderr, "group %u: %d rounds\n", gl, round + 1);
                 break;
             }
         }
@@ -2304,8 +2310,8 @@ constexpr uint32_t kLeadSteps = sizeof(kLeadLadder) / sizeof(kLeadLadder[0]), kL
                    kLeadBatchesMax = 4096;
 uint32_t spec_lead_bits(uint32_t step)
 {
-    const char* e = getenv("HJD_SPEC_LEAD");   // read per batch (~100 ns): tests switch it in-process
-    return e ? static_cast<uint32_t>(atoi(e)) : kLeadLadder[step < kLeadSteps ? step : kLeadSteps - 1];
+    const auto& e = tuning().spec_lead;
+    return e.is_set() ? static_cast<uint32_t>(e.get()) : kLeadLadder[step < kLeadSteps ? step : kLeadSteps - 1];
 }
 
 // ---------------------------------------------------------------------------
@@ -2425,13 +2431,7 @@ namespace {
 // GPU when the caller's bytes are pinned host memory (hipHostMalloc'd or
 // hipHostRegister'ed, e.g. hjd_host_register), so the host CPU never touches
 // the scan, on the host otherwise.
-int destuff_policy()
-{
-    const char* e = getenv("HJD_DESTUFF");   // read per frame (~100 ns): tests switch it in-process
-    if (e && !strcmp(e, "host")) return 0;
-    if (e && !strcmp(e, "device")) return 2;
-    return 1;
-}
+int destuff_policy() { return static_cast<int>(tuning().destuff.get()); }
 
 bool pinned_host(const void* p, size_t n)
 {
@@ -2455,10 +2455,10 @@ int hjd_gdec::plan_raw(const uint8_t* data, size_t size, RawCursor& cur, int& mo
     mode = kDestuffHost;
     raw_off = 0;
     fits = true;
-    const int pol = gpu ? destuff_policy() : 0;
-    if (pol == 0 || !data) return HJD_OK;
+    const int pol = gpu ? destuff_policy() : hjd_internal::kPolicyHost;
+    if (pol == hjd_internal::kPolicyHost || !data) return HJD_OK;
     const bool pinned = pinned_host(data, size);
-    if (pol == 2) mode = pinned ? kDestuffFromCaller : kDestuffFromStaging;
+    if (pol == hjd_internal::kPolicyDevice) mode = pinned ? kDestuffFromCaller : kDestuffFromStaging;
     else if (pinned) mode = kDestuffFromCaller;
     if (mode == kDestuffHost) return HJD_OK;
     hjd_internal::ScanHeader h;
@@ -2475,7 +2475,7 @@ int hjd_gdec::plan_raw(const uint8_t* data, size_t size, RawCursor& cur, int& mo
     // only the destuffed bytes in the data area
     fits = align_up(raw + kDataPad, 16) + reserve <= data_room &&
            cur.place(data + h.scan_offset, raw, size, mode == kDestuffFromCaller, data_cap(), raw_off, reserve);
-    if (!fits && host_fallback && pol == 1) {   // auto: destuff this one on the host instead
+    if (!fits && host_fallback && pol == hjd_internal::kPolicyAuto) {   // auto: destuff this one on the host instead
         mode = kDestuffHost;
         raw_off = 0;
         fits = true;
@@ -2912,11 +2912,11 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
         }
         if (bits > kDenseBitsPerBlock * blocks) {
             spec = false;
-            const char* e = getenv("HJD_DENSE_SUB_BITS");   // tuning: the dense scans' S
+            const auto& e = tuning().dense_sub_bits;   // tuning: the dense scans' S
             constexpr size_t nt = sizeof(kDenseTiers) / sizeof(kDenseTiers[0]);
             size_t t = 0;
             while (t + 1 < nt && bits > kDenseTiers[t].bits_per_block * blocks) ++t;
-            const uint32_t want = e ? static_cast<uint32_t>(atoi(e)) : kDenseTiers[t].sub_bits;
+            const uint32_t want = e.is_set() ? static_cast<uint32_t>(e.get()) : kDenseTiers[t].sub_bits;
             g->batch_sub_bits = std::max(want, static_cast<uint32_t>(g->caps.sub_bits));
         }
     }
@@ -3152,11 +3152,8 @@ extern "C" {
 // HJD_SUB_BITS overrides it (tuning hook, tools/gpu_subbits_sweep.sh).
 static int default_sub_bits(int max_frames)
 {
-    static const int env = [] {
-        const char* e = getenv("HJD_SUB_BITS");
-        return e ? atoi(e) : 0;
-    }();
-    if (env) return env;
+    const auto& e = tuning().sub_bits;
+    if (e.is_set() && e.get()) return static_cast<int>(e.get());
     return max_frames >= 48 ? 2 * kDefaultSubBits : max_frames <= 2 ? kDefaultSubBits / 2 : kDefaultSubBits;
 }
 
@@ -3171,15 +3168,15 @@ static int default_sub_bits(int max_frames)
 // the critical path and most of the GPU is idle.  HJD_SYNC_SPEC=0/1 overrides.
 static bool spec_sync_default(int max_frames)
 {
-    const char* e = getenv("HJD_SYNC_SPEC");
-    if (e) return atoi(e) != 0;
+    const auto& e = tuning().sync_spec;
+    if (e.is_set()) return e.get() != 0;
     return max_frames <= 2;
 }
 
 static int stream_sub_bits(int max_frames)
 {
-    const char* e = getenv("HJD_SUB_BITS");
-    if (e) return atoi(e);
+    const auto& e = tuning().sub_bits;
+    if (e.is_set()) return static_cast<int>(e.get());
     return max_frames >= 24 ? 4 * kDefaultSubBits : default_sub_bits(max_frames);
 }
 
@@ -3193,7 +3190,8 @@ int hjd_gdec_create(hjd_ctx* ctx, int max_frames, int64_t max_scan_bytes, int64_
     // bits, no longer ~7 serial rounds: shorter subsequences pay there.  One
     // FHD q90 JPEG end to end (profiles/r03_fhd420_jpeg_spec_sweep.json):
     // 0.65 ms at S = 512 / lead-in 512, 0.71 at 1024, 0.69-0.76 at 768.
-    if (sub_bits == 0) sub_bits = spec && !getenv("HJD_SUB_BITS") ? kDefaultSubBits / 4 : default_sub_bits(max_frames);
+    if (sub_bits == 0)
+        sub_bits = spec && !tuning().sub_bits.is_set() ? kDefaultSubBits / 4 : default_sub_bits(max_frames);
     if (sub_bits < 32 || sub_bits > (1 << 20)) return set_error(HJD_E_INVALID, "sub_bits out of range [32, 2^20]");
     *out = nullptr;
     hjd_gdec* g = new (std::nothrow) hjd_gdec;
@@ -3215,7 +3213,7 @@ int hjd_gdec_create(hjd_ctx* ctx, int max_frames, int64_t max_scan_bytes, int64_
 int hjd_gdec_destroy(hjd_gdec* g)
 {
     if (!g) return HJD_OK;
-    if (g->host_calls && getenv("HJD_GDEC_HOST_TIMES"))
+    if (g->host_calls && tuning().gdec_host_times.get())
         fprintf(stderr, "hjd_gdec host us/call over %lld calls: wait_staging %.1f stage %.1f issue %.1f\n",
                 static_cast<long long>(g->host_calls), g->host_us[0] / g->host_calls, g->host_us[1] / g->host_calls,
                 g->host_us[2] / g->host_calls);
@@ -3343,12 +3341,12 @@ int hjd_debug_entropy_syncstats(const uint8_t* data, size_t size, int sub_bits, 
     const uint32_t S = static_cast<uint32_t>(sub_bits);
     // HJD_SYNC_PHASES=n: guesses (k*S, j, 0) for j < n; the first of them to
     // meet the true decode counts (speculation over block-in-MCU positions)
-    const char* ph = getenv("HJD_SYNC_PHASES");
-    const uint32_t nph = std::max(1, std::min(ph ? atoi(ph) : 1, static_cast<int>(F.bpm)));
+    const auto& ph = tuning().sync_phases;
+    const uint32_t nph = std::max(1, std::min(ph.is_set() ? static_cast<int>(ph.get()) : 1, static_cast<int>(F.bpm)));
     // HJD_SYNC_OFFSETS=m: also guesses m-1 bit positions before k*S (offsets
     // 7, 19, 37, 61, ... bits), each with the n phases
-    const char* os = getenv("HJD_SYNC_OFFSETS");
-    const uint32_t noff = std::max(1, os ? atoi(os) : 1);
+    const auto& os = tuning().sync_offsets;
+    const uint32_t noff = std::max(1, os.is_set() ? static_cast<int>(os.get()) : 1);
     static const uint32_t kOffs[] = {0, 7, 19, 37, 61, 91, 127, 169, 217, 271, 331, 397};
     for (uint32_t k = 1; static_cast<uint64_t>(k) * S < p.data_bits; ++k) {
         int bin = nbins - 1;
@@ -3520,8 +3518,8 @@ int hjd_debug_entropy_emulate(const uint8_t* data, size_t size, int sub_bits, in
     hjd_gdec g;
     g.gpu = false;
     g.caps = make_caps(1, static_cast<int64_t>(size), std::max<int64_t>(capacity_blocks, 1), sub_bits);
-    const char* se = getenv("HJD_SYNC_SPEC");   // the emulation takes the round-based sync unless asked
-    g.spec = se && atoi(se) != 0;
+    const auto& se = tuning().sync_spec;   // the emulation takes the round-based sync unless asked
+    g.spec = se.is_set() && se.get() != 0;
     int rc = gdec_alloc(&g);
     if (rc) return rc;
     struct Free {
@@ -3583,13 +3581,6 @@ int hjd_debug_entropy_emulate(const uint8_t* data, size_t size, int sub_bits, in
 // rotate, each on its own HIP stream, so one batch's upload overlaps another's
 // kernels); the thread that completes a closed batch issues it.
 // ---------------------------------------------------------------------------
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <thread>
-
 namespace {
 
 struct GBatch {
@@ -3792,9 +3783,8 @@ int hjd_gstream_create(hjd_ctx* ctx, int max_frames, int64_t max_scan_bytes, int
     st->slot_batch.assign(nslots, nullptr);
     // NUMA locality: pinned staging is allocated, and the
     // workers run, on the CPUs of the GPU's NUMA node (HJD_NUMA=0 disables).
-    const char* numa_env = getenv("HJD_NUMA");
-    const hjd_internal::CpuSet local = (numa_env && numa_env[0] == '0') ? hjd_internal::CpuSet{}
-                                                                       : hjd_internal::device_local_cpus(st->device);
+    const hjd_internal::CpuSet local =
+        tuning().numa.get() ? hjd_internal::device_local_cpus(st->device) : hjd_internal::CpuSet{};
     const std::vector<int> prev = hjd_internal::bind_current_thread(local);
     for (int s = 0; s < nslots; ++s) {
         int rc = hjd_gdec_create(ctx, max_frames, max_scan_bytes, max_blocks, stream_sub_bits(max_frames),

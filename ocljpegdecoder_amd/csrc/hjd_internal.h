@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <atomic>
 #include <vector>
 
 struct hjd_ctx;
@@ -139,6 +140,26 @@ int ctx_num_cu(const struct ::hjd_ctx* ctx);
 int d16_probe(int device);
 int d16_probe_cached(int device);
 bool d16_gather_selected(int device);
+
+// The HJD_* overrides, one field each (the list, with what each one does, is
+// the table in hjd_runtime.hip).  tuning() parses the environment at its
+// first call and never looks at it again; after that only
+// hjd_debug_set_tuning() changes a field.  Every field is one relaxed atomic,
+// so any thread may read it at any time.
+constexpr int64_t kTuneUnset = INT64_MIN;   // an integer override nobody set: the call site's own choice applies
+struct TuneField {
+    std::atomic<int64_t> v{0};
+    int64_t get() const { return v.load(std::memory_order_relaxed); }
+    bool is_set() const { return get() != kTuneUnset; }
+};
+enum { kPolicyHost = 0, kPolicyAuto = 1, kPolicyDevice = 2 };      // HJD_DESTUFF
+enum { kProbeRun = 0, kProbeFail = 1, kProbeHipFail = 2 };         // HJD_D16_PROBE
+struct Tuning {
+    TuneField destuff, spec_lead, dense_sub_bits, d16, autotune_cache, sub_bits, sync_spec, emu_rounds, sync_phases,
+        sync_offsets, gdec_host_times, numa, stream_pair, lat_tasks, tasks_per_wave, d16_probe, compat_copy,
+        compat_stats, compat_teardown;
+};
+const Tuning& tuning();
 
 }  // namespace hjd_internal
 

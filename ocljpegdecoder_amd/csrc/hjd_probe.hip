@@ -183,8 +183,8 @@ int run_probe(int device)
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess) return probe_failed(0);
     if (hipSetDevice(device) != hipSuccess) return probe_failed(prev);
-    const char* force = getenv("HJD_D16_PROBE");
-    const size_t bytes = (force && strcmp(force, "hipfail") == 0) ? (size_t(1) << 60) : 64 * sizeof(uint32_t);
+    const bool hipfail = hjd_internal::tuning().d16_probe.get() == hjd_internal::kProbeHipFail;
+    const size_t bytes = hipfail ? (size_t(1) << 60) : 64 * sizeof(uint32_t);
     uint32_t* d = nullptr;
     if (hipMalloc(&d, bytes) != hipSuccess) return probe_failed(prev);
     hipStream_t s = nullptr;
@@ -219,8 +219,7 @@ int hjd_internal::d16_probe(int device)
     if (device < 0) return 0;
     if (static_cast<size_t>(device) >= g_probe.size()) g_probe.resize(device + 1, -1);
     if (g_probe[device] >= 0) return g_probe[device];
-    const char* force = getenv("HJD_D16_PROBE");
-    if (force && strcmp(force, "fail") == 0) {
+    if (hjd_internal::tuning().d16_probe.get() == hjd_internal::kProbeFail) {
         g_probe[device] = 0;
         return 0;
     }

@@ -95,16 +95,123 @@ struct hjd_plan {
 
 constexpr int64_t kDefaultLatencyMaxTasks = 1024;   // measured: profiles/r01_latency_kernel.json
 
+// ---------------------------------------------------------------------------
+// Tuning overrides.  kTuning is the list of them: the environment variable's
+// name, the field of hjd_internal::Tuning it fills and how its string is
+// parsed (a null string: the variable is not set).  The environment is read
+// once, when tuning() is first called; hjd_debug_set_tuning() goes through the
+// same rows.  "Per call" overrides act from the next call on a live object,
+// "at create" ones on objects created after the change.
+// ---------------------------------------------------------------------------
+namespace {
+
+using hjd_internal::kTuneUnset;
+using hjd_internal::Tuning;
+
+int64_t parse_int(const char* s) { return s ? atoi(s) : kTuneUnset; }
+int64_t parse_lat_tasks(const char* s) { return s ? atoll(s) : kDefaultLatencyMaxTasks; }
+int64_t parse_tasks_per_wave(const char* s) { return s ? atoll(s) : 0; }
+int64_t parse_not_0(const char* s) { return !(s && s[0] == '0'); }           // on unless the value starts with 0
+int64_t parse_present(const char* s) { return s != nullptr; }                // on when set, to anything
+int64_t parse_flag(const char* s) { return s && *s && strcmp(s, "0") != 0; }   // on when set, not empty, not "0"
+int64_t parse_destuff(const char* s)
+{
+    if (s && !strcmp(s, "host")) return hjd_internal::kPolicyHost;
+    if (s && !strcmp(s, "device")) return hjd_internal::kPolicyDevice;
+    return hjd_internal::kPolicyAuto;
+}
+int64_t parse_d16_probe(const char* s)
+{
+    if (s && !strcmp(s, "fail")) return hjd_internal::kProbeFail;
+    if (s && !strcmp(s, "hipfail")) return hjd_internal::kProbeHipFail;
+    return hjd_internal::kProbeRun;
+}
+int64_t parse_compat_copy(const char* s)   // idct_compat.hip CopyMode
+{
+    return s && !strcmp(s, "staged") ? 1 : s && !strcmp(s, "register") ? 2 : 0;
+}
+
+const struct TuneRow {
+    const char* name;
+    hjd_internal::TuneField Tuning::*field;
+    int64_t (*parse)(const char*);
+} kTuning[] = {
+    // host | auto | device: where a scan's byte stuffing is removed.  Per call (each frame).
+    {"HJD_DESTUFF", &Tuning::destuff, parse_destuff},
+    // Lead-in bits of the speculative sync's runs, instead of the adaptive ladder.  Per call (each batch).
+    {"HJD_SPEC_LEAD", &Tuning::spec_lead, parse_int},
+    // Subsequence bits S of dense scans, instead of the tiers.  Per call (each batch).
+    {"HJD_DENSE_SUB_BITS", &Tuning::dense_sub_bits, parse_int},
+    // 0: the 4:4:4 kernels gather with v_perm even where the d16 probe passed.  Per call (each launch).
+    {"HJD_D16", &Tuning::d16, parse_not_0},
+    // 0: hjd_plan_autotune neither reads nor fills the process-wide cache.  Per call.
+    {"HJD_AUTOTUNE_CACHE", &Tuning::autotune_cache, parse_not_0},
+    // Subsequence bits S of GPU entropy decoders and streams created with sub_bits 0.  At create.
+    {"HJD_SUB_BITS", &Tuning::sub_bits, parse_int},
+    // 0 | 1: round-based or speculative sync, instead of the choice by max_frames.  At create; the
+    // host emulation (off unless 1) takes it per call.
+    {"HJD_SYNC_SPEC", &Tuning::sync_spec, parse_int},
+    // Set: the host emulation prints its sync rounds and overflow levels.  Per call.
+    {"HJD_EMU_ROUNDS", &Tuning::emu_rounds, parse_present},
+    // Guessed block-in-MCU phases / bit offsets of hjd_debug_entropy_sync_check.  Per call.
+    {"HJD_SYNC_PHASES", &Tuning::sync_phases, parse_int},
+    {"HJD_SYNC_OFFSETS", &Tuning::sync_offsets, parse_int},
+    // Set: hjd_gdec_destroy prints the decoder's host time per call.  At destroy.
+    {"HJD_GDEC_HOST_TIMES", &Tuning::gdec_host_times, parse_present},
+    // 0: a stream's workers and pinned staging are not bound to the GPU's NUMA node.  At create.
+    {"HJD_NUMA", &Tuning::numa, parse_not_0},
+    // 0: a stream worker takes one job at a time, not two interleaved.  At create (each worker's start).
+    {"HJD_STREAM_PAIR", &Tuning::stream_pair, parse_not_0},
+    // Most tasks an HJD_KERNEL_AUTO launch gives the latency kernel.  Per call (each launch).
+    {"HJD_LAT_TASKS", &Tuning::lat_tasks, parse_lat_tasks},
+    // > 0: tasks per wave of the throughput kernel, instead of the per-sampling default.  Per call.
+    {"HJD_TASKS_PER_WAVE", &Tuning::tasks_per_wave, parse_tasks_per_wave},
+    // fail | hipfail: the d16 probe reports a half-preserving part / its HIP calls fail.  At the
+    // first hjd_ctx_create of a device (a completed probe is cached).
+    {"HJD_D16_PROBE", &Tuning::d16_probe, parse_d16_probe},
+    // idct.h shim: pageable | staged | register host copies; statistics line per image; the
+    // reference's per-image teardown.  At create (each clidct_create).
+    {"HJD_COMPAT_COPY", &Tuning::compat_copy, parse_compat_copy},
+    {"HJD_COMPAT_STATS", &Tuning::compat_stats, parse_flag},
+    {"HJD_COMPAT_TEARDOWN", &Tuning::compat_teardown, parse_flag},
+};
+constexpr size_t kTuningRows = sizeof(kTuning) / sizeof(kTuning[0]);
+
+struct TuningState {
+    Tuning now;
+    int64_t start[kTuningRows];   // what the environment gave (hjd_debug_set_tuning(name, NULL))
+    TuningState()
+    {
+        for (size_t i = 0; i < kTuningRows; ++i) {
+            start[i] = kTuning[i].parse(getenv(kTuning[i].name));
+            (now.*kTuning[i].field).v.store(start[i], std::memory_order_relaxed);
+        }
+    }
+};
+TuningState& tuning_state()
+{
+    static TuningState s;
+    return s;
+}
+
+}  // namespace
+
+const Tuning& hjd_internal::tuning() { return tuning_state().now; }
+
+extern "C" int hjd_debug_set_tuning(const char* name, const char* value)
+{
+    TuningState& s = tuning_state();
+    for (size_t i = 0; name && i < kTuningRows; ++i)
+        if (!strcmp(name, kTuning[i].name)) {
+            (s.now.*kTuning[i].field).v.store(value ? kTuning[i].parse(value) : s.start[i], std::memory_order_relaxed);
+            return HJD_OK;
+        }
+    return fail(HJD_E_INVALID, "hjd_debug_set_tuning: no override named %s", name ? name : "(null)");
+}
+
 // Launches of at most this many tasks take the latency kernel (one workgroup
 // per task) in HJD_KERNEL_AUTO mode; HJD_LAT_TASKS overrides it (tuning).
-static int64_t latency_max_tasks()
-{
-    static const int64_t v = [] {
-        const char* e = getenv("HJD_LAT_TASKS");
-        return e ? static_cast<int64_t>(atoll(e)) : int64_t(kDefaultLatencyMaxTasks);
-    }();
-    return v;
-}
+static int64_t latency_max_tasks() { return hjd_internal::tuning().lat_tasks.get(); }
 
 // The 4:4:4 kernels gather coefficient pairs with ds_read_u16_d16_hi
 // (hjd::kVarD16), which relies on d16 LDS loads zeroing the other half of
@@ -117,11 +224,9 @@ static int64_t latency_max_tasks()
 // pass.  Launches only read the cached answer.
 bool hjd_internal::d16_gather_selected(int device)
 {
-    const char* e = getenv("HJD_D16");
-    if (e && e[0] == '0') return false;
+    if (!tuning().d16.get()) return false;
     return device >= 0 && hjd_internal::d16_probe_cached(device) == 1;
 }
-static bool device_d16_gather(int device) { return hjd_internal::d16_gather_selected(device); }
 
 static int geometry(int width, int height, int sampling, int& mcu_w, int& mcu_h, int& bpm, int& tasks_mcus);
 static int64_t default_per_wave(int sampling, int fmt);
@@ -210,7 +315,7 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
                                    hjd::decode_kernel<0, 0, hjd::kOutPlanar | hjd::kVarD16>};
         if ((variant & 3) != 0) return set_error(HJD_E_INVALID, "kernel variants are BGRX-only");
         KP k24 = kTable24[12 * (out_format - 1) + ((sg.index << 1) | fmt)];
-        if (sampling == HJD_YUV444 && fmt == 0 && device_d16_gather(device)) k24 = kD16[out_format - 1];
+        if (sampling == HJD_YUV444 && fmt == 0 && hjd_internal::d16_gather_selected(device)) k24 = kD16[out_format - 1];
         hipLaunchKernelGGL(k24, dim3(grid), dim3(hjd::kGroupThreads), 0,
                            static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
                            reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out),
@@ -233,7 +338,7 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
         // [4:2:0, 4:4:4, 4:4:4 d16 gather][stages]
         static const KP kStageK[3][8] = {HJD_ST(1, 0), HJD_ST(0, 0), HJD_ST(0, hjd::kVarD16)};
 #undef HJD_ST
-        const int col = sampling == HJD_YUV420 ? 0 : device_d16_gather(device) ? 2 : 1;   // as the product gathers
+        const int col = sampling == HJD_YUV420 ? 0 : hjd_internal::d16_gather_selected(device) ? 2 : 1;   // as the product gathers
         const KP k = kStageK[col][si];
         hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream), d_coefs,
                            d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
@@ -250,7 +355,7 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
                                  HJD_K4(4, 0), HJD_K4(4, 1), HJD_K4(5, 0), HJD_K4(5, 1)};
 #undef HJD_K4
     KP k = kTable[key];
-    if (sampling == HJD_YUV444 && fmt == 0 && (variant & 2) == 0 && device_d16_gather(device))
+    if (sampling == HJD_YUV444 && fmt == 0 && (variant & 2) == 0 && hjd_internal::d16_gather_selected(device))
         k = (variant & 1) ? hjd::decode_kernel<0, 0, hjd::kVarPlainStores | hjd::kVarD16>
                           : hjd::decode_kernel<0, 0, hjd::kVarD16>;
     hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream),
@@ -481,10 +586,7 @@ int64_t hjd_plan_coef_bytes(const hjd_plan* plan) { return plan ? plan->coef_byt
 // HJD_TASKS_PER_WAVE overrides it (tuning).
 static int64_t default_per_wave(int sampling, int fmt)
 {
-    static const int64_t env = [] {
-        const char* e = getenv("HJD_TASKS_PER_WAVE");
-        return e ? static_cast<int64_t>(atoll(e)) : int64_t(0);
-    }();
+    const int64_t env = hjd_internal::tuning().tasks_per_wave.get();
     if (env > 0) return env;
     if (fmt != 0 || sampling == HJD_GRAY || sampling == HJD_YUV411_H4V1) return 1;
     return sampling == HJD_YUV420 ? 2 : 16;
@@ -572,11 +674,7 @@ struct TuneKey {
 std::mutex g_tune_mu;
 std::map<TuneKey, std::pair<int, int>> g_tune;   // -> (tasks per wave, store bit)
 
-bool tune_cache_enabled()
-{
-    const char* e = getenv("HJD_AUTOTUNE_CACHE");
-    return !(e && e[0] == '0');
-}
+bool tune_cache_enabled() { return hjd_internal::tuning().autotune_cache.get() != 0; }
 }  // namespace
 
 int hjd_autotune_cache_clear(void)

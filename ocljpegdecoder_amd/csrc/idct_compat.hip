@@ -38,6 +38,7 @@
 
 #include "hjd.h"
 #include "hjd_device.hpp"
+#include "hjd_internal.h"
 #include "idct.h"
 
 namespace {
@@ -85,7 +86,7 @@ struct Compat {
     size_t h2d_bytes = 0, d2h_bytes = 0;
     uint64_t fnv = 0;
     int copy_mode = kPageable;
-    bool stats = false, teardown = false, env_read = false;
+    bool stats = false, teardown = false;
 } g;
 
 bool report(const char* what)
@@ -106,18 +107,14 @@ double ms_since(clk::time_point t0)
     return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 }
 
-void read_env()
+// The HJD_COMPAT_* overrides as they stand now (hjd_internal::tuning()): taken
+// per image, so one image is copied and reported in one mode.
+void read_tuning()
 {
-    if (g.env_read) return;
-    g.env_read = true;
-    const char* m = getenv("HJD_COMPAT_COPY");
-    if (m && !strcmp(m, "staged")) g.copy_mode = kStaged;
-    else if (m && !strcmp(m, "register")) g.copy_mode = kRegister;
-    else g.copy_mode = kPageable;
-    const char* st = getenv("HJD_COMPAT_STATS");
-    g.stats = st && *st && strcmp(st, "0");
-    const char* td = getenv("HJD_COMPAT_TEARDOWN");
-    g.teardown = td && *td && strcmp(td, "0");
+    const hjd_internal::Tuning& t = hjd_internal::tuning();
+    g.copy_mode = static_cast<int>(t.compat_copy.get());   // the table's values are CopyMode's
+    g.stats = t.compat_stats.get() != 0;
+    g.teardown = t.compat_teardown.get() != 0;
 }
 
 // Grow-only device buffer.
@@ -298,7 +295,7 @@ void Fast_IDCT(int* block)
 int Initialize_OpenCL_IDCT()
 {
     puts("[ ] Initializing HIP environment");
-    read_env();
+    read_tuning();
     int n = 0;
     if (hjd_device_count(&n) != HJD_OK) {
         report("hjd_device_count");
@@ -321,7 +318,7 @@ int Initialize_OpenCL_IDCT()
 
 bool clidct_create()
 {
-    read_env();
+    read_tuning();
     if (g.device < 0 && Initialize_OpenCL_IDCT() != 0) return false;
     ++g.image_no;
     g.allocs = 0;

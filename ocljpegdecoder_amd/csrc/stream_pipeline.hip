@@ -199,10 +199,7 @@ int hjd_stream::issue(const Job& job, int rc, const hjd_jpeg_info& info)
 // proceed.
 void hjd_stream::worker()
 {
-    static const bool pair = [] {
-        const char* e = getenv("HJD_STREAM_PAIR");
-        return !(e && e[0] == '0');
-    }();
+    const bool pair = hjd_internal::tuning().stream_pair.get() != 0;
     for (;;) {
         Job jobs[2];
         int n = 0;
@@ -297,9 +294,8 @@ int hjd_stream_create(hjd_ctx* ctx, int64_t max_blocks, int nslots, int nthreads
         for (auto* v : {&st->t_h2d0, &st->t_h2d1, &st->t_k0, &st->t_k1})
             if ((e = hipEventCreate(&(*v)[t])) != hipSuccess) return bail("event", e);
     // NUMA-local workers; HJD_NUMA=0 disables
-    const char* numa_env = getenv("HJD_NUMA");
-    const hjd_internal::CpuSet local = (numa_env && numa_env[0] == '0') ? hjd_internal::CpuSet{}
-                                                                       : hjd_internal::device_local_cpus(st->device);
+    const hjd_internal::CpuSet local =
+        hjd_internal::tuning().numa.get() ? hjd_internal::device_local_cpus(st->device) : hjd_internal::CpuSet{};
     for (int t = 0; t < nthreads; ++t)
         st->workers.emplace_back([st, local] {
             hjd_internal::bind_current_thread(local);

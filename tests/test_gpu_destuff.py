@@ -12,6 +12,7 @@ src/decoder.cpp:94-159, and its RST handling, :288-307).
    pinned-memory inputs through GpuDecoder and GpuJpegStream, whose host scan
    bytes must be zero.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -25,9 +26,16 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
-def _device_destuff(monkeypatch):
-    monkeypatch.setenv("HJD_DESTUFF", "device")
-    yield
+def _device_destuff(hjd):
+    with hjd.debug_tuning("HJD_DESTUFF", "device"):
+        yield
+
+
+@pytest.fixture
+def tuning(hjd):
+    """tuning(name, value): hjd.debug_tuning for the rest of the test."""
+    with contextlib.ExitStack() as stack:
+        yield lambda name, value: stack.enter_context(hjd.debug_tuning(name, value))
 
 
 def _u8p(a):
@@ -155,10 +163,10 @@ def _pil_files():
     return out + [d for _, d in E._golden_bytes()]
 
 
-def test_pinned_inputs_gpu_decoder(hjd, ctx, monkeypatch):
+def test_pinned_inputs_gpu_decoder(hjd, ctx, tuning):
     """HJD_DESTUFF=auto (the default): pinned bytes take the device path."""
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     datas = _pil_files()
     pinned = [hjd.pinned_bytes(d) for d in datas]
     infos = [hjd.parse(d) for d in datas]
@@ -174,14 +182,14 @@ def test_pinned_inputs_gpu_decoder(hjd, ctx, monkeypatch):
         assert s & ~1 == 0
 
 
-def test_pinned_scans_in_separate_registrations(hjd, ctx, monkeypatch):
+def test_pinned_scans_in_separate_registrations(hjd, ctx, tuning):
     """Two scans in separately page-locked ranges that lie less than 64 KiB
     apart: the decoder mirrors their distance and tries one DMA over both,
     which crosses the unregistered page between them and is rejected; it then
     copies the scans one by one (torch's pinned blocks can lie this close)."""
     import mmap
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     datas = _pil_files()[:2]
     page = mmap.PAGESIZE
     n1 = -(-len(datas[0]) // page) * page
@@ -256,13 +264,13 @@ def _registered_layout(hjd, datas, gaps, first=5):
 
 
 @pytest.mark.parametrize("policy", ["auto", "device"])
-def test_pinned_separate_registrations_exact_capacity(hjd, ctx, monkeypatch, policy):
+def test_pinned_separate_registrations_exact_capacity(hjd, ctx, tuning, policy):
     """scans in separately page-locked regions at gaps of
     1 B to 60 KiB, decoder capacity exactly the sum of the file sizes (the
     documented sizing): every frame decodes bit-exactly on the device path
     (no host destuff), whatever the gaps cost the mirrored DMA layout."""
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", policy)
+    tuning("HJD_DESTUFF", policy)
     base = _pil_files()
     datas = (base * 3)[:14]
     gaps = [1, 3, 40, 4096 + 5, 61440, 2 * 4096 + 1, 16, 20000, 60 * 1024, 7, 100, 8191, 2]
@@ -289,7 +297,7 @@ def test_pinned_separate_registrations_exact_capacity(hjd, ctx, monkeypatch, pol
         cleanup()
 
 
-def test_pinned_capacity_by_entropy_bytes_falls_back_to_host(hjd, ctx, monkeypatch):
+def test_pinned_capacity_by_entropy_bytes_falls_back_to_host(hjd, ctx, tuning):
     """sized by entropy-coded bytes (the older sizing), pinned
     frames whose raw scans would not fit are destuffed on the host in auto
     mode instead of failing the batch; HJD_DESTUFF=device reports it."""
@@ -303,7 +311,7 @@ def test_pinned_capacity_by_entropy_bytes_falls_back_to_host(hjd, ctx, monkeypat
     infos = [hjd.parse(d) for d in datas]
     total = sum(i.nblocks for i in infos)
     coefs = torch.full((total, 64), 0x5A5A, dtype=torch.int16, device="cuda")
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     with hjd.GpuDecoder(ctx, len(datas), ent, total) as gd:
         offs = gd.decode_coefs(pinned, coefs)
         assert gd.last_bytes()["host_scan_bytes"] > 0
@@ -313,12 +321,12 @@ def test_pinned_capacity_by_entropy_bytes_falls_back_to_host(hjd, ctx, monkeypat
             ref, _ = hjd.decode_coefs(d)
             np.testing.assert_array_equal(host[o:o + i.nblocks], ref)
             assert s & ~1 == 0
-        monkeypatch.setenv("HJD_DESTUFF", "device")
+        tuning("HJD_DESTUFF", "device")
         with pytest.raises(hjd._lib.HjdError):
             gd.decode_coefs(pinned, coefs)
 
 
-def test_pinned_capacity_by_raw_scan_bytes_stays_on_device(hjd, ctx, monkeypatch):
+def test_pinned_capacity_by_raw_scan_bytes_stays_on_device(hjd, ctx, tuning):
     """sized by the files' entropy-coded bytes as they lie in
     the file (stuffing and markers included: size - scan_offset), every pinned
     frame's raw scan fits, so none may fall back to the host destuff -- the
@@ -330,7 +338,7 @@ def test_pinned_capacity_by_raw_scan_bytes_stays_on_device(hjd, ctx, monkeypatch
     infos = [hjd.parse(d) for d in datas]
     total = sum(i.nblocks for i in infos)
     coefs = torch.full((total, 64), 0x5A5A, dtype=torch.int16, device="cuda")
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     with hjd.GpuDecoder(ctx, len(datas), raw, total) as gd:
         offs = gd.decode_coefs(pinned, coefs)
         assert gd.last_bytes()["host_scan_bytes"] == 0
@@ -342,12 +350,12 @@ def test_pinned_capacity_by_raw_scan_bytes_stays_on_device(hjd, ctx, monkeypatch
             assert s & ~1 == 0
 
 
-def test_pinned_input_reusable_on_return(hjd, ctx, monkeypatch):
+def test_pinned_input_reusable_on_return(hjd, ctx, tuning):
     """hjd_gdec_decode* may return before the kernels run, but
     not before the DMA has read the caller's pinned bytes; overwriting them
     right after the call must not change the result."""
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     datas = [E._pil(2048, 1536, 95, 0, seed=41), E._pil(1920, 1080, 90, 2, seed=42)] + _pil_files()[:2]
     infos = [hjd.parse(d) for d in datas]
     total = sum(i.nblocks for i in infos)
@@ -367,12 +375,12 @@ def test_pinned_input_reusable_on_return(hjd, ctx, monkeypatch):
 
 
 @pytest.mark.parametrize("policy", ["auto", "device"])
-def test_small_last_scan_tight_decoder(hjd, ctx, monkeypatch, policy):
+def test_small_last_scan_tight_decoder(hjd, ctx, tuning, policy):
     """the destuff kernels walk a frame's whole last 16-KiB
     tile; a small scan that ends a tightly sized raw area must decode (lanes
     past the scan's end load nothing)."""
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", policy)
+    tuning("HJD_DESTUFF", policy)
     for d in [E._pil(1, 1, 90, 2, seed=3), E._pil(33, 17, 90, 0, seed=4), E._pil(64, 64, 50, 2, seed=5)]:
         info = hjd.parse(d)
         p = hjd.pinned_bytes(d)
@@ -385,9 +393,9 @@ def test_small_last_scan_tight_decoder(hjd, ctx, monkeypatch, policy):
         np.testing.assert_array_equal(coefs.cpu().numpy(), ref)
 
 
-def test_pinned_inputs_stream_no_host_scan_bytes(hjd, ctx, monkeypatch):
+def test_pinned_inputs_stream_no_host_scan_bytes(hjd, ctx, tuning):
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     datas = _pil_files()
     infos = [hjd.parse(d) for d in datas]
     pinned = [hjd.pinned_bytes(d) for d in datas]
@@ -424,11 +432,11 @@ def _arena(hjd, datas, seed):
     return arena, views
 
 
-def test_pinned_arena_runs_gpu_decoder(hjd, ctx, monkeypatch):
+def test_pinned_arena_runs_gpu_decoder(hjd, ctx, tuning):
     """Adjacent files in one pinned arena: their scans are placed at the same
     distance in the raw area (unaligned starts) and move in one DMA per run."""
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     datas = _pil_files()
     arena, views = _arena(hjd, datas, seed=5)
     infos = [hjd.parse(d) for d in datas]
@@ -446,9 +454,9 @@ def test_pinned_arena_runs_gpu_decoder(hjd, ctx, monkeypatch):
     del arena
 
 
-def test_pinned_arena_stream(hjd, ctx, monkeypatch):
+def test_pinned_arena_stream(hjd, ctx, tuning):
     import torch
-    monkeypatch.setenv("HJD_DESTUFF", "auto")
+    tuning("HJD_DESTUFF", "auto")
     datas = _pil_files() * 3
     arena, views = _arena(hjd, datas, seed=9)
     infos = [hjd.parse(d) for d in datas]

@@ -5,6 +5,8 @@ HJD_SYNC_SPEC=1 forces it on every decoder and stream, and every test of
 test_gpu_entropy.py runs again (imported below): coefficients equal the host
 decoder's, pixels the reference's and the oracle's, damaged files flagged.
 The lead-in sweep at small S drives the chain kernel's repair path."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -15,15 +17,22 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
-def _spec_sync(monkeypatch):
-    monkeypatch.setenv("HJD_SYNC_SPEC", "1")
-    yield
+def _spec_sync(hjd):
+    with hjd.debug_tuning("HJD_SYNC_SPEC", "1"):
+        yield
+
+
+@pytest.fixture
+def tuning(hjd):
+    """tuning(name, value): hjd.debug_tuning for the rest of the test."""
+    with contextlib.ExitStack() as stack:
+        yield lambda name, value: stack.enter_context(hjd.debug_tuning(name, value))
 
 
 @pytest.mark.parametrize("lead", [0, 256, 1024])
 @pytest.mark.parametrize("sub_bits", [64, 512])
-def test_lead_in_sweep_on_device(hjd, ctx, monkeypatch, lead, sub_bits):
-    monkeypatch.setenv("HJD_SPEC_LEAD", str(lead))
+def test_lead_in_sweep_on_device(hjd, ctx, tuning, lead, sub_bits):
+    tuning("HJD_SPEC_LEAD", lead)
     datas = [E._pil(1920, 1080, 90, 2, seed=61), E._pil(640, 480, 95, 0, seed=62, restart_marker_blocks=3),
              E._pil(333, 77, 85, 1, seed=63)] + [d for _, d in E._golden_bytes()[:2]]
     got, status = E._coefs_gpu(hjd, ctx, datas, sub_bits)
@@ -33,9 +42,9 @@ def test_lead_in_sweep_on_device(hjd, ctx, monkeypatch, lead, sub_bits):
         assert s & ~1 == 0
 
 
-def test_single_image_default_is_speculative(hjd, ctx, monkeypatch):
+def test_single_image_default_is_speculative(hjd, ctx, tuning):
     """A one-frame decoder takes the speculative sync without the override."""
-    monkeypatch.delenv("HJD_SYNC_SPEC", raising=False)
+    tuning("HJD_SYNC_SPEC", None)
     import torch
     d = E._pil(1920, 1080, 90, 2, seed=64)
     info = hjd.parse(d)
@@ -50,14 +59,14 @@ def test_single_image_default_is_speculative(hjd, ctx, monkeypatch):
                                   O.decode_q16(ref, info.qt, info.width, info.height, info.sampling))
 
 
-def test_lead_ladder_after_a_repair(hjd, ctx, monkeypatch):
+def test_lead_ladder_after_a_repair(hjd, ctx, tuning):
     """A latency decoder whose chain needed a repair (status bit 0) decodes the
     next frames with a longer lead-in (spec_lead_bits' ladder): this frame
     breaks at 512 bits and not at 1536 (pinned by the emulation,
     test_entropy_emulation_spec.py), so the first call reports a repair and
     the next ones none; every call's coefficients are exact."""
-    monkeypatch.delenv("HJD_SYNC_SPEC", raising=False)
-    monkeypatch.delenv("HJD_SPEC_LEAD", raising=False)
+    tuning("HJD_SYNC_SPEC", None)
+    tuning("HJD_SPEC_LEAD", None)
     import torch
     d = E._pil(1920, 1080, 90, 0, seed=5)
     ref, info = hjd.decode_coefs(d)
@@ -73,14 +82,14 @@ def test_lead_ladder_after_a_repair(hjd, ctx, monkeypatch):
 
 
 @pytest.mark.parametrize("q,sub,seed", [(95, 2, 3), (97, 0, 3), (98, 2, 3), (100, 2, 8)])
-def test_dense_single_images_take_the_round_based_tiers(hjd, ctx, monkeypatch, q, sub, seed):
+def test_dense_single_images_take_the_round_based_tiers(hjd, ctx, tuning, q, sub, seed):
     """Latency decoders leave the speculative sync for dense scans (> 200 bits
     per block) and run the round-based one at a longer S than their own
     (kDenseTiers: 1024, 2048, 8192 for these four FHD frames of 232, 301,
     322 and 436 bits per block).  Coefficients and pixels stay exact, the
     decoder reused across calls."""
-    monkeypatch.delenv("HJD_SYNC_SPEC", raising=False)
-    monkeypatch.delenv("HJD_SPEC_LEAD", raising=False)
+    tuning("HJD_SYNC_SPEC", None)
+    tuning("HJD_SPEC_LEAD", None)
     import torch
     import oracle_py as O
     d = E._pil(1920, 1080, q, sub, seed=seed)
@@ -99,12 +108,12 @@ def test_dense_single_images_take_the_round_based_tiers(hjd, ctx, monkeypatch, q
                                   O.decode_q16(ref, info.qt, info.width, info.height, info.sampling))
 
 
-def test_early_pull_and_a_late_destuff_error(hjd, ctx, monkeypatch):
+def test_early_pull_and_a_late_destuff_error(hjd, ctx, tuning):
     """A lone large scan is pulled to the GPU in two parts, the first while the
     host still destuffs (gdec_early_pull).  A wrong RSTn near the end fails the
     host destuff after that first pull; the same decoder then decodes a good
     file exactly (the early pull of the failed call cannot leak into it)."""
-    monkeypatch.delenv("HJD_SYNC_SPEC", raising=False)
+    tuning("HJD_SYNC_SPEC", None)
     import torch
     import oracle_py as O
     good = E._pil(1920, 1080, 95, 2, seed=71, restart_marker_blocks=8)

@@ -113,34 +113,31 @@ def test_16bit_quantisation_tables(hjd, ctx, mode, s):
 
 
 @pytest.mark.parametrize("d16", ["0", "probe"])
-def test_444_gather_forms_vs_oracle(hjd, ctx, monkeypatch, d16):
+def test_444_gather_forms_vs_oracle(hjd, ctx, d16):
     """4:4:4 persistent kernel with both coefficient-pair gathers: the
     ds_read_u16_d16_hi | ds_read_u16 form (hjd::kVarD16, taken where the
     hardware probe passed: MI355X as deployed) and the v_perm form (HJD_D16=0,
     and parts the probe did not pass)."""
     import torch
-    if d16 == "0":
-        monkeypatch.setenv("HJD_D16", "0")
-    else:
-        monkeypatch.delenv("HJD_D16", raising=False)
     arch = torch.cuda.get_device_properties(0).gcnArchName
-    print("device", arch, "d16 gather selected", ctx.d16_gather()[1])
-    assert ctx.d16_gather()[1] == (d16 != "0" and ctx.d16_gather()[0])
-    for (w, h) in SIZES + [(3840, 64)]:
-        coefs, qt = O.synthetic_coefs(w, h, 0, seed=7 * w + h)
-        exp = O.decode_q16(coefs, qt, w, h, 0)
-        for out_format in (0, 1):
-            got = _run(hjd, ctx, coefs, qt, w, h, 0, 1, out_format=out_format)
-            np.testing.assert_array_equal(got, _expect(exp, out_format), err_msg=f"{w}x{h} fmt={out_format}")
+    with hjd.debug_tuning("HJD_D16", "0" if d16 == "0" else None):
+        print("device", arch, "d16 gather selected", ctx.d16_gather()[1])
+        assert ctx.d16_gather()[1] == (d16 != "0" and ctx.d16_gather()[0])
+        for (w, h) in SIZES + [(3840, 64)]:
+            coefs, qt = O.synthetic_coefs(w, h, 0, seed=7 * w + h)
+            exp = O.decode_q16(coefs, qt, w, h, 0)
+            for out_format in (0, 1):
+                got = _run(hjd, ctx, coefs, qt, w, h, 0, 1, out_format=out_format)
+                np.testing.assert_array_equal(got, _expect(exp, out_format), err_msg=f"{w}x{h} fmt={out_format}")
 
 
-def test_d16_probe_selects_gather(hjd, ctx, monkeypatch):
+def test_d16_probe_selects_gather(hjd, ctx):
     """Without an override the 4:4:4 gather form follows the one-wave hardware
     probe (hjd_probe.hip), not the device's ISA name; MI355X as deployed
     (sramecc+) zeroes the d16 load's low half, so the probe passes there."""
     import torch
-    monkeypatch.delenv("HJD_D16", raising=False)
-    zeroes, selected = ctx.d16_gather()
+    with hjd.debug_tuning("HJD_D16", None):
+        zeroes, selected = ctx.d16_gather()
     arch = torch.cuda.get_device_properties(0).gcnArchName
     print("device", arch, "probe zeroes low half", zeroes, "d16 selected", selected)
     assert selected == zeroes

@@ -137,7 +137,7 @@ def test_gpu_entropy_emulation_rejects_progressive(hjd):
 @pytest.mark.parametrize("sub", [0, 1, 2])
 @pytest.mark.parametrize("dri", [0, 4])
 @pytest.mark.parametrize("spec", ["0", "1"])
-def test_gpu_entropy_emulation_multiscan(hjd, monkeypatch, scans, sub, dri, spec):
+def test_gpu_entropy_emulation_multiscan(hjd, scans, sub, dri, spec):
     """The GPU entropy algorithm (host emulation of the kernels) on sequential
     files with several scans: each scan is an entropy frame of its own
     (kLayoutMcu for interleaved scans, kLayoutRaster for one component) and
@@ -145,17 +145,17 @@ def test_gpu_entropy_emulation_multiscan(hjd, monkeypatch, scans, sub, dri, spec
     decoder's, padding blocks zero; round-based and speculative sync, short
     subsequences so that every scan spans several groups."""
     from PIL import Image
-    monkeypatch.setenv("HJD_SYNC_SPEC", spec)
     w, h = 181, 97
     b = io.BytesIO()
     Image.fromarray(_image(w, h, seed=sub + 3)).save(b, format="JPEG", quality=90, subsampling=sub)
     base = b.getvalue()
     c0, _ = hjd.decode_coefs(base)
     data, expect = JW.rewrite_scans(base, c0, scans, dri)
-    for sub_bits in (48, 0):
-        c1, status = hjd.emulate_entropy(data, sub_bits)
-        np.testing.assert_array_equal(c1, expect, err_msg=f"S={sub_bits}")
-        assert status & ~1 == 0
+    with hjd.debug_tuning("HJD_SYNC_SPEC", spec):
+        for sub_bits in (48, 0):
+            c1, status = hjd.emulate_entropy(data, sub_bits)
+            np.testing.assert_array_equal(c1, expect, err_msg=f"S={sub_bits}")
+            assert status & ~1 == 0
 
 
 def test_gpu_entropy_emulation_multiscan_damaged(hjd):

@@ -61,9 +61,9 @@ int main(int argc, char** argv)
             int32_t status = 0;
             // every other mutant through the speculative sync (latency decoders),
             // with a random lead-in of its spec runs
-            setenv("HJD_SYNC_SPEC", i % 2 ? "1" : "0", 1);
+            hjd_debug_set_tuning("HJD_SYNC_SPEC", i % 2 ? "1" : "0");
             const char* leads[] = {"0", "100", "512", "1024"};
-            setenv("HJD_SPEC_LEAD", leads[rng() % 4], 1);
+            hjd_debug_set_tuning("HJD_SPEC_LEAD", leads[rng() % 4]);
             const int rc = hjd_debug_entropy_emulate(buf, d.size(), subs[rng() % 8], coefs, mi.nblocks, &status);
             if (rc == HJD_OK) ++ok;
             else ++corrupt;
