@@ -264,6 +264,29 @@ int hjd_debug_entropy_emulate(const uint8_t* data, size_t size, int sub_bits, in
  * statistics. */
 int hjd_debug_entropy_sync_check(const uint8_t* data, size_t size, int sub_bits, int64_t* runs, int64_t* mismatches);
 
+/* Test hook: the state a decoder carries from call to call (read-only; the
+ * batch_* fields describe the most recent issued call, the lead_* fields the
+ * lead-in ladder as hjd_gdec_sync last left it). */
+typedef struct hjd_gdec_debug_state {
+    uint32_t chain_epoch;        /* look-back tag of the last call that ran ent_chain_lb_kernel (0: none yet) */
+    int32_t batch_spec;          /* the call took the speculative sync (0: the round-based one) */
+    int32_t batch_lookback;      /* the call ran the look-back chain kernel (ent_chain_lb_kernel) */
+    uint32_t batch_chain_chunks; /* chunks of its frame with the most subsequences (that kernel's grid width) */
+    uint32_t batch_sub_bits;     /* its S: the dense tier's, or the decoder's own */
+    uint32_t batch_lead_bits;    /* lead-in of its spec runs (0: round-based sync) */
+    uint32_t lead_step;          /* ladder step of the next speculative call */
+    uint32_t lead_left;          /* clean calls before the ladder steps down */
+    uint32_t lead_hold;          /* the clean run a step down waits for */
+    int32_t lead_stepped_down;   /* the last synced call ended a clean run: the next runs one step lower */
+} hjd_gdec_debug_state;
+int hjd_debug_gdec_state(hjd_gdec* g, hjd_gdec_debug_state* out);
+/* Test hook: sets the host's look-back tag counter (0 .. 2^24 - 1), so a test
+ * reaches the tag's wrap through the ordinary increment of the next calls.
+ * Only the counter: the look-back words on the device keep their tags, and the
+ * next call still advances the counter before it uses it.  HJD_E_STATE while a
+ * call is pending (before hjd_gdec_sync). */
+int hjd_debug_gdec_set_chain_epoch(hjd_gdec* g, uint32_t value);
+
 #ifdef __cplusplus
 }
 #endif

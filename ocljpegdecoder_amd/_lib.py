@@ -56,6 +56,25 @@ class HjdJpegInfo(ctypes.Structure):
     ]
 
 
+class HjdGdecDebugState(ctypes.Structure):
+    """struct hjd_gdec_debug_state (include/hjd_host.h)."""
+    _fields_ = [
+        ("chain_epoch", ctypes.c_uint32),
+        ("batch_spec", ctypes.c_int32),
+        ("batch_lookback", ctypes.c_int32),
+        ("batch_chain_chunks", ctypes.c_uint32),
+        ("batch_sub_bits", ctypes.c_uint32),
+        ("batch_lead_bits", ctypes.c_uint32),
+        ("lead_step", ctypes.c_uint32),
+        ("lead_left", ctypes.c_uint32),
+        ("lead_hold", ctypes.c_uint32),
+        ("lead_stepped_down", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(HjdGdecDebugState) == 40
+
+
 # (name, restype, argtypes) of every exported C symbol declared in include/*.h
 SIGNATURES = {
     # include/hjd.h
@@ -198,6 +217,8 @@ def _bind_host(lib):
                                                      ctypes.POINTER(ctypes.c_int16), ctypes.c_int64, c_i32p]),
         "hjd_debug_entropy_sync_check": (ctypes.c_int, [u8p, ctypes.c_size_t, ctypes.c_int,
                                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+        "hjd_debug_gdec_state": (ctypes.c_int, [vp, ctypes.POINTER(HjdGdecDebugState)]),
+        "hjd_debug_gdec_set_chain_epoch": (ctypes.c_int, [vp, ctypes.c_uint32]),
     })
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name, None)

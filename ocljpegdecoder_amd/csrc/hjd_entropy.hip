@@ -480,7 +480,8 @@ struct EntBatchDev {
     uint32_t* chainfn;           // [frame][chain_chunks][kLbWords] look-back words of the chunks (ent_chain_lb_kernel)
     uint32_t* chain_broken;      // non-null: the look-back chain kernel runs (its words are allocated)
     uint32_t chain_chunks;       // chunks of the frame with the most subsequences (grid width)
-    uint32_t chain_epoch;        // 1 .. 2^24 - 1, new per launch: tags the look-back words (no clearing)
+    uint32_t chain_epoch;        // 1 .. 2^24 - 1, new per launch: tags the look-back words (cleared only when
+                                 // the tag wraps back to 1: gdec_issue)
 };
 
 
@@ -1346,8 +1347,10 @@ __global__ __launch_bounds__(kChainThreads) void ent_chain_kernel(EntBatchDev b)
 // maps into one function (the scan) and publishes it, then thread 0 finds the
 // slot entering the chunk from the nearest published exit before it and the
 // published maps in between (look-back words tagged with the launch's epoch,
-// so nothing is cleared between launches), publishes its own exit, and the
-// chunk writes its rows' slots.  A chunk whose predecessor has published
+// so nothing is cleared between launches; the tag has 24 bits, and the launch
+// that takes it back to 1 clears every word first, gdec_issue, so a word of
+// the launch one full cycle earlier is never read as this launch's),
+// publishes its own exit, and the chunk writes its rows' slots.  A chunk whose predecessor has published
 // nothing yet was dispatched after it (lower blockIdx.x first), so the wait
 // ends.  Each chunk then reduces the chain statistics of the groups it holds:
 // a group's part in its first chunk into agg, its part in the next into agg2
@@ -2361,6 +2364,9 @@ struct hjd_gdec {
     bool staged_by_done = false;        // the last issue pulled its staging: `done` also means staged
     uint32_t batch_sub_bits = 0;        // S of the batch being assembled (0: caps.sub_bits)
     bool batch_spec = false;            // the pending batch took the speculative sync
+    bool batch_lookback = false;        // ... and ran ent_chain_lb_kernel (hjd_debug_gdec_state)
+    uint32_t batch_chain_chunks = 0;    // its chain_chunks
+    uint32_t batch_lead = 0;            // its lead-in in bits (0: round-based sync)
     uint32_t lead_step = 0;             // spec_lead_bits' ladder step for the next batch
     uint32_t lead_left = 0;             // clean batches before it steps down
     uint32_t lead_hold = kLeadBatches;  // the clean run a step down waits for
@@ -2936,23 +2942,38 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
     b.raw = g->d_raw;
     b.tiles = g->d_tiles;
     b.steps_g = g->d_steps;
+    g->batch_lookback = false;
+    g->batch_chain_chunks = b.chain_chunks;
+    g->batch_lead = 0;
+    bool epoch_wrapped = false;
     if (spec) {
         b.spec = g->d_spec;
         b.cand = g->d_cand;
         b.cmap = g->d_cmap;
         b.cslot = g->d_cslot;
         b.spec_lead = spec_lead_bits(g->lead_step);
+        g->batch_lead = b.spec_lead;
         if (static_cast<int64_t>(b.chain_chunks) * b.nframes <= g->chain_fn_rows) {
             b.chainfn = g->d_chainfn;
             b.chain_broken = g->d_chain_broken;
             b.agg2 = g->d_agg2;
+            epoch_wrapped = g->chain_epoch >= 0xFFFFFFu;
             g->chain_epoch = g->chain_epoch % 0xFFFFFFu + 1u;   // 1 .. 2^24 - 1
             b.chain_epoch = g->chain_epoch;
+            g->batch_lookback = true;
         }
     }
     // the device buffers are reused: order this call after the previous one
     // (which may have been issued on another stream)
     if (g->pending) HJD_HIP(hipStreamWaitEvent(s, g->done, 0));
+    // The look-back words are told apart by their tag alone, and a frame's word
+    // row moves with the batch's chain_chunks, so a word may outlive any number
+    // of launches.  When the tag starts over at 1, the words of the launches one
+    // cycle (2^24 - 1 launches) earlier would carry this launch's tag again:
+    // clear them all, behind the previous call and before this call's kernels
+    // (one memset per 16.7 M launches).
+    if (epoch_wrapped)
+        HJD_HIP(hipMemsetAsync(g->d_chainfn, 0, 4 * kLbWords * static_cast<size_t>(g->chain_fn_rows), s));
     bool pull = g->spec;   // latency decoders, every scan host-destuffed (one data run)
     for (const Prepared& p : g->frames) pull = pull && p.destuff == kDestuffHost;
     PullSegs segs{};
@@ -3300,6 +3321,34 @@ int hjd_gdec_sync(hjd_gdec* g, int32_t* status)
     }
     g->pending = false;
     if (bad) return set_error(HJD_E_INVALID, "%d of %d frames had corrupt entropy data", bad, g->nframes_issued);
+    return HJD_OK;
+}
+
+int hjd_debug_gdec_state(hjd_gdec* g, hjd_gdec_debug_state* out)
+{
+    if (!g || !out) return set_error(HJD_E_INVALID, "gdec or out is NULL");
+    out->chain_epoch = g->chain_epoch;
+    out->batch_spec = g->batch_spec;
+    out->batch_lookback = g->batch_lookback;
+    out->batch_chain_chunks = g->batch_chain_chunks;
+    out->batch_sub_bits = g->batch_sub_bits ? g->batch_sub_bits : static_cast<uint32_t>(g->caps.sub_bits);
+    out->batch_lead_bits = g->batch_lead;
+    out->lead_step = g->lead_step;
+    out->lead_left = g->lead_left;
+    out->lead_hold = g->lead_hold;
+    out->lead_stepped_down = g->lead_stepped_down;
+    return HJD_OK;
+}
+
+// Only the host's counter: the words in d_chainfn keep their tags, and the
+// next launch advances the counter as ever (gdec_issue), so the wrap a test
+// reaches this way is the one 2^24 - 1 launches reach.
+int hjd_debug_gdec_set_chain_epoch(hjd_gdec* g, uint32_t value)
+{
+    if (!g) return set_error(HJD_E_INVALID, "gdec is NULL");
+    if (value > 0xFFFFFFu) return set_error(HJD_E_INVALID, "the look-back tag has 24 bits");
+    if (g->pending) return set_error(HJD_E_STATE, "a call is pending: hjd_gdec_sync first");
+    g->chain_epoch = value;
     return HJD_OK;
 }
 

@@ -376,6 +376,19 @@ class GpuDecoder:
         check(self.lib.hjd_gdec_last_bytes(self.handle, ctypes.byref(hb), ctypes.byref(h2d)), "hjd_gdec_last_bytes")
         return {"host_scan_bytes": hb.value, "h2d_bytes": h2d.value}
 
+    def debug_state(self) -> dict:
+        """Test hook: the state the decoder carries from call to call
+        (struct hjd_gdec_debug_state, include/hjd_host.h) as a dict of ints."""
+        st = _lib.HjdGdecDebugState()
+        check(self.lib.hjd_debug_gdec_state(self.handle, ctypes.byref(st)), "hjd_debug_gdec_state")
+        return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+    def debug_set_chain_epoch(self, value: int):
+        """Test hook: sets the host's look-back tag counter (not the words on
+        the device); the next call advances it as ever.  Refused while a call
+        is pending."""
+        check(self.lib.hjd_debug_gdec_set_chain_epoch(self.handle, int(value)), "hjd_debug_gdec_set_chain_epoch")
+
     def sync(self, raise_on_error: bool = True) -> List[int]:
         """Wait for the last call; per-frame status words (include/hjd_host.h:
         bit 0 HJD_GDEC_SEQUENTIAL is informational, a sequential verification

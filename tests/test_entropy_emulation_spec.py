@@ -63,3 +63,18 @@ def test_repair_sets_status_bit_and_long_leads_avoid_it(hjd, tuning):
         got, status = hjd.emulate_entropy(data, 512)
         np.testing.assert_array_equal(got, ref, err_msg=f"lead={lead}")
         assert status == bit, (lead, status)
+
+
+@pytest.mark.parametrize("seed,bits", [(0, (1, 0)), (1, (0, 0))])
+def test_ladder_walk_frames(hjd, tuning, seed, bits):
+    """The two frames that walk the lead-in ladder on the GPU
+    (test_gpu_decoder_reuse.py): at S = 512 the 320x240 q90 4:4:4 frame of
+    seed 0 needs a repair at a lead-in of 512 bits and none at 1536, and the
+    frame of seed 1 is clean at both."""
+    data = E._pil(320, 240, 90, 0, seed=seed)
+    ref, _ = hjd.decode_coefs(data)
+    for lead, bit in zip((512, 1536), bits):
+        tuning("HJD_SPEC_LEAD", lead)
+        got, status = hjd.emulate_entropy(data, 512)
+        np.testing.assert_array_equal(got, ref, err_msg=f"lead={lead}")
+        assert status == bit, (lead, status)

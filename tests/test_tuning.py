@@ -69,6 +69,30 @@ print("read once ok")
     assert r.returncode == 0 and "read once ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_gdec_debug_entries_are_exported_and_reject_null(hjd):
+    """hjd_debug_gdec_state / hjd_debug_gdec_set_chain_epoch (per-decoder state,
+    so not part of the process-wide table above): exported, bound in _lib.py,
+    mirrored on GpuDecoder, and a NULL handle is HJD_E_INVALID without a device."""
+    import ctypes
+    lib = hjd._lib.load()
+    syms = subprocess.run(["nm", "-D", "--defined-only", hjd._lib.LIB_PATH], capture_output=True, text=True,
+                          check=True).stdout.split()
+    st = hjd._lib.HjdGdecDebugState()
+    for name, args in (("hjd_debug_gdec_state", (None, ctypes.byref(st))),
+                       ("hjd_debug_gdec_set_chain_epoch", (None, 5))):
+        assert name in syms and name in hjd._lib.SIGNATURES
+        assert getattr(lib, name).argtypes == hjd._lib.SIGNATURES[name][1]
+        assert getattr(lib, name)(*args) == -1   # HJD_E_INVALID
+        assert "NULL" in hjd._lib.error_string()
+    assert callable(hjd.GpuDecoder.debug_state) and callable(hjd.GpuDecoder.debug_set_chain_epoch)
+    # the struct is the header's: ten 32-bit integers in the declared order
+    text = open(os.path.join(O.REPO, "include", "hjd_host.h")).read()
+    body = text[text.index("typedef struct hjd_gdec_debug_state {"):text.index("} hjd_gdec_debug_state;")]
+    fields = re.findall(r"^\s*(u?int32_t) (\w+);", body, re.M)
+    assert [n for _, n in fields] == [n for n, _ in st._fields_]
+    assert [t for t, _ in fields] == ["uint32_t" if c is ctypes.c_uint32 else "int32_t" for _, c in st._fields_]
+
+
 def test_setter_accepts_exactly_the_documented_names(hjd):
     text = open(os.path.join(O.REPO, "INTEGRATION.md")).read()
     table = text[text.index("### Environment overrides"):]
