@@ -7,7 +7,11 @@
  * take the GPU entropy decoder; progressive files, which it does not take, go
  * through the host Huffman decoder and a plan.
  *
- *   make -C examples && examples/jpeg2bmp out_dir a.jpg [b.jpg ...]
+ *   make -C examples && examples/jpeg2bmp [--scale N] out_dir a.jpg [b.jpg ...]
+ *
+ * --scale N (2, 4 or 8; 4:4:4, 4:2:0 and gray files): the scaled decode -- the
+ * BMP is ceil(W/N) x ceil(H/N) (hjd_scaled_size, hjd_gdec_set_scale,
+ * hjd_plan_create_scaled).
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -54,7 +58,7 @@ static uint8_t* read_file(const char* path, size_t* size)
 
 /* Host Huffman + the fused kernel through a one-frame plan. */
 static int decode_host_path(hjd_ctx* ctx, const uint8_t* data, size_t size, const hjd_jpeg_info* info,
-                            void* d_out, int32_t pitch)
+                            void* d_out, int32_t pitch, int scale)
 {
     int16_t* coefs = (int16_t*)malloc((size_t)info->nblocks * 64 * sizeof(int16_t));
     hjd_jpeg_info full;
@@ -73,7 +77,7 @@ static int decode_host_path(hjd_ctx* ctx, const uint8_t* data, size_t size, cons
     fr.qt_index[0] = 0;
     fr.qt_index[1] = 1;
     fr.qt_index[2] = 2;
-    CHECK(hjd_plan_create(ctx, &fr, 1, HJD_IN_Q16_ZIGZAG, &full.qt[0][0], 3, &plan));
+    CHECK(hjd_plan_create_scaled(ctx, &fr, 1, HJD_IN_Q16_ZIGZAG, &full.qt[0][0], 3, scale, &plan));
     CHECK(hjd_plan_launch(plan, d_coefs, d_out, NULL, 0));
     HIP_CHECK(hipDeviceSynchronize());
     CHECK(hjd_plan_destroy(plan));
@@ -84,8 +88,14 @@ static int decode_host_path(hjd_ctx* ctx, const uint8_t* data, size_t size, cons
 
 int main(int argc, char** argv)
 {
+    int scale = 1;
+    if (argc >= 3 && !strcmp(argv[1], "--scale")) {
+        scale = atoi(argv[2]);
+        argv += 2;
+        argc -= 2;
+    }
     if (argc < 3) {
-        fprintf(stderr, "usage: %s out_dir file.jpg...\n", argv[0]);
+        fprintf(stderr, "usage: %s [--scale 1|2|4|8] out_dir file.jpg...\n", argv[0]);
         return 2;
     }
     hjd_ctx* ctx = NULL;
@@ -99,13 +109,16 @@ int main(int argc, char** argv)
         }
         hjd_jpeg_info info;
         CHECK(hjd_jpeg_parse(data, size, &info));
-        const int32_t pitch = info.width * 4;
-        const size_t bytes = (size_t)pitch * (size_t)info.height;
+        int out_w = 0, out_h = 0;
+        CHECK(hjd_scaled_size(info.width, info.height, scale, &out_w, &out_h));
+        const int32_t pitch = out_w * 4;
+        const size_t bytes = (size_t)pitch * (size_t)out_h;
         void* d_out = NULL;
         HIP_CHECK(hipMalloc(&d_out, bytes));
         if (info.process != 2) {   /* sequential (one scan or several): GPU Huffman decode + fused kernel */
             hjd_gdec* gd = NULL;
             CHECK(hjd_gdec_create(ctx, 1, (int64_t)size, info.nblocks, 0, &gd));
+            CHECK(hjd_gdec_set_scale(gd, scale));
             const uint8_t* datas[1] = {data};
             const size_t sizes[1] = {size};
             void* outs[1] = {d_out};
@@ -114,13 +127,13 @@ int main(int argc, char** argv)
             CHECK(hjd_gdec_decode(gd, datas, sizes, 1, outs, pitches, NULL));
             CHECK(hjd_gdec_sync(gd, &status));
             CHECK(hjd_gdec_destroy(gd));
-        } else if (decode_host_path(ctx, data, size, &info, d_out, pitch)) {
+        } else if (decode_host_path(ctx, data, size, &info, d_out, pitch, scale)) {
             return 1;
         }
         uint8_t* px = (uint8_t*)malloc(bytes);
         HIP_CHECK(hipMemcpy(px, d_out, bytes, hipMemcpyDeviceToHost));
         uint8_t header[54];
-        CHECK(hjd_bmp_header(info.width, info.height, header));
+        CHECK(hjd_bmp_header(out_w, out_h, header));
         const char* base = strrchr(argv[a], '/');
         base = base ? base + 1 : argv[a];
         char path[4096];
@@ -134,6 +147,7 @@ int main(int argc, char** argv)
         printf("%s: %dx%d sampling %d process %d scans %s -> %s (%s Huffman)\n", argv[a], info.width, info.height,
                info.sampling, info.process, info.single_scan ? "1" : "several", path,
                info.process != 2 ? "GPU" : "host");
+        if (scale != 1) printf("  scale 1/%d: %dx%d\n", scale, out_w, out_h);
         free(px);
         HIP_CHECK(hipFree(d_out));
         free(data);

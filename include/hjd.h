@@ -132,6 +132,9 @@ int hjd_ctx_device(const hjd_ctx* ctx);
 
 /* ---- sizes ---- */
 int hjd_frame_blocks(int width, int height, int sampling, int64_t* nblocks);
+/* Output size of a width x height source decoded at `scale` (1, 2, 4 or 8):
+ * ceil(width/scale) x ceil(height/scale).  Host only: needs no device. */
+int hjd_scaled_size(int width, int height, int scale, int* out_w, int* out_h);
 
 /*
  * Plan: validates a batch of frames, computes the work decomposition and
@@ -142,6 +145,36 @@ int hjd_frame_blocks(int width, int height, int sampling, int64_t* nblocks);
  */
 int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                     const int32_t* qtables, int nq, hjd_plan** out);
+/*
+ * Scaled decode: the plan's frames come out at 1/scale of their size, scale =
+ * 1, 2, 4 or 8 (scale 1 is exactly hjd_plan_create).  Definition (exact,
+ * integer): every 8x8 block's IDCT samples -- the full 8-point IDCT, after its
+ * [-256,255] clamp -- are reduced to (8/scale)^2 box means,
+ *     m = (sum of the scale x scale box + scale*scale/2) >> (2 * log2 scale)
+ * (arithmetic shift: floor); boxes never cross a block.  The scaled blocks
+ * form the component planes in the same MCU order as the full-size ones,
+ * chroma is replicated nearest by the sampling's own factors on the scaled
+ * grids (4:2:0 at scale 8: an MCU is 2x2 luma samples over one chroma sample),
+ * and the colour conversion is the full-size one applied to the means.  This
+ * is a box filter of the bit-exact full-size samples, not a reduced-size IDCT.
+ *
+ * Frames carry the SOURCE width and height.  The output is
+ * ceil(width/scale) x ceil(height/scale) pixels (hjd_scaled_size), cropped as
+ * at full size: the boxes on the right and bottom edges include the encoder's
+ * padding samples past the visible edge, as libjpeg's scaled decode does.
+ * out_pitch, its minimum and alignment rules and the planar plane stride
+ * (out_pitch * scaled height) all refer to the scaled size.
+ *
+ * scale > 1 serves HJD_YUV444, HJD_YUV420 and HJD_GRAY with HJD_IN_Q16_ZIGZAG
+ * input, all four output formats, through the persistent kernel only (however
+ * few tasks the plan has): 4:2:2, 4:1:1, 4:4:0, HJD_IN_I32_NATURAL, a non-zero
+ * hjd_plan_set_variant, hjd_plan_set_kernel(HJD_KERNEL_LATENCY) and
+ * hjd_debug_plan_launch_stages return HJD_E_INVALID.  hjd_plan_set_chunk and
+ * hjd_plan_autotune (chunks only; the cache key includes the scale) work.
+ */
+int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
+                           const int32_t* qtables, int nq, int scale, hjd_plan** out);
+int hjd_plan_scale(const hjd_plan* plan);          /* 1, 2, 4 or 8 */
 int hjd_plan_destroy(hjd_plan* plan);
 /* Tuning hook: kernel variant bits (0 = default).  bit 0: plain instead of
  * non-temporal output stores; bit 1: workgroup-interleaved task order.
@@ -156,7 +189,7 @@ int hjd_plan_set_kernel(hjd_plan* plan, int mode);   /* hjd_kernel_mode */
  * enough for the latency kernel keeps it.  Identical pixels either way. */
 int hjd_plan_set_chunk(hjd_plan* plan, int tasks);
 int64_t hjd_plan_tasks(const hjd_plan* plan);      /* work items (strips) */
-int64_t hjd_plan_pixels(const hjd_plan* plan);     /* visible pixels */
+int64_t hjd_plan_pixels(const hjd_plan* plan);     /* visible output pixels (a scaled plan: of the scaled size) */
 int64_t hjd_plan_coef_bytes(const hjd_plan* plan); /* algorithmic input bytes */
 
 /*
@@ -187,7 +220,7 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
                       int32_t* tasks_per_wave, int32_t* variant);
 /* hjd_plan_autotune's choice is cached per process (device x sampling x
  * input format x output format x the other variant bits x frame count x
- * task count):
+ * task count x scale):
  * a later plan of the same key takes it with no launch (and d_out is then NOT
  * written).  HJD_AUTOTUNE_CACHE=0 disables the cache; this empties it. */
 int hjd_autotune_cache_clear(void);

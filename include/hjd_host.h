@@ -174,6 +174,13 @@ int hjd_gdec_sync(hjd_gdec* g, int32_t* status);
  * take vector stores where pointer and pitch are multiples of 4 and byte
  * stores otherwise (include/hjd.h). */
 int hjd_gdec_set_output_format(hjd_gdec* g, int out_format);
+/* Decode scale of the following hjd_gdec_decode calls: 1 (default), 2, 4 or 8
+ * (the scaled decode of include/hjd.h, hjd_plan_create_scaled).  Image i comes
+ * out ceil(width/scale) x ceil(height/scale); pitches[] and the planar plane
+ * stride refer to that size.  An issued call keeps its scale.  A scaled call
+ * holding a 4:2:2, 4:1:1 or 4:4:0 file fails (HJD_E_INVALID) before anything
+ * is enqueued.  hjd_gdec_decode_coefs is unaffected. */
+int hjd_gdec_set_scale(hjd_gdec* g, int scale);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

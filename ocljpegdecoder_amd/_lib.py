@@ -87,6 +87,11 @@ SIGNATURES = {
     "hjd_frame_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "hjd_plan_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdFrame), ctypes.c_int, ctypes.c_int,
                                        c_i32p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_scaled_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int)]),
+    "hjd_plan_create_scaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdFrame), ctypes.c_int, ctypes.c_int,
+                                              c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_plan_scale": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_plan_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_plan_set_variant": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "hjd_plan_set_kernel": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -185,6 +190,7 @@ def _bind_host(lib):
                                                  ctypes.c_int, vp, ctypes.POINTER(ctypes.c_int64), vp]),
         "hjd_gdec_sync": (ctypes.c_int, [vp, c_i32p]),
         "hjd_gdec_set_output_format": (ctypes.c_int, [vp, ctypes.c_int]),
+        "hjd_gdec_set_scale": (ctypes.c_int, [vp, ctypes.c_int]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -68,6 +68,15 @@ def block_components(sampling: int, nblocks: int) -> np.ndarray:
     return np.array(([0] * nluma + [1, 2][: bpm - nluma]) * (nblocks // bpm), dtype=np.int64)
 
 
+def scaled_size(width: int, height: int, scale: int):
+    """(W', H') = (ceil(width / scale), ceil(height / scale)) of a scaled
+    decode (hjd_scaled_size; scale 1, 2, 4 or 8).  Host only."""
+    w, h = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().hjd_scaled_size(int(width), int(height), int(scale), ctypes.byref(w), ctypes.byref(h)),
+          "hjd_scaled_size")
+    return w.value, h.value
+
+
 def frame_blocks(width: int, height: int, sampling: int) -> int:
     mw, mh, bpm, _ = mcu_geometry(width, height, sampling)
     return mw * mh * bpm
@@ -167,7 +176,7 @@ class FrameSpec:
     sampling: int
     coef_offset: int = 0          # in blocks
     out_offset: int = 0           # bytes
-    out_pitch: int = 0            # bytes (0 -> default_pitch(width, out_format))
+    out_pitch: int = 0            # bytes (0 -> default_pitch(width, out_format); of the scaled width in a scaled plan)
     qt_index: Sequence[int] = field(default_factory=lambda: (0, 1, 1))
     out_format: int = OUT_BGRX
 
@@ -175,13 +184,16 @@ class FrameSpec:
     def pitch(self) -> int:
         return self.out_pitch or default_pitch(self.width, self.out_format)
 
-    def to_c(self) -> HjdFrame:
+    def to_c(self, scale: int = 1) -> HjdFrame:
+        """The C record; width and height stay the source's, out_pitch = 0
+        resolves against the size scaled by `scale`."""
         f = HjdFrame()
         f.coef_offset = self.coef_offset
         f.out_offset = self.out_offset
         f.width = self.width
         f.height = self.height
-        f.out_pitch = self.pitch
+        f.out_pitch = self.pitch if scale == 1 else (
+            self.out_pitch or default_pitch(scaled_size(self.width, self.height, scale)[0], self.out_format))
         f.sampling = self.sampling
         for i in range(3):
             f.qt_index[i] = int(self.qt_index[i])
@@ -193,20 +205,30 @@ class Plan:
     """A validated batch of frames with its device-side frame table (hjd_plan)."""
 
     def __init__(self, ctx: Context, frames: Sequence[FrameSpec], input_format: int = IN_Q16_ZIGZAG,
-                 qtables: Optional[np.ndarray] = None):
+                 qtables: Optional[np.ndarray] = None, scale: int = 1):
+        """scale 2, 4 or 8: a scaled plan (hjd_plan_create_scaled).  Frames
+        carry the source size; every frame comes out scaled_size(W, H, scale)
+        and out_pitch (0: default_pitch of the scaled width) refers to that."""
         self.ctx = ctx
         self.lib = ctx.lib
         self.frames = list(frames)
-        arr = (HjdFrame * max(1, len(self.frames)))(*[f.to_c() for f in self.frames])
+        if scale != 1:
+            scaled_size(1, 1, scale)   # a bad scale raises here, before any frame is sized with it
+        arr = (HjdFrame * max(1, len(self.frames)))(*[f.to_c(scale) for f in self.frames])
         if qtables is not None:
             q = np.ascontiguousarray(qtables, dtype=np.int32).reshape(-1, 64)
             qp, nq = q.ctypes.data_as(_lib.c_i32p), q.shape[0]
         else:
             q, qp, nq = None, None, 0
         h = ctypes.c_void_p()
-        check(self.lib.hjd_plan_create(ctx.handle, arr, len(self.frames), input_format, qp, nq, ctypes.byref(h)),
-              "hjd_plan_create")
+        if scale == 1:
+            check(self.lib.hjd_plan_create(ctx.handle, arr, len(self.frames), input_format, qp, nq, ctypes.byref(h)),
+                  "hjd_plan_create")
+        else:
+            check(self.lib.hjd_plan_create_scaled(ctx.handle, arr, len(self.frames), input_format, qp, nq, int(scale),
+                                                  ctypes.byref(h)), "hjd_plan_create_scaled")
         self.handle = h
+        self.scale = self.lib.hjd_plan_scale(h)
         self.input_format = input_format
         self.tasks = self.lib.hjd_plan_tasks(h)
         self.pixels = self.lib.hjd_plan_pixels(h)
@@ -215,8 +237,11 @@ class Plan:
         self.coef_elem_bytes = 2 if input_format == IN_Q16_ZIGZAG else 4
         self.coef_elems_needed = max([64 * (f.coef_offset + frame_blocks(f.width, f.height, f.sampling))
                                       for f in self.frames] or [0])
-        self.out_bytes_needed = max([f.out_offset + (out_rows(f.height, f.out_format) - 1) * f.pitch +
-                                     _ROW_BYTES[f.out_format] * f.width for f in self.frames] or [0])
+        self.out_bytes_needed = 0
+        for f, c in zip(self.frames, arr):   # on the scaled size (scale 1: the frame's own)
+            sw, sh = (f.width, f.height) if scale == 1 else scaled_size(f.width, f.height, scale)
+            self.out_bytes_needed = max(self.out_bytes_needed, f.out_offset + (out_rows(sh, f.out_format) - 1) *
+                                        c.out_pitch + _ROW_BYTES[f.out_format] * sw)
 
     def _check_tensor(self, t, what, elem_bytes, nbytes_needed):
         if isinstance(t, int):
@@ -364,12 +389,15 @@ def debug_tuning(name: str, value):
 
 
 def decode_frame(ctx: Context, coefs, qt: np.ndarray, width: int, height: int, sampling: int,
-                 input_format: int = IN_Q16_ZIGZAG, stream=None):
+                 input_format: int = IN_Q16_ZIGZAG, stream=None, scale: int = 1):
     """Decode one frame already resident on the device; returns an int32 (H, W)
-    device tensor holding BGRX words (0x00RRGGBB)."""
+    device tensor holding BGRX words (0x00RRGGBB); scale 2, 4 or 8: (H', W') =
+    scaled_size(width, height, scale), reversed."""
     import torch
     plan = Plan(ctx, [FrameSpec(width, height, sampling, qt_index=(0, 1, 2))], input_format,
-                qtables=qt if input_format == IN_Q16_ZIGZAG else None)
+                qtables=qt if input_format == IN_Q16_ZIGZAG else None, scale=scale)
+    if scale != 1:
+        width, height = scaled_size(width, height, scale)
     out = torch.empty((height, width), dtype=torch.int32, device=coefs.device)
     plan.launch(coefs, out, stream)
     return out, plan

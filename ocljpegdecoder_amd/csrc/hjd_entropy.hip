@@ -2419,6 +2419,7 @@ struct hjd_gdec {
     int64_t tasks[kClasses] = {};
     uint8_t* out_base[kClasses] = {};
     int out_format = HJD_OUT_BGRX;      // pixel output format (hjd_gdec_set_output_format)
+    int scale = 1;                      // decode scale of hjd_gdec_decode: 1, 2, 4 or 8 (hjd_gdec_set_scale)
 };
 
 int hjd_gdec::wait_staging()
@@ -2656,11 +2657,13 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
         const int pmask = hjd_internal::out_format_any_alignment(out_format) ? 0 : 3;
         for (int i = 0; i < n; ++i) {
             const Prepared& p = frames[i];
-            if (!d_outs[i] || !pitches || pitches[i] < obytes * p.width || (pitches[i] & pmask) ||
+            if (!d_outs[i] || !pitches || pitches[i] < obytes * hjd_internal::scaled_dim(p.width, scale) ||
+                (pitches[i] & pmask) ||
                 (reinterpret_cast<uintptr_t>(d_outs[i]) & amask))
                 return set_error(HJD_E_INVALID,
                                  "frame %d: bad output buffer or pitch (BGRX: 16-byte aligned, >= 4*width; "
-                                 "BGR24: 4-byte aligned, >= 3*width; RGB24: >= 3*width; planar RGB: >= width)", i);
+                                 "BGR24: 4-byte aligned, >= 3*width; RGB24: >= 3*width; planar RGB: >= width; "
+                                 "width = the scaled width)", i);
             ++nrec[sampling_class(p.sampling)];
         }
         int r[kClasses];
@@ -2674,7 +2677,7 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
             const int64_t t = hjd_internal::make_frame_record(
                 p.width, p.height, p.sampling, static_cast<int64_t>(ef[i].coef_off),
                 static_cast<int64_t>(static_cast<uint8_t*>(d_outs[i]) - out_base[sidx]), pitches[i], qti, &rec,
-                out_format, reinterpret_cast<uintptr_t>(out_base[sidx]));
+                out_format, reinterpret_cast<uintptr_t>(out_base[sidx]), scale);
             if (t < 0) return static_cast<int>(t);
             rec.task_begin = tasks[sidx];
             tasks[sidx] += t;
@@ -3092,7 +3095,7 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
                 g->device, g->num_cu, hjd_gdec::kClassSampling[sidx], HJD_IN_Q16_ZIGZAG, 0, coefs,
                 reinterpret_cast<const int32_t*>(g->d_blob + g->H.qt),
                 reinterpret_cast<const FrameRecord*>(g->d_blob + g->H.recs) + r0, g->nrec[sidx], g->tasks[sidx],
-                g->out_base[sidx], s, 0, g->out_format);
+                g->out_base[sidx], s, 0, g->out_format, HJD_KERNEL_AUTO, g->scale);
             if (rc) return rc;
             r0 += g->nrec[sidx];
         }
@@ -3262,6 +3265,17 @@ int hjd_gdec_decode(hjd_gdec* g, const uint8_t* const* datas, const size_t* size
                     const int32_t* pitches, void* stream)
 {
     if (!d_outs) return set_error(HJD_E_INVALID, "d_outs is NULL");
+    if (g && g->scale != 1 && datas && sizes) {
+        // a scaled call refuses a file the scaled kernels do not serve before
+        // anything is staged or enqueued (a malformed file fails in staging)
+        hjd_internal::ScanHeader h;
+        for (int i = 0; i < n; ++i)
+            if (datas[i] && hjd_internal::parse_scan_header(datas[i], sizes[i], &h) == HJD_OK &&
+                !hjd_internal::scaled_sampling_ok(h.sampling))
+                return set_error(HJD_E_INVALID,
+                                 "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not sampling %d", i,
+                                 g->scale, h.sampling);
+    }
     return gdec_run(g, datas, sizes, n, d_outs, pitches, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -3286,6 +3300,14 @@ int hjd_gdec_set_output_format(hjd_gdec* g, int out_format)
     if (!g) return set_error(HJD_E_INVALID, "gdec is NULL");
     if (!hjd_internal::out_format_bytes(out_format)) return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
     g->out_format = out_format;   // applies to the next decode; an issued one keeps its format
+    return HJD_OK;
+}
+
+int hjd_gdec_set_scale(hjd_gdec* g, int scale)
+{
+    if (!g) return set_error(HJD_E_INVALID, "gdec is NULL");
+    if (hjd_internal::scale_log2(scale) < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    g->scale = scale;   // applies to the next decode; an issued one keeps its scale
     return HJD_OK;
 }
 

@@ -46,14 +46,24 @@ struct FrameRecord {
 // Fill a one-frame record (task_begin 0); returns the frame's task count, or
 // a negative status for an unsupported geometry.  out_format: HJD_OUT_*;
 // base_bits: low bits of the address out_base is relative to (out_vector_ok).
+// scale (1, 2, 4, 8): width and height are the source's; the record holds the
+// scaled size (scaled_dim) and `pitch` refers to it.
 int64_t make_frame_record(int width, int height, int sampling, int64_t coef_base, int64_t out_base, int pitch,
-                          const int qt_index[3], FrameRecord* rec, int out_format = 0, uintptr_t base_bits = 0);
+                          const int qt_index[3], FrameRecord* rec, int out_format = 0, uintptr_t base_bits = 0,
+                          int scale = 1);
+
+// Scaled decode (hjd_plan_create_scaled): log2 of a legal scale, or -1.
+inline int scale_log2(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }
+// Output size of a source dimension at a scale: ceil(d / scale).
+inline int scaled_dim(int d, int scale) { return (d + scale - 1) / scale; }
+// Samplings (enum hjd_sampling) the scaled kernels serve: 4:4:4, 4:2:0, gray.
+inline bool scaled_sampling_ok(int sampling) { return sampling == 0 || sampling == 1 || sampling == 4; }
 
 // Launch the fused kernel on device-resident frame records / natural-order
 // qtables (no host synchronisation, safe to call from any host thread).
 int launch_decode(int device, int num_cu, int sampling, int input_format, int variant, const void* d_coefs,
                   const int32_t* d_qt_nat, const FrameRecord* d_frames, int nframes, int64_t tasks, void* d_out,
-                  void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0);
+                  void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0, int scale = 1);
 
 // Bytes per output pixel of an HJD_OUT_* format overall (0 if unknown).
 inline int out_format_bytes(int out_format)

@@ -152,7 +152,9 @@ struct TaskGeom {
     int x_base;     // first pixel column
 };
 
-template <int kSampling>
+// kLog: log2 of the decode scale (scaled kernels): the strip's position on
+// the scaled output grid; the MCU and block arithmetic stays in source units.
+template <int kSampling, int kLog = 0>
 __device__ __forceinline__ TaskGeom task_geom(const FrameCursor& c, int64_t task)
 {
     using G = KGeom<kSampling>;
@@ -162,8 +164,8 @@ __device__ __forceinline__ TaskGeom task_geom(const FrameCursor& c, int64_t task
     TaskGeom g;
     g.nblk = min(G::kMcus, c.mcu_w - mx0) * G::kBpm;
     g.blk0 = c.coef_base + (static_cast<int64_t>(my) * c.mcu_w + mx0) * G::kBpm;
-    g.y_base = my * G::kMcuH;
-    g.x_base = mx0 * G::kMcuW;
+    g.y_base = (my * G::kMcuH) >> kLog;
+    g.x_base = (mx0 * G::kMcuW) >> kLog;
     return g;
 }
 
@@ -196,6 +198,12 @@ constexpr int kAblGatherBroadcast = 256;
 // (plane = pitch * height, wave-uniform, 64-bit).
 constexpr int kOutRgb24 = 512;
 constexpr int kOutPlanar = 1024;
+// Scaled decode: log2 of the scale (1, 2, 3 = 1/2, 1/4, 1/8) in bits 11-12
+// (decode_kernel; the latency kernel has no scaled form).
+constexpr int kScaleShift = 11;
+constexpr int kVarScale = 3 << kScaleShift;
+template <int kVariant>
+constexpr int kScaleLog = (kVariant & kVarScale) >> kScaleShift;
 // Bytes per pixel within one output row (planar: of one plane's row).
 template <int kVariant>
 constexpr int kOutBytes = (kVariant & kOutPlanar) != 0 ? 1 : (kVariant & (kOutBgr24 | kOutRgb24)) != 0 ? 3 : 4;
@@ -562,6 +570,140 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
     }
 }
 
+// ---- scaled decode (1/2, 1/4, 1/8: kLog = 1, 2, 3) ---------------------------
+// The IDCT leaves each block as n x n box means (n = 8 >> kLog) in the top-left
+// corner of its slot, rows still 16 bytes apart (idct_stage).  A scaled strip
+// is the full strip divided by the scale: 4:2:0 64x8 / 32x4 / 16x2 px, 4:4:4
+// 64x4 / 32x2 / 16x1, gray 192x4 / 96x2 / 48x1 -- always a multiple of 4 px
+// wide, so the colour units stay 4 px x 1 row and go through emit_row4 /
+// store4 unchanged.
+
+// Two horizontally adjacent scaled samples (x even; low half first) of row y
+// of component kComp's plane of the strip (the plane the MCUs' scaled blocks
+// of that component form; 4:2:0 luma: 2 x 2 blocks per MCU).
+template <int kSampling, int kLog, int kComp>
+__device__ __forceinline__ uint32_t scaled_pair(const char* __restrict__ slots, int x, int y)
+{
+    constexpr int kN = 3 - kLog;                                   // log2 samples per block side
+    constexpr int kBpm = KGeom<kSampling>::kBpm;
+    constexpr int kHb = kSampling == 1 && kComp == 0 ? 1 : 0;      // log2 blocks per MCU side
+    constexpr int kFirst = kComp == 0 ? 0 : kBpm - 3 + kComp;      // the component's first block of an MCU
+    auto offset = [&](int xs) {
+        const int m = xs >> (kN + kHb), xm = xs & ((1 << (kN + kHb)) - 1);
+        const int blk = m * kBpm + kFirst + ((y >> kN) << kHb) + (xm >> kN);
+        return blk * kSlotBytes + (y & ((1 << kN) - 1)) * 16 + (xm & ((1 << kN) - 1)) * 2;
+    };
+    if constexpr (kN > 0) {
+        return *reinterpret_cast<const uint32_t*>(slots + offset(x));   // both in one block row
+    } else {   // one sample per block: the pair comes from two blocks
+        const uint32_t a = *reinterpret_cast<const unsigned short*>(slots + offset(x));
+        const uint32_t b = *reinterpret_cast<const unsigned short*>(slots + offset(x + 1));
+        return a | (b << 16);
+    }
+}
+
+// Colour stage of a scaled strip: units of 4 px x 1 row, kUnits per strip,
+// unit u = 64 * it + lane (lanes past the last unit idle).  Chroma is
+// replicated nearest on the scaled grids, by the sampling's own factors.
+template <int kSampling, int kLog, bool kFull, int kVariant>
+__device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slots, int lane,
+                                                    uint8_t* __restrict__ out, int pitch, int width, int height,
+                                                    int y_base, int x_base)
+{
+    static_assert(kSampling == 0 || kSampling == 1 || kSampling == 3, "scaled decode: 4:4:4, 4:2:0 and gray");
+    using G = KGeom<kSampling>;
+    constexpr int kUW = (G::kStripW >> kLog) / 4;        // units per strip row
+    constexpr int kUnits = kUW * (G::kMcuH >> kLog);
+    constexpr int kPx = kOutBytes<kVariant>;
+    uint8_t* const strip = out + static_cast<int64_t>(y_base) * pitch + static_cast<int64_t>(x_base) * kPx;
+    const int64_t plane = (kVariant & kOutPlanar) != 0 ? static_cast<int64_t>(pitch) * height : 0;
+#pragma unroll
+    for (int it = 0; it < (kUnits + 63) / 64; ++it) {
+        const int u = it * 64 + lane;
+        const bool valid = kUnits % 64 == 0 || u < kUnits;
+        const int uc = valid ? u : 0;                    // idle lanes read unit 0's samples
+        const int y = uc / kUW;
+        const int cu4 = uc - y * kUW;
+        const int x = cu4 * 4;                           // within the scaled strip
+        const uint32_t lo = static_cast<uint32_t>(y) * static_cast<uint32_t>(pitch) + static_cast<uint32_t>(x * kPx);
+        const int xu = x_base + x;
+        const bool live = valid && (kFull || y_base + y < height);
+        const uint32_t y01 = scaled_pair<kSampling, kLog, 0>(slots, x, y);
+        const uint32_t y23 = scaled_pair<kSampling, kLog, 0>(slots, x + 2, y);
+        if constexpr (kSampling == 3) {
+            const uint32_t g01 = sat_pk_u8(y01), g23 = sat_pk_u8(y23);
+            if (live)
+                store4<kFull, kVariant>(strip, lo, xu, width, perm(g01, g01, 0x0c000000u), perm(g01, g01, 0x0c010101u),
+                                        perm(g23, g23, 0x0c000000u), perm(g23, g23, 0x0c010101u), plane);
+        } else if constexpr (kSampling == 0) {
+            const uint32_t u01 = scaled_pair<0, kLog, 1>(slots, x, y), u23 = scaled_pair<0, kLog, 1>(slots, x + 2, y);
+            const uint32_t v01 = scaled_pair<0, kLog, 2>(slots, x, y), v23 = scaled_pair<0, kLog, 2>(slots, x + 2, y);
+            const ChromaTerms c0 = chroma_terms<0>(u01, v01);
+            const ChromaTerms c1 = chroma_terms<1>(u01, v01);
+            const ChromaTerms c2 = chroma_terms<0>(u23, v23);
+            const ChromaTerms c3 = chroma_terms<1>(u23, v23);
+            const ChromaPair p01 = pair_of(c0, c1), p23 = pair_of(c2, c3);
+            const bool flagged = __builtin_amdgcn_ballot_w64(live && (p01.flagged | p23.flagged) != 0) != 0;
+            if (live) {
+                if (flagged)   // wave-uniform, rare
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane);
+                else
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane);
+            }
+        } else {
+            // 4:2:0: chroma samples x/2 and x/2 + 1 of chroma row y/2 serve 2 px each
+            const uint32_t cu = scaled_pair<1, kLog, 1>(slots, x >> 1, y >> 1);
+            const uint32_t cv = scaled_pair<1, kLog, 2>(slots, x >> 1, y >> 1);
+            const ChromaTerms c0 = chroma_terms<0>(cu, cv);
+            const ChromaTerms c1 = chroma_terms<1>(cu, cv);
+            const ChromaPair p0 = pair_of(c0, c0), p1 = pair_of(c1, c1);
+            const bool flagged = __builtin_amdgcn_ballot_w64(live && (p0.flagged | p1.flagged) != 0) != 0;
+            if (live) {
+                if (flagged)   // wave-uniform, rare
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane);
+                else
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane);
+            }
+        }
+    }
+}
+
+// x + the same value of another lane of the 8-lane group (DPP): quad_perm
+// [1,0,3,2] = lane ^ 1, quad_perm [2,3,0,1] = lane ^ 2, row_half_mirror =
+// lane 7 - i (the other quad of the group).  Every lane of the wave is active
+// in the IDCT rounds, so every source lane is valid.
+constexpr int kDppXor1 = 0xb1, kDppXor2 = 0x4e, kDppHalfMirror = 0x141;
+template <int kCtrl>
+__device__ __forceinline__ int dpp_add(int x)
+{
+    return x + __builtin_amdgcn_update_dpp(0, x, kCtrl, 0xf, 0xf, true);
+}
+
+// Box means of one block's column-pass output (scaled decode): this lane holds
+// column r's eight clamped samples in the words' high halves.  m = (sum of
+// the s x s box + s*s/2) >> 2 log2 s, floor: the vertical sums are in-lane
+// adds, the horizontal ones DPP adds over lanes r^1, r^2, r^4; afterwards
+// every lane of a box column holds the box's mean, and the lane with
+// r % s == 0 writes the 8/s means of box column r / s into the block's slot
+// (rows 16 bytes apart, as the full-size samples).  The luma level shift
+// commutes with the mean ((S + 128 s^2 + s^2/2) >> 2k = ((S + s^2/2) >> 2k) + 128).
+template <int kLog>
+__device__ __forceinline__ void store_box_means(char* __restrict__ blk, int r, const int (&c8)[8])
+{
+    constexpr int kS = 1 << kLog, kN = 8 >> kLog;
+#pragma unroll
+    for (int j = 0; j < kN; ++j) {
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < kS; ++k) acc += c8[j * kS + k] >> 16;
+        acc = dpp_add<kDppXor1>(acc);
+        if constexpr (kLog >= 2) acc = dpp_add<kDppXor2>(acc);
+        if constexpr (kLog >= 3) acc = dpp_add<kDppHalfMirror>(acc);
+        const int m = (acc + kS * kS / 2) >> (2 * kLog);
+        if ((r & (kS - 1)) == 0) *reinterpret_cast<short*>(blk + j * 16 + (r >> kLog) * 2) = static_cast<short>(m);
+    }
+}
+
 // Task-local block (= LDS slot) transformed by lane group g in round i.  The
 // mapping keeps each round's component uniform across the wave (dequant table
 // and luma level shift): 4:4:4 / 4:2:0 / gray blocks are MCU-interleaved with
@@ -741,7 +883,9 @@ __device__ __forceinline__ void load_qrow_pk(const int* __restrict__ qt_pool, in
 // Samples end up as int16 row-major in the block slots (luma as Y + 128).  The next round's
 // coefficient gathers are issued before this round's column math, so their
 // LDS latency overlaps it.
-template <int kSampling, int kFmt, int kVariant = 0>
+// kLog > 0 (scaled decode): the slots receive each block's box means instead
+// (store_box_means).
+template <int kSampling, int kFmt, int kVariant = 0, int kLog = 0>
 __device__ __forceinline__ void idct_stage(char* __restrict__ slots, char* __restrict__ rowbuf, int lane,
                                            const int (&zoff)[8], const uint32_t (&q)[3][4],
                                            const int* __restrict__ src32, int nblk,
@@ -785,7 +929,9 @@ __device__ __forceinline__ void idct_stage(char* __restrict__ slots, char* __res
             idct8_col_hi<kLumaLevel>(c8);   // luma leaves the IDCT level-shifted (Ys = Y + 128)
         else
             idct8_col_hi(c8);
-        {
+        if constexpr (kLog > 0) {
+            store_box_means<kLog>(slots + b * kSlotBytes, r, c8);
+        } else {
             char* blk = slots + b * kSlotBytes + r * 2;   // column r; the samples are the words' high halves
 #pragma unroll
             for (int k = 0; k < 8; ++k)
@@ -812,6 +958,14 @@ __device__ __forceinline__ uint32_t group_order(uint32_t bid, uint32_t ngroups)
 // [w*T/W, (w+1)*T/W) so its frame changes rarely and the frame record stays in
 // SGPRs; the next task's coefficients are prefetched into VGPRs while the
 // current one is transformed.
+//
+// Scaled decode (hjd_plan_create_scaled): kVariant's kVarScale bits hold log2
+// of the scale (1, 2, 3), so the scaled kernels are further instantiations of
+// this one and the full-size ones keep their names and code.  They take int16
+// zigzag input, 4:4:4 / 4:2:0 / gray, and the output format bits only.  The
+// frame records hold the scaled width, height and pitch; mcu_w and strips
+// stay in source MCUs.  Edge boxes include the encoder's padding samples past
+// the visible edge (output ceil(W / s) x ceil(H / s)).
 template <int kSampling, int kFmt, int kVariant>
 __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kernel(const void* __restrict__ coefs,
                                                               const int* __restrict__ qt_pool,
@@ -820,6 +974,9 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
                                                               int64_t chunk, int64_t rem)
 {
     using L = KLayout;
+    constexpr int kLog = kScaleLog<kVariant>;
+    static_assert(kLog == 0 || (kFmt == 0 && (kVariant & ~(kVarScale | kOutBgr24 | kOutRgb24 | kOutPlanar)) == 0),
+                  "scaled kernels: int16 zigzag input, output format bits only");
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerGroup * L::wave_lds];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -884,7 +1041,7 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
         }
     };
     if constexpr (kFmt == 0) {
-        prefetch(task_geom<kSampling>(pc, t_begin));
+        prefetch(task_geom<kSampling, kLog>(pc, t_begin));
         // the first task's table rows load beside its coefficients, so a wave
         // start waits for one memory round trip, not two
         q_tables[0] = pc.qt0; q_tables[1] = pc.qt1; q_tables[2] = pc.qt2;
@@ -896,7 +1053,7 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
     for (int64_t task = t_begin, next_task; task >= 0; task = next_task) {
         next_task = task + t_step < t_end ? task + t_step : -1;   // -1: this is the wave's last task
         const FrameCursor cc = pc;
-        const TaskGeom tg = task_geom<kSampling>(cc, task);
+        const TaskGeom tg = task_geom<kSampling, kLog>(cc, task);
         if constexpr (kFmt == 0) {
             if (cc.qt0 != q_tables[0] || cc.qt1 != q_tables[1] || cc.qt2 != q_tables[2]) {
                 q_tables[0] = cc.qt0; q_tables[1] = cc.qt1; q_tables[2] = cc.qt2;
@@ -911,23 +1068,33 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
             wave_lds_sync();
             if (next_task >= 0) {   // the next task's loads fly during this task
                 while (next_task >= pc.end) cursor_load(pc, frames, nframes, total_tasks, pc.idx + 1);
-                prefetch(task_geom<kSampling>(pc, next_task));
+                prefetch(task_geom<kSampling, kLog>(pc, next_task));
             }
         } else {
             if (next_task >= 0)
                 while (next_task >= pc.end) cursor_load(pc, frames, nframes, total_tasks, pc.idx + 1);
         }
 
-        constexpr int kRows = KGeom<kSampling>::kMcuH;
-        constexpr int kStripW = KGeom<kSampling>::kStripW;
+        constexpr int kRows = KGeom<kSampling>::kMcuH >> kLog;
+        constexpr int kStripW = KGeom<kSampling>::kStripW >> kLog;
         uint8_t* fout = out + cc.out_base;
         const bool full = cc.vec_ok && tg.x_base + kStripW <= cc.width && tg.y_base + kRows <= cc.height;
         if constexpr ((kVariant & kAblNoIdct) == 0)
-            idct_stage<kSampling, kFmt, kVariant>(slots, rowbuf, lane, zoff, q,
-                                                  static_cast<const int*>(coefs) + tg.blk0 * 64, tg.nblk, slots_lds);
+            idct_stage<kSampling, kFmt, kVariant, kLog>(slots, rowbuf, lane, zoff, q,
+                                                        static_cast<const int*>(coefs) + tg.blk0 * 64, tg.nblk,
+                                                        slots_lds);
 
         if constexpr ((kVariant & kAblNoColour) != 0) {
             (void)fout;
+        } else if constexpr (kLog > 0) {
+            if (full)
+                colour_stage_scaled<kSampling, kLog, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height,
+                                                                     tg.y_base, tg.x_base);
+            else {
+                colour_stage_scaled<kSampling, kLog, false, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height,
+                                                                      tg.y_base, tg.x_base);
+                __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): edge strips drain their stores, as below
+            }
         } else if (full)
             colour_stage<kSampling, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base);
         else {

@@ -91,6 +91,7 @@ struct hjd_plan {
     int tuned_per_wave = 0;     // its tasks per wave
     int autotune_launches = 0;  // kernel launches of the last hjd_plan_autotune
     int autotune_cached = 0;    // 1: that call reused a cached choice
+    int scale = 1;              // hjd_plan_create_scaled: 1, 2, 4 or 8
 };
 
 constexpr int64_t kDefaultLatencyMaxTasks = 1024;   // measured: profiles/r01_latency_kernel.json
@@ -240,19 +241,23 @@ int hjd_internal::ctx_num_cu(const hjd_ctx* ctx) { return ctx->num_cu; }
 
 int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int64_t coef_base, int64_t out_base,
                                         int pitch, const int qt_index[3], FrameRecord* rec, int out_format,
-                                        uintptr_t base_bits)
+                                        uintptr_t base_bits, int scale)
 {
     int mw, mh, bpm, tasks_mcus;
     int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
     if (rc) return rc;
+    if (scale_log2(scale) < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    if (scale > 1 && !scaled_sampling_ok(sampling))
+        return set_error(HJD_E_INVALID, "scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not sampling %d", scale,
+                         sampling);
     static_assert(sizeof(FrameRecord) == sizeof(FrameDev), "record layout");
     FrameDev d;
     memset(&d, 0, sizeof(d));
     d.coef_base = coef_base;
     d.out_base = out_base;
     d.task_begin = 0;
-    d.width = width;
-    d.height = height;
+    d.width = scaled_dim(width, scale);
+    d.height = scaled_dim(height, scale);
     d.pitch = pitch;
     d.sampling = sampling;
     d.mcu_w = mw;
@@ -266,7 +271,7 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
 int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_format, int variant,
                                 const void* d_coefs, const int32_t* d_qt_nat, const FrameRecord* d_frames,
                                 int nframes, int64_t tasks, void* d_out, void* stream, int grid_blocks, int out_format,
-                                int kernel_mode)
+                                int kernel_mode, int scale)
 {
     HJD_HIP(hipSetDevice(device));
     const int fmt = input_format == HJD_IN_Q16_ZIGZAG ? 0 : 1;
@@ -285,6 +290,31 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
     const int64_t split_n = (variant & 2) ? static_cast<int64_t>(grid) : static_cast<int64_t>(grid) * hjd::kWavesPerGroup;
     const int64_t split_t = (variant & 2) ? (tasks + hjd::kWavesPerGroup - 1) / hjd::kWavesPerGroup : tasks;
     const int64_t chunk = split_t / split_n, rem = split_t % split_n;
+    if (scale != 1) {   // scaled decode: the persistent kernel only, [log2 scale - 1][sampling][output format]
+        const int lg = scale_log2(scale);
+        if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+        if (!scaled_sampling_ok(sampling))
+            return set_error(HJD_E_INVALID, "scaled decode serves 4:4:4, 4:2:0 and gray, not sampling %d", sampling);
+        if (fmt != 0) return set_error(HJD_E_INVALID, "scaled decode takes HJD_IN_Q16_ZIGZAG input only");
+        if (variant != 0) return set_error(HJD_E_INVALID, "scaled decode has no kernel variants");
+        if (kernel_mode == HJD_KERNEL_LATENCY)
+            return set_error(HJD_E_INVALID, "scaled decode has no latency kernel");
+#define HJD_KS1(S, V, L) hjd::decode_kernel<S, 0, (V) | ((L) << hjd::kScaleShift)>
+#define HJD_KS4(S, L) HJD_KS1(S, 0, L), HJD_KS1(S, hjd::kOutBgr24, L), HJD_KS1(S, hjd::kOutRgb24, L), \
+                      HJD_KS1(S, hjd::kOutPlanar, L)
+#define HJD_KS(L) HJD_KS4(0, L), HJD_KS4(1, L), HJD_KS4(3, L)
+        static const KP kScaled[36] = {HJD_KS(1), HJD_KS(2), HJD_KS(3)};
+#undef HJD_KS
+#undef HJD_KS4
+#undef HJD_KS1
+        const int srow = sampling == HJD_YUV444 ? 0 : sampling == HJD_YUV420 ? 1 : 2;
+        hipLaunchKernelGGL(kScaled[12 * (lg - 1) + 4 * srow + out_format], dim3(grid), dim3(hjd::kGroupThreads), 0,
+                           static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
+                           reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out),
+                           chunk, rem);
+        HJD_HIP(hipGetLastError());
+        return HJD_OK;
+    }
     if (latency && (variant >> kStageShift) == 0) {   // [output format][sampling index][input format]
 #define HJD_KL(V) hjd::decode_kernel_lat<0, 0, V>, hjd::decode_kernel_lat<0, 1, V>, \
                   hjd::decode_kernel_lat<1, 0, V>, hjd::decode_kernel_lat<1, 1, V>, \
@@ -441,12 +471,32 @@ int hjd_frame_blocks(int width, int height, int sampling, int64_t* nblocks)
     return HJD_OK;
 }
 
+int hjd_scaled_size(int width, int height, int scale, int* out_w, int* out_h)
+{
+    if (hjd_internal::scale_log2(scale) < 0) return fail(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
+        return fail(HJD_E_INVALID, "invalid dimensions %dx%d", width, height);
+    if (!out_w || !out_h) return fail(HJD_E_INVALID, "out_w or out_h is NULL");
+    *out_w = hjd_internal::scaled_dim(width, scale);
+    *out_h = hjd_internal::scaled_dim(height, scale);
+    return HJD_OK;
+}
+
 int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                     const int32_t* qtables, int nq, hjd_plan** out)
+{
+    return hjd_plan_create_scaled(ctx, frames, nframes, input_format, qtables, nq, 1, out);
+}
+
+int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
+                           const int32_t* qtables, int nq, int scale, hjd_plan** out)
 {
     if (!ctx || !out || (!frames && nframes > 0) || nframes < 0)
         return fail(HJD_E_INVALID, "invalid plan arguments");
     *out = nullptr;
+    if (hjd_internal::scale_log2(scale) < 0) return fail(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    if (scale > 1 && input_format == HJD_IN_I32_NATURAL)
+        return fail(HJD_E_INVALID, "scaled decode (scale %d) takes HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL", scale);
     if (input_format != HJD_IN_Q16_ZIGZAG && input_format != HJD_IN_I32_NATURAL)
         return fail(HJD_E_INVALID, "unknown input format %d", input_format);
     if (input_format == HJD_IN_Q16_ZIGZAG && (!qtables || nq <= 0))
@@ -470,7 +520,12 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
             return fail(HJD_E_INVALID, "frame %d: mixed sampling in one plan (use one plan per sampling)", i);
         if (f.out_format != out_format)
             return fail(HJD_E_INVALID, "frame %d: mixed output formats in one plan (use one plan per format)", i);
-        if (f.out_pitch < static_cast<int64_t>(rbytes) * f.width || (f.out_pitch & amask) || (f.out_offset & amask))
+        if (scale > 1 && !hjd_internal::scaled_sampling_ok(f.sampling))
+            return fail(HJD_E_INVALID,
+                        "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not 4:2:2, 4:1:1 or 4:4:0 "
+                        "(sampling %d)", i, scale, f.sampling);
+        const int sw = hjd_internal::scaled_dim(f.width, scale), sh = hjd_internal::scaled_dim(f.height, scale);
+        if (f.out_pitch < static_cast<int64_t>(rbytes) * sw || (f.out_pitch & amask) || (f.out_offset & amask))
             return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
         FrameDev& d = fd[i];
         if (input_format == HJD_IN_Q16_ZIGZAG) {
@@ -481,8 +536,8 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
         d.coef_base = static_cast<int64_t>(f.coef_offset);
         d.out_base = static_cast<int64_t>(f.out_offset);
         d.task_begin = tasks;
-        d.width = f.width;
-        d.height = f.height;
+        d.width = sw;
+        d.height = sh;
         d.pitch = f.out_pitch;
         d.sampling = f.sampling;
         d.mcu_w = mw;
@@ -490,7 +545,7 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
         for (int c = 0; c < 3; ++c) d.qt[c] = input_format == HJD_IN_Q16_ZIGZAG ? f.qt_index[c] : 0;
         d.vec_ok = hjd_internal::out_vector_ok(out_format, f.out_pitch, static_cast<int64_t>(f.out_offset)) ? 1 : 0;
         tasks += static_cast<int64_t>(d.strips) * mh;
-        pixels += static_cast<int64_t>(f.width) * f.height;
+        pixels += static_cast<int64_t>(sw) * sh;
         blocks += static_cast<int64_t>(mw) * mh * bpm;
     }
 
@@ -501,6 +556,7 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
     p->input_format = input_format;
     p->sampling = sampling;
     p->out_format = out_format;
+    p->scale = scale;
     p->nframes = nframes;
     p->tasks = tasks;
     p->pixels = pixels;
@@ -544,6 +600,8 @@ int hjd_plan_set_variant(hjd_plan* plan, int variant)
     if (variant < 0 || variant > 3) return fail(HJD_E_INVALID, "unknown kernel variant %d", variant);
     if (variant != 0 && hjd_internal::out_format_any_alignment(plan->out_format))
         return fail(HJD_E_INVALID, "kernel variants are BGRX-only");
+    if (variant != 0 && plan->scale != 1)
+        return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no kernel variants", plan->scale);
     plan->variant = variant;
     return HJD_OK;
 }
@@ -562,12 +620,15 @@ int hjd_plan_set_kernel(hjd_plan* plan, int mode)
     if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
     if (mode != HJD_KERNEL_AUTO && mode != HJD_KERNEL_PERSISTENT && mode != HJD_KERNEL_LATENCY)
         return fail(HJD_E_INVALID, "unknown kernel mode %d", mode);
+    if (mode == HJD_KERNEL_LATENCY && plan->scale != 1)
+        return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no latency kernel", plan->scale);
     plan->kernel_mode = mode;
     return HJD_OK;
 }
 
 int64_t hjd_plan_tasks(const hjd_plan* plan) { return plan ? plan->tasks : -1; }
 int64_t hjd_plan_pixels(const hjd_plan* plan) { return plan ? plan->pixels : -1; }
+int hjd_plan_scale(const hjd_plan* plan) { return plan ? plan->scale : -1; }
 int64_t hjd_plan_coef_bytes(const hjd_plan* plan) { return plan ? plan->coef_bytes : -1; }
 
 // Grid of the fused kernel: short contiguous task chunks per wave and many
@@ -614,7 +675,7 @@ static int grid_for_chunk(int64_t tasks, int64_t per_wave, bool occupancy_floor)
 // A default launch of this plan takes the persistent kernel (not the latency one).
 static bool plan_is_persistent(const hjd_plan* p)
 {
-    return p->kernel_mode == HJD_KERNEL_PERSISTENT ||
+    return p->kernel_mode == HJD_KERNEL_PERSISTENT || p->scale != 1 ||   // a scaled plan has no latency kernel
            (p->kernel_mode == HJD_KERNEL_AUTO && p->tasks > latency_max_tasks());
 }
 
@@ -640,7 +701,7 @@ int hjd_plan_launch(hjd_plan* plan, const void* d_coefs, void* d_out, void* stre
                                        plan->variant, d_coefs, plan->d_qt,
                                        reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
                                        plan->nframes, plan->tasks, d_out, stream, grid_blocks, plan->out_format,
-                                       plan->kernel_mode);
+                                       plan->scale != 1 ? HJD_KERNEL_PERSISTENT : plan->kernel_mode, plan->scale);
 }
 
 // The fused kernel's launch adapted to the device it runs on (VERDICT r3:
@@ -665,10 +726,11 @@ namespace {
 struct TuneKey {
     int device, sampling, input_format, out_format, keep_variant, nframes;
     int64_t tasks;
+    int scale;
     bool operator<(const TuneKey& o) const
     {
-        return std::tie(device, sampling, input_format, out_format, keep_variant, nframes, tasks) <
-               std::tie(o.device, o.sampling, o.input_format, o.out_format, o.keep_variant, o.nframes, o.tasks);
+        return std::tie(device, sampling, input_format, out_format, keep_variant, nframes, tasks, scale) <
+               std::tie(o.device, o.sampling, o.input_format, o.out_format, o.keep_variant, o.nframes, o.tasks, o.scale);
     }
 };
 std::mutex g_tune_mu;
@@ -701,7 +763,7 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
     if (plan->tasks == 0 || !plan_is_persistent(plan)) return report();
     const int keep = plan->variant & ~1;
     const TuneKey key{plan->ctx->device, plan->sampling, plan->input_format, plan->out_format, keep, plan->nframes,
-                      plan->tasks};
+                      plan->tasks, plan->scale};
     if (tune_cache_enabled()) {
         std::lock_guard<std::mutex> lock(g_tune_mu);
         auto it = g_tune.find(key);
@@ -725,7 +787,9 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
         bool dup = false;
         for (const Cand& c : cands) dup |= c.grid == g;
         if (dup) continue;
-        for (int st = 0; st < (plan->out_format == HJD_OUT_BGRX ? 2 : 1); ++st) cands.push_back({pw, st, g, 1e30f});
+        // the store policy is a BGRX variant bit; scaled plans have no variants (chunks only)
+        for (int st = 0; st < (plan->out_format == HJD_OUT_BGRX && plan->scale == 1 ? 2 : 1); ++st)
+            cands.push_back({pw, st, g, 1e30f});
     }
     HJD_HIP(hipSetDevice(plan->ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -745,7 +809,7 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
                                                    plan->input_format, v, d_coefs, plan->d_qt,
                                                    reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
                                                    plan->nframes, plan->tasks, d_out, s, c.grid, plan->out_format,
-                                                   HJD_KERNEL_PERSISTENT);
+                                                   HJD_KERNEL_PERSISTENT, plan->scale);
             };
             float ms = 0;
             if ((rc = go()) || (rc = hipEventRecord(e0, s) == hipSuccess ? HJD_OK : HJD_E_HIP) || (rc = go()) ||
@@ -813,6 +877,8 @@ int hjd_debug_plan_launch_stages(hjd_plan* plan, int stages, const void* d_coefs
     if (stages != 4 && stages != 16 && stages != 20 && stages != 64 && stages != 80 && stages != 8 && stages != 24 &&
         stages != 256)
         return fail(HJD_E_INVALID, "unknown stage variant %d", stages);
+    if (plan->scale != 1)
+        return fail(HJD_E_INVALID, "stage variants are not built for scaled plans (scale %d)", plan->scale);
     if (plan->input_format != HJD_IN_Q16_ZIGZAG || plan->out_format != HJD_OUT_BGRX ||
         (plan->sampling != HJD_YUV420 && plan->sampling != HJD_YUV444))
         return fail(HJD_E_INVALID, "stage variants: 4:2:0 / 4:4:4, int16 zigzag in, BGRX out");

@@ -288,12 +288,20 @@ class GpuDecoder:
         self.handle = h
         self._n = 0
         self.out_format = 0
+        self.scale = 1
 
     def set_output_format(self, out_format: int):
         """OUT_BGRX (default), OUT_BGR24, OUT_RGB24 or OUT_RGB_PLANAR for the
         following decode() calls."""
         check(self.lib.hjd_gdec_set_output_format(self.handle, int(out_format)), "hjd_gdec_set_output_format")
         self.out_format = int(out_format)
+
+    def set_scale(self, scale: int):
+        """Decode scale of the following decode() calls: 1 (default), 2, 4 or 8
+        (hjd_gdec_set_scale): image i comes out scaled_size(W, H, scale), and
+        the outputs are sized for that.  4:4:4, 4:2:0 and gray files only."""
+        check(self.lib.hjd_gdec_set_scale(self.handle, int(scale)), "hjd_gdec_set_scale")
+        self.scale = int(scale)
 
     def decode(self, datas: Sequence[bytes], outs, stream=None):
         """outs: contiguous device tensors, one row per image row: (H, W) int32
@@ -312,9 +320,11 @@ class GpuDecoder:
               "hjd_gdec_decode")
         self._n = n
 
-    def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None):
+    def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1):
         """Decode to uint8 RGB tensors: layout "chw" gives (3, H, W) per image
-        (OUT_RGB_PLANAR), "hwc" gives (H, W, 3) (OUT_RGB24).  Without `out`,
+        (OUT_RGB_PLANAR), "hwc" gives (H, W, 3) (OUT_RGB24).  scale 2, 4 or 8
+        decodes at 1/scale (H and W below are then scaled_size's; the
+        decoder's own scale is restored afterwards).  Without `out`,
         one new device tensor per image is returned as a list.  With `out`, a
         contiguous uint8 device tensor (N, 3, H, W) ("chw") or (N, H, W, 3)
         ("hwc"), image i is decoded into out[i] and `out` is returned;
@@ -322,7 +332,7 @@ class GpuDecoder:
         decode(): call sync() before reading.  The decoder's output format is
         restored afterwards."""
         import torch
-        from .backend import OUT_RGB24, OUT_RGB_PLANAR
+        from .backend import OUT_RGB24, OUT_RGB_PLANAR, scaled_size
         if layout not in ("chw", "hwc"):
             raise ValueError('layout must be "chw" or "hwc"')
         chw = layout == "chw"
@@ -332,10 +342,10 @@ class GpuDecoder:
             c = HjdJpegInfo()
             check(self.lib.hjd_jpeg_parse(ctypes.cast(addr, _u8p), size, ctypes.byref(c)), "hjd_jpeg_parse")
             infos.append(JpegInfo.from_c(c))
+        sizes = [scaled_size(i.width, i.height, scale) for i in infos]   # (W', H')
         if out is None:
             dev = torch.device("cuda", self.ctx.device)
-            outs = [torch.empty((3, i.height, i.width) if chw else (i.height, i.width, 3), dtype=torch.uint8,
-                                device=dev) for i in infos]
+            outs = [torch.empty((3, h, w) if chw else (h, w, 3), dtype=torch.uint8, device=dev) for w, h in sizes]
         else:
             if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.ndim == 4
                     and out.shape[1 if chw else 3] == 3):
@@ -343,16 +353,19 @@ class GpuDecoder:
             if out.shape[0] != len(infos):
                 raise ValueError(f"out holds {out.shape[0]} images, {len(infos)} JPEGs given")
             oh, ow = (out.shape[2], out.shape[3]) if chw else (out.shape[1], out.shape[2])
-            for k, i in enumerate(infos):
-                if (i.height, i.width) != (oh, ow):
-                    raise ValueError(f"image {k} is {i.width}x{i.height}, out is {ow}x{oh}")
+            for k, (w, h) in enumerate(sizes):
+                if (h, w) != (oh, ow):
+                    raise ValueError(f"image {k} is {w}x{h}" + (f" at scale {scale}" if scale != 1 else "") +
+                                     f", out is {ow}x{oh}")
             outs = [out[k] for k in range(len(infos))]
-        prev = self.out_format
+        prev, prev_scale = self.out_format, self.scale
+        self.set_scale(scale)
         self.set_output_format(OUT_RGB_PLANAR if chw else OUT_RGB24)
         try:
             self.decode(datas, outs, stream)
         finally:
             self.set_output_format(prev)
+            self.set_scale(prev_scale)
         return outs if out is None else out
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
