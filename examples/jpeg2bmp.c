@@ -7,11 +7,14 @@
  * take the GPU entropy decoder; progressive files, which it does not take, go
  * through the host Huffman decoder and a plan.
  *
- *   make -C examples && examples/jpeg2bmp [--scale N] out_dir a.jpg [b.jpg ...]
+ *   make -C examples && examples/jpeg2bmp [--roi x,y,w,h] [--scale N] out_dir a.jpg [b.jpg ...]
  *
  * --scale N (2, 4 or 8; 4:4:4, 4:2:0 and gray files): the scaled decode -- the
  * BMP is ceil(W/N) x ceil(H/N) (hjd_scaled_size, hjd_gdec_set_scale,
  * hjd_plan_create_scaled).
+ * --roi x,y,w,h: every file comes out cropped to that rectangle of its output
+ * grid (the scaled one with --scale): only the strips that touch it are
+ * decoded (hjd_gdec_decode_roi, hjd_plan_create_roi).
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -58,7 +61,7 @@ static uint8_t* read_file(const char* path, size_t* size)
 
 /* Host Huffman + the fused kernel through a one-frame plan. */
 static int decode_host_path(hjd_ctx* ctx, const uint8_t* data, size_t size, const hjd_jpeg_info* info,
-                            void* d_out, int32_t pitch, int scale)
+                            void* d_out, int32_t pitch, int scale, const hjd_rect* roi)
 {
     int16_t* coefs = (int16_t*)malloc((size_t)info->nblocks * 64 * sizeof(int16_t));
     hjd_jpeg_info full;
@@ -77,7 +80,7 @@ static int decode_host_path(hjd_ctx* ctx, const uint8_t* data, size_t size, cons
     fr.qt_index[0] = 0;
     fr.qt_index[1] = 1;
     fr.qt_index[2] = 2;
-    CHECK(hjd_plan_create_scaled(ctx, &fr, 1, HJD_IN_Q16_ZIGZAG, &full.qt[0][0], 3, scale, &plan));
+    CHECK(hjd_plan_create_roi(ctx, &fr, 1, HJD_IN_Q16_ZIGZAG, &full.qt[0][0], 3, scale, roi, &plan));
     CHECK(hjd_plan_launch(plan, d_coefs, d_out, NULL, 0));
     HIP_CHECK(hipDeviceSynchronize());
     CHECK(hjd_plan_destroy(plan));
@@ -89,13 +92,25 @@ static int decode_host_path(hjd_ctx* ctx, const uint8_t* data, size_t size, cons
 int main(int argc, char** argv)
 {
     int scale = 1;
-    if (argc >= 3 && !strcmp(argv[1], "--scale")) {
-        scale = atoi(argv[2]);
+    hjd_rect rect;
+    const hjd_rect* roi = NULL;
+    const char* prog = argv[0];
+    while (argc >= 3 && (!strcmp(argv[1], "--scale") || !strcmp(argv[1], "--roi"))) {
+        if (!strcmp(argv[1], "--scale")) {
+            scale = atoi(argv[2]);
+        } else {
+            char tail = 0;
+            if (sscanf(argv[2], "%d,%d,%d,%d%c", &rect.x, &rect.y, &rect.w, &rect.h, &tail) != 4) {
+                fprintf(stderr, "--roi takes x,y,w,h, not \"%s\"\n", argv[2]);
+                return 2;
+            }
+            roi = &rect;
+        }
         argv += 2;
         argc -= 2;
     }
     if (argc < 3) {
-        fprintf(stderr, "usage: %s [--scale 1|2|4|8] out_dir file.jpg...\n", argv[0]);
+        fprintf(stderr, "usage: %s [--roi x,y,w,h] [--scale 1|2|4|8] out_dir file.jpg...\n", prog);
         return 2;
     }
     hjd_ctx* ctx = NULL;
@@ -111,6 +126,11 @@ int main(int argc, char** argv)
         CHECK(hjd_jpeg_parse(data, size, &info));
         int out_w = 0, out_h = 0;
         CHECK(hjd_scaled_size(info.width, info.height, scale, &out_w, &out_h));
+        if (roi) {   /* validated here, so a bad rectangle ends the run before any device work */
+            CHECK(hjd_roi_geometry(info.width, info.height, info.sampling, scale, roi, NULL, NULL));
+            out_w = roi->w;
+            out_h = roi->h;
+        }
         const int32_t pitch = out_w * 4;
         const size_t bytes = (size_t)pitch * (size_t)out_h;
         void* d_out = NULL;
@@ -124,10 +144,13 @@ int main(int argc, char** argv)
             void* outs[1] = {d_out};
             const int32_t pitches[1] = {pitch};
             int32_t status = 0;
-            CHECK(hjd_gdec_decode(gd, datas, sizes, 1, outs, pitches, NULL));
+            if (roi)
+                CHECK(hjd_gdec_decode_roi(gd, datas, sizes, 1, roi, outs, pitches, NULL));
+            else
+                CHECK(hjd_gdec_decode(gd, datas, sizes, 1, outs, pitches, NULL));
             CHECK(hjd_gdec_sync(gd, &status));
             CHECK(hjd_gdec_destroy(gd));
-        } else if (decode_host_path(ctx, data, size, &info, d_out, pitch, scale)) {
+        } else if (decode_host_path(ctx, data, size, &info, d_out, pitch, scale, roi)) {
             return 1;
         }
         uint8_t* px = (uint8_t*)malloc(bytes);
@@ -148,6 +171,7 @@ int main(int argc, char** argv)
                info.sampling, info.process, info.single_scan ? "1" : "several", path,
                info.process != 2 ? "GPU" : "host");
         if (scale != 1) printf("  scale 1/%d: %dx%d\n", scale, out_w, out_h);
+        if (roi) printf("  roi %d,%d %dx%d\n", roi->x, roi->y, roi->w, roi->h);
         free(px);
         HIP_CHECK(hipFree(d_out));
         free(data);

@@ -175,6 +175,53 @@ int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int inpu
 int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                            const int32_t* qtables, int nq, int scale, hjd_plan** out);
 int hjd_plan_scale(const hjd_plan* plan);          /* 1, 2, 4 or 8 */
+
+/*
+ * Region-of-interest decode.  A ROI is a rectangle (x, y, w, h) on the
+ * frame's output grid W' x H': the frame's own W x H in a scale-1 plan,
+ * hjd_scaled_size(W, H, scale) in a scaled one.  It must satisfy x, y >= 0,
+ * w, h >= 1, x + w <= W', y + h <= H'; anything else is HJD_E_INVALID.  The
+ * output of a ROI frame is exactly full[y:y+h, x:x+w], where `full` is what
+ * the same plan without the ROI writes: bit-exact in every output format, no
+ * new arithmetic.  Pixel (x, y) of the frame lands at out_offset; out_pitch,
+ * its minimum (row bytes x w) and its alignment rules refer to the ROI width;
+ * the planar plane stride is out_pitch * h; no byte outside the w x h payload
+ * is written.
+ *
+ * Only the strips (tasks of 48 blocks of one MCU row) that touch the
+ * rectangle are decoded, and the strips are anchored at the ROI's first MCU
+ * column: hjd_roi_geometry gives the count.  Coefficients of other strips are
+ * never read.
+ *
+ * Vector stores: let dx be x minus the first pixel column of the MCU that
+ * holds x (on the output grid).  Strips wholly inside the ROI keep the
+ * full-width vector stores when dx % 4 == 0 (at scale 1, and wherever the
+ * scaled MCU is >= 4 px wide, that is x % 4 == 0) and out_pitch and
+ * out_offset meet the format's present alignment (16 bytes BGRX, 4 bytes the
+ * 3-byte and planar formats).  Any other x is legal and takes the guarded
+ * stores for every strip, as an unaligned pitch does today.
+ *
+ * A ROI plan takes HJD_IN_Q16_ZIGZAG input, all four output formats, every
+ * sampling at scale 1 and 4:4:4 / 4:2:0 / gray at scale 2, 4, 8, through the
+ * persistent kernel only (HJD_KERNEL_AUTO takes it however few tasks there
+ * are).  HJD_IN_I32_NATURAL, a non-zero hjd_plan_set_variant,
+ * hjd_plan_set_kernel(HJD_KERNEL_LATENCY) and hjd_debug_plan_launch_stages
+ * return HJD_E_INVALID.  hjd_plan_set_chunk and hjd_plan_autotune work (the
+ * cache key includes the ROI flag).
+ */
+typedef struct hjd_rect { int32_t x, y, w, h; } hjd_rect;
+/* Validates `roi` against a width x height source of `sampling` at `scale`
+ * and returns the ROI's task count and the coefficient blocks those tasks
+ * read (strips are clipped at the MCU-row end).  Host only: needs no device. */
+int hjd_roi_geometry(int width, int height, int sampling, int scale, const hjd_rect* roi, int64_t* tasks,
+                     int64_t* blocks);
+/* rois == NULL: exactly hjd_plan_create_scaled.  Otherwise one rectangle per
+ * frame; frames carry the source size.  hjd_plan_pixels is then the sum of
+ * w * h, hjd_plan_tasks the ROI task count and hjd_plan_coef_bytes 128 x the
+ * blocks read. */
+int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
+                        const int32_t* qtables, int nq, int scale, const hjd_rect* rois, hjd_plan** out);
+int hjd_plan_has_roi(const hjd_plan* plan);        /* 1: created with rois */
 int hjd_plan_destroy(hjd_plan* plan);
 /* Tuning hook: kernel variant bits (0 = default).  bit 0: plain instead of
  * non-temporal output stores; bit 1: workgroup-interleaved task order.

@@ -181,6 +181,16 @@ int hjd_gdec_set_output_format(hjd_gdec* g, int out_format);
  * holding a 4:2:2, 4:1:1 or 4:4:0 file fails (HJD_E_INVALID) before anything
  * is enqueued.  hjd_gdec_decode_coefs is unaffected. */
 int hjd_gdec_set_scale(hjd_gdec* g, int scale);
+/* hjd_gdec_decode with one region of interest per image (include/hjd.h,
+ * hjd_plan_create_roi): rois[i] is a rectangle on image i's output grid at the
+ * decoder's current scale, image i comes out rois[i].w x rois[i].h with its
+ * pixel (x, y) at d_outs[i], and pitches[] and the planar plane stride refer
+ * to the ROI.  The entropy decode still covers the whole scan; only the pixel
+ * kernel and the output shrink.  A call with an invalid rectangle, or one
+ * combining scale > 1 with a 4:2:2, 4:1:1 or 4:4:0 file, fails
+ * (HJD_E_INVALID) before anything is enqueued. */
+int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                        void* const* d_outs, const int32_t* pitches, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

@@ -41,6 +41,7 @@ from .backend import (  # noqa: E402
     device_worker_cpus,
     frame_blocks,
     mcu_geometry,
+    roi_geometry,
     scaled_size,
     stream_worker_threads,
     worker_cpus,
@@ -55,6 +56,6 @@ __all__ = [
     "decode_coefs_batch", "decode_coefs_into", "decode_jpeg", "emulate_entropy",
     "parse", "pinned_bytes",
     "Context", "FrameSpec", "Plan", "autotune_cache_clear", "decode_frame", "device_count", "frame_blocks", "mcu_geometry", "worker_cpus", "cpu_share", "debug_tuning",
-    "device_worker_cpus", "stream_worker_threads", "scaled_size",
+    "device_worker_cpus", "stream_worker_threads", "scaled_size", "roi_geometry",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -32,6 +32,11 @@ class HjdFrame(ctypes.Structure):
 assert ctypes.sizeof(HjdFrame) == 48
 
 
+class HjdRect(ctypes.Structure):
+    """struct hjd_rect (include/hjd.h): a ROI (x, y, w, h) on a frame's output grid."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("x", "y", "w", "h")]
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -92,6 +97,13 @@ SIGNATURES = {
     "hjd_plan_create_scaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdFrame), ctypes.c_int, ctypes.c_int,
                                               c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "hjd_plan_scale": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_roi_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(HjdRect), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_int64)]),
+    "hjd_plan_create_roi": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdFrame), ctypes.c_int, ctypes.c_int,
+                                           c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(HjdRect),
+                                           ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_plan_has_roi": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_plan_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_plan_set_variant": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "hjd_plan_set_kernel": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -191,6 +203,8 @@ def _bind_host(lib):
         "hjd_gdec_sync": (ctypes.c_int, [vp, c_i32p]),
         "hjd_gdec_set_output_format": (ctypes.c_int, [vp, ctypes.c_int]),
         "hjd_gdec_set_scale": (ctypes.c_int, [vp, ctypes.c_int]),
+        "hjd_gdec_decode_roi": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int,
+                                               ctypes.POINTER(HjdRect), ctypes.POINTER(vp), c_i32p, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import HjdFrame, check
+from ._lib import HjdFrame, HjdRect, check
 
 YUV444 = 0
 YUV420 = 1  # == the reference's ColorSpace::YUV411 (src/macro.h:114-119), H2V2
@@ -75,6 +75,18 @@ def scaled_size(width: int, height: int, scale: int):
     check(_lib.load().hjd_scaled_size(int(width), int(height), int(scale), ctypes.byref(w), ctypes.byref(h)),
           "hjd_scaled_size")
     return w.value, h.value
+
+
+def roi_geometry(width: int, height: int, sampling: int, scale: int, roi):
+    """(tasks, blocks) of the ROI (x, y, w, h) on the output grid of a
+    width x height source of `sampling` at `scale` (hjd_roi_geometry): the
+    pixel kernel's tasks and the coefficient blocks they read.  An invalid
+    rectangle raises HjdError.  Host only."""
+    r = HjdRect(*[int(v) for v in roi])
+    tasks, blocks = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.load().hjd_roi_geometry(int(width), int(height), int(sampling), int(scale), ctypes.byref(r),
+                                       ctypes.byref(tasks), ctypes.byref(blocks)), "hjd_roi_geometry")
+    return tasks.value, blocks.value
 
 
 def frame_blocks(width: int, height: int, sampling: int) -> int:
@@ -179,10 +191,17 @@ class FrameSpec:
     out_pitch: int = 0            # bytes (0 -> default_pitch(width, out_format); of the scaled width in a scaled plan)
     qt_index: Sequence[int] = field(default_factory=lambda: (0, 1, 1))
     out_format: int = OUT_BGRX
+    roi: Optional[Sequence[int]] = None   # (x, y, w, h) on the output grid: the frame comes out cropped to it
 
     @property
     def pitch(self) -> int:
-        return self.out_pitch or default_pitch(self.width, self.out_format)
+        return self.out_pitch or default_pitch(self.roi[2] if self.roi is not None else self.width, self.out_format)
+
+    def out_size(self, scale: int = 1):
+        """(W, H) of what the frame writes: the ROI's, else the (scaled) frame's."""
+        if self.roi is not None:
+            return int(self.roi[2]), int(self.roi[3])
+        return (self.width, self.height) if scale == 1 else scaled_size(self.width, self.height, scale)
 
     def to_c(self, scale: int = 1) -> HjdFrame:
         """The C record; width and height stay the source's, out_pitch = 0
@@ -192,7 +211,7 @@ class FrameSpec:
         f.out_offset = self.out_offset
         f.width = self.width
         f.height = self.height
-        f.out_pitch = self.pitch if scale == 1 else (
+        f.out_pitch = self.pitch if scale == 1 or self.roi is not None else (
             self.out_pitch or default_pitch(scaled_size(self.width, self.height, scale)[0], self.out_format))
         f.sampling = self.sampling
         for i in range(3):
@@ -208,7 +227,9 @@ class Plan:
                  qtables: Optional[np.ndarray] = None, scale: int = 1):
         """scale 2, 4 or 8: a scaled plan (hjd_plan_create_scaled).  Frames
         carry the source size; every frame comes out scaled_size(W, H, scale)
-        and out_pitch (0: default_pitch of the scaled width) refers to that."""
+        and out_pitch (0: default_pitch of the scaled width) refers to that.
+        A plan is a ROI plan (hjd_plan_create_roi) when any frame has a roi;
+        frames without one take their whole output grid."""
         self.ctx = ctx
         self.lib = ctx.lib
         self.frames = list(frames)
@@ -221,7 +242,13 @@ class Plan:
         else:
             q, qp, nq = None, None, 0
         h = ctypes.c_void_p()
-        if scale == 1:
+        if any(f.roi is not None for f in self.frames):
+            whole = [(0, 0) + f.out_size(scale) for f in self.frames]
+            rects = (HjdRect * len(self.frames))(*[HjdRect(*[int(v) for v in (f.roi if f.roi is not None else r)])
+                                                   for f, r in zip(self.frames, whole)])
+            check(self.lib.hjd_plan_create_roi(ctx.handle, arr, len(self.frames), input_format, qp, nq, int(scale),
+                                               rects, ctypes.byref(h)), "hjd_plan_create_roi")
+        elif scale == 1:
             check(self.lib.hjd_plan_create(ctx.handle, arr, len(self.frames), input_format, qp, nq, ctypes.byref(h)),
                   "hjd_plan_create")
         else:
@@ -229,6 +256,7 @@ class Plan:
                                                   ctypes.byref(h)), "hjd_plan_create_scaled")
         self.handle = h
         self.scale = self.lib.hjd_plan_scale(h)
+        self.has_roi = bool(self.lib.hjd_plan_has_roi(h))
         self.input_format = input_format
         self.tasks = self.lib.hjd_plan_tasks(h)
         self.pixels = self.lib.hjd_plan_pixels(h)
@@ -238,8 +266,8 @@ class Plan:
         self.coef_elems_needed = max([64 * (f.coef_offset + frame_blocks(f.width, f.height, f.sampling))
                                       for f in self.frames] or [0])
         self.out_bytes_needed = 0
-        for f, c in zip(self.frames, arr):   # on the scaled size (scale 1: the frame's own)
-            sw, sh = (f.width, f.height) if scale == 1 else scaled_size(f.width, f.height, scale)
+        for f, c in zip(self.frames, arr):   # on the ROI's or the scaled size (scale 1: the frame's own)
+            sw, sh = f.out_size(scale)
             self.out_bytes_needed = max(self.out_bytes_needed, f.out_offset + (out_rows(sh, f.out_format) - 1) *
                                         c.out_pitch + _ROW_BYTES[f.out_format] * sw)
 
@@ -389,15 +417,15 @@ def debug_tuning(name: str, value):
 
 
 def decode_frame(ctx: Context, coefs, qt: np.ndarray, width: int, height: int, sampling: int,
-                 input_format: int = IN_Q16_ZIGZAG, stream=None, scale: int = 1):
+                 input_format: int = IN_Q16_ZIGZAG, stream=None, scale: int = 1, roi=None):
     """Decode one frame already resident on the device; returns an int32 (H, W)
     device tensor holding BGRX words (0x00RRGGBB); scale 2, 4 or 8: (H', W') =
-    scaled_size(width, height, scale), reversed."""
+    scaled_size(width, height, scale), reversed; roi (x, y, w, h) on that
+    grid: an (h, w) tensor."""
     import torch
-    plan = Plan(ctx, [FrameSpec(width, height, sampling, qt_index=(0, 1, 2))], input_format,
-                qtables=qt if input_format == IN_Q16_ZIGZAG else None, scale=scale)
-    if scale != 1:
-        width, height = scaled_size(width, height, scale)
+    spec = FrameSpec(width, height, sampling, qt_index=(0, 1, 2), roi=roi)
+    plan = Plan(ctx, [spec], input_format, qtables=qt if input_format == IN_Q16_ZIGZAG else None, scale=scale)
+    width, height = spec.out_size(scale)
     out = torch.empty((height, width), dtype=torch.int32, device=coefs.device)
     plan.launch(coefs, out, stream)
     return out, plan

@@ -31,6 +31,7 @@
 #include <deque>
 #include <mutex>
 #include <new>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -432,7 +433,7 @@ Caps make_caps(int max_frames, int64_t max_scan_bytes, int64_t max_blocks, int s
     c.max_segs = max_blocks + ef;
     c.max_tiles = max_scan_bytes / kTileBytes + max_frames;
     const size_t per_frame = (sizeof(EntFrame) + sizeof(HuffLut) * kMaxTables + 8) * kMaxScans + sizeof(FrameRecord) +
-                             192 * 4 + sizeof(RawFrame) + 4;
+                             sizeof(hjd_internal::RoiRecord) + 192 * 4 + sizeof(RawFrame) + 4;
     c.hdr_cap = align_up(per_frame * max_frames + 4 * static_cast<size_t>(c.max_segs + c.max_wgs + c.max_tiles) +
                              10 * kAlign, kAlign);
     c.data = c.hdr_cap;
@@ -2420,6 +2421,13 @@ struct hjd_gdec {
     uint8_t* out_base[kClasses] = {};
     int out_format = HJD_OUT_BGRX;      // pixel output format (hjd_gdec_set_output_format)
     int scale = 1;                      // decode scale of hjd_gdec_decode: 1, 2, 4 or 8 (hjd_gdec_set_scale)
+    // hjd_gdec_decode_roi: one rectangle per image for the call being issued
+    // (else null).  Each sampling class's records are then followed by its
+    // RoiRecord table (launch_decode: d_frames + nframes), so a record slot
+    // takes kRoiSlot bytes; roi_batch: the issued batch was laid out that way.
+    const hjd_rect* rois = nullptr;
+    bool roi_batch = false;
+    static constexpr size_t kRoiSlot = sizeof(FrameRecord) + sizeof(hjd_internal::RoiRecord);
 };
 
 int hjd_gdec::wait_staging()
@@ -2586,7 +2594,7 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
     o.seg = align_up(o.tabs + sizeof(HuffLut) * ntab, kAlign);
     o.wg = align_up(o.seg + 4 * nseg, kAlign);
     o.recs = align_up(o.wg + 4 * nwg, kAlign);
-    o.qt = align_up(o.recs + (d_outs ? sizeof(FrameRecord) * n : 0), kAlign);
+    o.qt = align_up(o.recs + (d_outs ? (rois ? kRoiSlot : sizeof(FrameRecord)) * n : 0), kAlign);
     size_t ntiles = 0;
     for (const Prepared& p : frames)
         if (p.destuff != kDestuffHost)
@@ -2649,6 +2657,7 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
         tasks[k] = 0;
         out_base[k] = nullptr;
     }
+    roi_batch = d_outs && rois;
     if (d_outs) {   // pixel-kernel records grouped by sampling class (one launch each)
         FrameRecord* recs = reinterpret_cast<FrameRecord*>(h_stage + o.recs);
         int32_t* qtn = reinterpret_cast<int32_t*>(h_stage + o.qt);
@@ -2657,31 +2666,44 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
         const int pmask = hjd_internal::out_format_any_alignment(out_format) ? 0 : 3;
         for (int i = 0; i < n; ++i) {
             const Prepared& p = frames[i];
-            if (!d_outs[i] || !pitches || pitches[i] < obytes * hjd_internal::scaled_dim(p.width, scale) ||
+            const int out_w = rois ? rois[i].w : hjd_internal::scaled_dim(p.width, scale);
+            if (!d_outs[i] || !pitches || pitches[i] < obytes * out_w ||
                 (pitches[i] & pmask) ||
                 (reinterpret_cast<uintptr_t>(d_outs[i]) & amask))
                 return set_error(HJD_E_INVALID,
                                  "frame %d: bad output buffer or pitch (BGRX: 16-byte aligned, >= 4*width; "
                                  "BGR24: 4-byte aligned, >= 3*width; RGB24: >= 3*width; planar RGB: >= width; "
-                                 "width = the scaled width)", i);
+                                 "width = the scaled width, or the ROI's)", i);
             ++nrec[sampling_class(p.sampling)];
         }
         int r[kClasses];
         for (int k = 0, acc = 0; k < kClasses; acc += nrec[k], ++k) r[k] = acc;
+        int written[kClasses] = {};
         for (int i = 0; i < n; ++i) {
             const Prepared& p = frames[i];
             const int sidx = sampling_class(p.sampling);
             if (!out_base[sidx]) out_base[sidx] = static_cast<uint8_t*>(d_outs[i]);
             const int qti[3] = {3 * i, 3 * i + 1, 3 * i + 2};
             FrameRecord rec;
+            hjd_internal::RoiRecord side;
             const int64_t t = hjd_internal::make_frame_record(
                 p.width, p.height, p.sampling, static_cast<int64_t>(ef[i].coef_off),
                 static_cast<int64_t>(static_cast<uint8_t*>(d_outs[i]) - out_base[sidx]), pitches[i], qti, &rec,
-                out_format, reinterpret_cast<uintptr_t>(out_base[sidx]), scale);
+                out_format, reinterpret_cast<uintptr_t>(out_base[sidx]), scale, rois ? &rois[i] : nullptr,
+                rois ? &side : nullptr);
             if (t < 0) return static_cast<int>(t);
             rec.task_begin = tasks[sidx];
             tasks[sidx] += t;
-            recs[r[sidx]++] = rec;
+            if (rois) {   // class k's block: nrec[k] records, then nrec[k] side records
+                const int k0 = r[sidx] - written[sidx];   // records of the classes before this one
+                uint8_t* blockp = h_stage + o.recs + kRoiSlot * static_cast<size_t>(k0);
+                reinterpret_cast<FrameRecord*>(blockp)[written[sidx]] = rec;
+                reinterpret_cast<hjd_internal::RoiRecord*>(blockp + sizeof(FrameRecord) * nrec[sidx])[written[sidx]] = side;
+                ++written[sidx];
+                ++r[sidx];
+            } else {
+                recs[r[sidx]++] = rec;
+            }
             for (int c = 0; c < 3; ++c)
                 for (int k = 0; k < 64; ++k) qtn[(3 * i + c) * 64 + kZigzag[k]] = p.qt[c][k];
         }
@@ -3094,8 +3116,10 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
             rc = hjd_internal::launch_decode(
                 g->device, g->num_cu, hjd_gdec::kClassSampling[sidx], HJD_IN_Q16_ZIGZAG, 0, coefs,
                 reinterpret_cast<const int32_t*>(g->d_blob + g->H.qt),
-                reinterpret_cast<const FrameRecord*>(g->d_blob + g->H.recs) + r0, g->nrec[sidx], g->tasks[sidx],
-                g->out_base[sidx], s, 0, g->out_format, HJD_KERNEL_AUTO, g->scale);
+                reinterpret_cast<const FrameRecord*>(
+                    g->d_blob + g->H.recs + (g->roi_batch ? hjd_gdec::kRoiSlot : sizeof(FrameRecord)) * r0),
+                g->nrec[sidx], g->tasks[sidx], g->out_base[sidx], s, 0, g->out_format,
+                g->roi_batch ? HJD_KERNEL_PERSISTENT : HJD_KERNEL_AUTO, g->scale, g->roi_batch);
             if (rc) return rc;
             r0 += g->nrec[sidx];
         }
@@ -3277,6 +3301,29 @@ int hjd_gdec_decode(hjd_gdec* g, const uint8_t* const* datas, const size_t* size
                                  g->scale, h.sampling);
     }
     return gdec_run(g, datas, sizes, n, d_outs, pitches, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                        void* const* d_outs, const int32_t* pitches, void* stream)
+{
+    if (!d_outs) return set_error(HJD_E_INVALID, "d_outs is NULL");
+    if (!rois) return set_error(HJD_E_INVALID, "rois is NULL");
+    if (g && datas && sizes) {
+        // an invalid rectangle, or a scale the file's sampling does not serve,
+        // is refused before anything is staged or enqueued (a malformed file
+        // fails in staging)
+        hjd_internal::ScanHeader h;
+        hjd_internal::RoiGeom rg;
+        for (int i = 0; i < n; ++i)
+            if (datas[i] && hjd_internal::parse_scan_header(datas[i], sizes[i], &h) == HJD_OK) {
+                const int rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rois[i], &rg);
+                if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+            }
+    }
+    if (g) g->rois = rois;
+    const int rc = gdec_run(g, datas, sizes, n, d_outs, pitches, nullptr, nullptr, static_cast<hipStream_t>(stream));
+    if (g) g->rois = nullptr;
+    return rc;
 }
 
 int hjd_gdec_decode_coefs(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, int16_t* d_coefs,

@@ -7,6 +7,7 @@
 
 struct hjd_ctx;
 struct hjd_jpeg_info;
+struct hjd_rect;
 
 namespace hjd_internal {
 
@@ -43,14 +44,36 @@ struct FrameRecord {
     int32_t vec_ok;
 };
 
+// Second per-frame record of a ROI launch (layout of hjd::RoiDev): the table
+// of them follows the frame records, at d_frames + nframes.
+struct RoiRecord {
+    int32_t row_stride, dx, dy, reserved;
+};
+
+// A ROI on a frame's output grid (the grid of `scale`), validated, in the
+// terms the kernel needs.
+struct RoiGeom {
+    int mxf, myf;       // first MCU column / row the ROI touches
+    int strips, rows;   // tasks per MCU row, MCU rows
+    int dx, dy;         // the ROI's origin relative to MCU (mxf, myf)'s pixel (0,0)
+    int mcu_w, rem_w;   // the frame's MCUs per row; those from mxf to the row end
+    int bpm;
+    int64_t tasks, blocks;   // blocks: the coefficient blocks the tasks read
+};
+// HJD_OK, or HJD_E_INVALID with the cause in the error string.
+int roi_geom(int width, int height, int sampling, int scale, const ::hjd_rect* roi, RoiGeom* g);
+
 // Fill a one-frame record (task_begin 0); returns the frame's task count, or
 // a negative status for an unsupported geometry.  out_format: HJD_OUT_*;
 // base_bits: low bits of the address out_base is relative to (out_vector_ok).
 // scale (1, 2, 4, 8): width and height are the source's; the record holds the
 // scaled size (scaled_dim) and `pitch` refers to it.
+// roi (with `side`): the record is re-anchored at the ROI's first MCU, `side`
+// gets its RoiRecord, out_base is where the ROI's first pixel lands and
+// `pitch` refers to the ROI width.
 int64_t make_frame_record(int width, int height, int sampling, int64_t coef_base, int64_t out_base, int pitch,
                           const int qt_index[3], FrameRecord* rec, int out_format = 0, uintptr_t base_bits = 0,
-                          int scale = 1);
+                          int scale = 1, const ::hjd_rect* roi = nullptr, RoiRecord* side = nullptr);
 
 // Scaled decode (hjd_plan_create_scaled): log2 of a legal scale, or -1.
 inline int scale_log2(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }
@@ -63,7 +86,8 @@ inline bool scaled_sampling_ok(int sampling) { return sampling == 0 || sampling 
 // qtables (no host synchronisation, safe to call from any host thread).
 int launch_decode(int device, int num_cu, int sampling, int input_format, int variant, const void* d_coefs,
                   const int32_t* d_qt_nat, const FrameRecord* d_frames, int nframes, int64_t tasks, void* d_out,
-                  void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0, int scale = 1);
+                  void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0, int scale = 1,
+                  bool roi = false);   // roi: the RoiRecord table follows d_frames[nframes - 1]
 
 // Bytes per output pixel of an HJD_OUT_* format overall (0 if unknown).
 inline int out_format_bytes(int out_format)

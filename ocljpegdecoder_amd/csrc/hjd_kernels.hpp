@@ -52,6 +52,20 @@ struct FrameDev {
 };
 static_assert(sizeof(FrameDev) == 64, "FrameDev layout");
 
+// Second per-frame table of a ROI plan (hjd_plan_create_roi), appended to the
+// frame table at frames + nframes; only the ROI kernels read it.  A ROI
+// frame's FrameDev is re-anchored at the ROI's first MCU (mxf, myf):
+// coef_base is that MCU's first block, out_base the (possibly negative)
+// address of the anchor MCU's pixel (0,0), width = dx + w, height = dy + h,
+// mcu_w the MCUs from the anchor to the true MCU-row end (the nblk clip),
+// strips the ROI's strips per MCU row.
+struct RoiDev {
+    int32_t row_stride;   // the frame's true MCUs per MCU row (coefficient row stride)
+    int32_t dx, dy;       // the ROI's first pixel, relative to the anchor MCU
+    int32_t reserved;     // 0
+};
+static_assert(sizeof(RoiDev) == 16, "RoiDev layout");
+
 // Natural index n -> zigzag position (inverse of the JPEG zigzag, src/zigzag.h).
 __device__ __forceinline__ int zz_of_natural(int n)
 {
@@ -82,8 +96,10 @@ struct FrameCursor {
     int64_t coef_base, out_base;
     int width, height, pitch, mcu_w, strips, vec_ok;
     int qt0, qt1, qt2;
+    int row_stride, dx, dy;  // ROI kernels only (RoiDev)
 };
 
+template <bool kRoi = false>
 __device__ __forceinline__ void cursor_load(FrameCursor& c, const FrameDev* __restrict__ fr, int nframes,
                                             int64_t total, int i)
 {
@@ -102,6 +118,12 @@ __device__ __forceinline__ void cursor_load(FrameCursor& c, const FrameDev* __re
     c.qt0 = f.qt[0];
     c.qt1 = f.qt[1];
     c.qt2 = f.qt[2];
+    if constexpr (kRoi) {
+        const RoiDev& r = reinterpret_cast<const RoiDev*>(fr + nframes)[i];
+        c.row_stride = r.row_stride;
+        c.dx = r.dx;
+        c.dy = r.dy;
+    }
 }
 
 // The frame owning `task` (once per wave, scalar).  Batches of equal frames
@@ -109,6 +131,7 @@ __device__ __forceinline__ void cursor_load(FrameCursor& c, const FrameDev* __re
 // against the record it loads anyway, so a wave start costs two dependent
 // scalar loads instead of a ~log2(nframes)-deep binary search, which is the
 // fallback for mixed plans.
+template <bool kRoi = false>
 __device__ __forceinline__ void cursor_seek(FrameCursor& c, const FrameDev* __restrict__ fr, int nframes,
                                             int64_t total, int64_t task)
 {
@@ -117,7 +140,7 @@ __device__ __forceinline__ void cursor_seek(FrameCursor& c, const FrameDev* __re
         if (k > 0 && task < (int64_t(1) << 32)) {
             const int64_t g = static_cast<uint32_t>(task) / static_cast<uint32_t>(k);   // 32-bit udiv
             if (g < nframes) {
-                cursor_load(c, fr, nframes, total, static_cast<int>(g));
+                cursor_load<kRoi>(c, fr, nframes, total, static_cast<int>(g));
                 if (c.begin <= task && task < c.end) return;
             }
         }
@@ -127,7 +150,7 @@ __device__ __forceinline__ void cursor_seek(FrameCursor& c, const FrameDev* __re
         const int mid = (lo + hi + 1) >> 1;
         if (fr[mid].task_begin <= task) lo = mid; else hi = mid - 1;
     }
-    cursor_load(c, fr, nframes, total, lo);
+    cursor_load<kRoi>(c, fr, nframes, total, lo);
 }
 
 // Compile-time geometry of the kernel's sampling index (hjd_internal::
@@ -154,7 +177,9 @@ struct TaskGeom {
 
 // kLog: log2 of the decode scale (scaled kernels): the strip's position on
 // the scaled output grid; the MCU and block arithmetic stays in source units.
-template <int kSampling, int kLog = 0>
+// kRoi: the cursor is re-anchored at the ROI's first MCU; c.mcu_w counts the
+// MCUs from there to the true row end and c.row_stride is the row stride.
+template <int kSampling, int kLog = 0, bool kRoi = false>
 __device__ __forceinline__ TaskGeom task_geom(const FrameCursor& c, int64_t task)
 {
     using G = KGeom<kSampling>;
@@ -163,7 +188,7 @@ __device__ __forceinline__ TaskGeom task_geom(const FrameCursor& c, int64_t task
     const int mx0 = (local - my * c.strips) * G::kMcus;
     TaskGeom g;
     g.nblk = min(G::kMcus, c.mcu_w - mx0) * G::kBpm;
-    g.blk0 = c.coef_base + (static_cast<int64_t>(my) * c.mcu_w + mx0) * G::kBpm;
+    g.blk0 = c.coef_base + (static_cast<int64_t>(my) * (kRoi ? c.row_stride : c.mcu_w) + mx0) * G::kBpm;
     g.y_base = (my * G::kMcuH) >> kLog;
     g.x_base = (mx0 * G::kMcuW) >> kLog;
     return g;
@@ -202,6 +227,29 @@ constexpr int kOutPlanar = 1024;
 // (decode_kernel; the latency kernel has no scaled form).
 constexpr int kScaleShift = 11;
 constexpr int kVarScale = 3 << kScaleShift;
+// ROI decode (hjd_plan_create_roi): the guarded stores also take the lower
+// bounds dx, dy of the re-anchored frame (RoiDev); int16 zigzag input, output
+// format and scale bits only.
+constexpr int kVarRoi = 1 << 13;
+// Column x / row y of the (re-anchored) frame is stored: below width /
+// height, and in a ROI kernel not below d (one unsigned compare does both).
+template <int kVariant>
+__device__ __forceinline__ bool in_bounds(int v, int limit, int d)
+{
+    if constexpr ((kVariant & kVarRoi) != 0)
+        return static_cast<uint32_t>(v - d) < static_cast<uint32_t>(limit - d);
+    else
+        return v < limit;
+}
+// Rows of one plane of a planar frame: a ROI frame's height is dy + h.
+template <int kVariant>
+__device__ __forceinline__ int plane_rows(int height, int dy)
+{
+    if constexpr ((kVariant & kVarRoi) != 0)
+        return height - dy;
+    else
+        return height;
+}
 template <int kVariant>
 constexpr int kScaleLog = (kVariant & kVarScale) >> kScaleShift;
 // Bytes per pixel within one output row (planar: of one plane's row).
@@ -224,7 +272,7 @@ constexpr int kOutBytes = (kVariant & kOutPlanar) != 0 ? 1 : (kVariant & (kOutBg
 // planes) only; their edge path stores bytes and takes any alignment.
 template <bool kFull, int kVariant = 0>
 __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff, int x, int width, uint32_t p0,
-                                       uint32_t p1, uint32_t p2, uint32_t p3, int64_t plane = 0)
+                                       uint32_t p1, uint32_t p2, uint32_t p3, int64_t plane = 0, int dx = 0)
 {
     // Pin the row base in SGPRs as a global (addrspace 1) pointer and the lane
     // offset as a 32-bit VGPR in this block: otherwise LLVM hoists
@@ -261,7 +309,7 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff,
             const uint32_t px[4] = {p0, p1, p2, p3};
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (x + k < width) {
+                if (in_bounds<kVariant>(x + k, width, dx)) {
                     dr[k] = static_cast<uint8_t>(px[k] >> 16);
                     dg[k] = static_cast<uint8_t>(px[k] >> 8);
                     db[k] = static_cast<uint8_t>(px[k]);
@@ -280,7 +328,7 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff,
             const uint32_t px[4] = {p0, p1, p2, p3};
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (x + k < width) {
+                if (in_bounds<kVariant>(x + k, width, dx)) {
                     d8[3 * k] = static_cast<uint8_t>(px[k] >> 16);
                     d8[3 * k + 1] = static_cast<uint8_t>(px[k] >> 8);
                     d8[3 * k + 2] = static_cast<uint8_t>(px[k]);
@@ -299,7 +347,7 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff,
             const uint32_t px[4] = {p0, p1, p2, p3};
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (x + k < width) {
+                if (in_bounds<kVariant>(x + k, width, dx)) {
                     d8[3 * k] = static_cast<uint8_t>(px[k]);
                     d8[3 * k + 1] = static_cast<uint8_t>(px[k] >> 8);
                     d8[3 * k + 2] = static_cast<uint8_t>(px[k] >> 16);
@@ -314,10 +362,10 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff,
         else
             __builtin_nontemporal_store(v, (gvec*)dst);
     } else {
-        if (x + 0 < width) dst[0] = p0;
-        if (x + 1 < width) dst[1] = p1;
-        if (x + 2 < width) dst[2] = p2;
-        if (x + 3 < width) dst[3] = p3;
+        if (in_bounds<kVariant>(x + 0, width, dx)) dst[0] = p0;
+        if (in_bounds<kVariant>(x + 1, width, dx)) dst[1] = p1;
+        if (in_bounds<kVariant>(x + 2, width, dx)) dst[2] = p2;
+        if (in_bounds<kVariant>(x + 3, width, dx)) dst[3] = p3;
     }
 }
 
@@ -335,12 +383,12 @@ template <bool kCheck, int kVariant, bool kFull>
 __device__ __forceinline__ void emit_row4(uint8_t* __restrict__ row, uint32_t loff, int xa, int width, uint32_t y01,
                                           uint32_t y23, const ChromaPair& p01, const ChromaPair& p23,
                                           const ChromaTerms* c0, const ChromaTerms* c1, const ChromaTerms* c2,
-                                          const ChromaTerms* c3, int64_t plane)
+                                          const ChromaTerms* c3, int64_t plane, int dx = 0)
 {
     uint32_t q0, q1, q2, q3;
     pixels2<kCheck>(y01, p01, c0, c1, q0, q1);
     pixels2<kCheck>(y23, p23, c2, c3, q2, q3);
-    store4<kFull, kVariant>(row, loff, xa, width, q0, q1, q2, q3, plane);
+    store4<kFull, kVariant>(row, loff, xa, width, q0, q1, q2, q3, plane, dx);
 }
 
 // kStride / u0: this wave converts colour units u0, u0 + kStride, ... of the
@@ -348,7 +396,8 @@ __device__ __forceinline__ void emit_row4(uint8_t* __restrict__ row, uint32_t lo
 // persistent kernel converts all of them: kStride 1, u0 0).
 template <int kSampling, bool kFull, int kVariant, int kStride = 1>
 __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int lane, uint8_t* __restrict__ out,
-                                             int pitch, int width, int height, int y_base, int x_base, int u0 = 0)
+                                             int pitch, int width, int height, int y_base, int x_base, int u0 = 0,
+                                             int dx = 0, int dy = 0)
 {
     const int cg = lane & 31;     // 4-pixel column group within the 128-px strip
     const int x0 = cg * 4;
@@ -358,7 +407,7 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
     const uint32_t loff = static_cast<uint32_t>(x0 * kPx) + static_cast<uint32_t>(ylane) * static_cast<uint32_t>(pitch);
     uint8_t* const strip = out + static_cast<int64_t>(y_base) * pitch + static_cast<int64_t>(x_base) * kPx;
     // planar: bytes between the planes' rows (wave-uniform, 64-bit: 2 * plane can pass 2^32)
-    const int64_t plane = (kVariant & kOutPlanar) != 0 ? static_cast<int64_t>(pitch) * height : 0;
+    const int64_t plane = (kVariant & kOutPlanar) != 0 ? static_cast<int64_t>(pitch) * plane_rows<kVariant>(height, dy) : 0;
     if constexpr (kSampling == 1) {
         const int m = cg >> 2;        // MCU within strip
         const int xm = x0 & 15;       // x within MCU: 0,4,8,12
@@ -385,17 +434,17 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const ChromaPair p0 = pair_of(c0, c0), p1 = pair_of(c1, c1);
             const int ya0 = y_base + y0;
             if (__builtin_amdgcn_ballot_w64((p0.flagged | p1.flagged) != 0)) {   // wave-uniform, rare
-                if (kFull || ya0 < height)
-                    emit_row4<true, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane);
-                if (kFull || ya0 + 1 < height)
+                if (kFull || in_bounds<kVariant>(ya0, height, dy))
+                    emit_row4<true, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                if (kFull || in_bounds<kVariant>(ya0 + 1, height, dy))
                     emit_row4<true, kVariant, kFull>(row0 + pitch, loff, xa, width, yb.x, yb.y, p0, p1, &c0, &c0, &c1,
-                                                     &c1, plane);
+                                                     &c1, plane, dx);
             } else {
-                if (kFull || ya0 < height)
-                    emit_row4<false, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane);
-                if (kFull || ya0 + 1 < height)
+                if (kFull || in_bounds<kVariant>(ya0, height, dy))
+                    emit_row4<false, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                if (kFull || in_bounds<kVariant>(ya0 + 1, height, dy))
                     emit_row4<false, kVariant, kFull>(row0 + pitch, loff, xa, width, yb.x, yb.y, p0, p1, &c0, &c0,
-                                                      &c1, &c1, plane);
+                                                      &c1, &c1, plane, dx);
             }
         }
     } else if constexpr (kSampling == 0) {
@@ -425,13 +474,13 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
                 const ChromaPair p01 = pair_of(c0, c1), p23 = pair_of(c2, c3);
                 const int ya = y_base + y;
                 uint8_t* row = strip + static_cast<int64_t>(4 * it + h) * pitch;   // wave-uniform
-                if (kFull || ya < height) {
+                if (kFull || in_bounds<kVariant>(ya, height, dy)) {
                     if (__builtin_amdgcn_ballot_w64((p01.flagged | p23.flagged) != 0))
                         emit_row4<true, kVariant, kFull>(row, loff, xa, width, sy.x, sy.y, p01, p23, &c0, &c1, &c2,
-                                                         &c3, plane);
+                                                         &c3, plane, dx);
                     else
                         emit_row4<false, kVariant, kFull>(row, loff, xa, width, sy.x, sy.y, p01, p23, &c0, &c1, &c2,
-                                                          &c3, plane);
+                                                          &c3, plane, dx);
                 }
             }
         }
@@ -462,11 +511,11 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
                                 static_cast<uint32_t>(cu4 * 4 * kPx);
             const int xu = x_base + cu4 * 4;
             const bool flagged = __builtin_amdgcn_ballot_w64((p0.flagged | p1.flagged) != 0) != 0;
-            if (kFull || y_base + y < height) {
+            if (kFull || in_bounds<kVariant>(y_base + y, height, dy)) {
                 if (flagged)
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
             }
         }
     } else if constexpr (kSampling == 4) {
@@ -491,11 +540,11 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const uint32_t lo = static_cast<uint32_t>(y) * static_cast<uint32_t>(pitch) +
                                 static_cast<uint32_t>(lane * 4 * kPx);
             const int xu = x_base + lane * 4;
-            if (kFull || y_base + y < height) {
+            if (kFull || in_bounds<kVariant>(y_base + y, height, dy)) {
                 if (__builtin_amdgcn_ballot_w64(p0.flagged != 0))
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane, dx);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane, dx);
             }
         }
     } else if constexpr (kSampling == 5) {
@@ -531,18 +580,18 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int xu = x_base + cu4 * 4;
             const int ya = y_base + y0;
             if (__builtin_amdgcn_ballot_w64((p01.flagged | p23.flagged) != 0)) {   // wave-uniform, rare
-                if (kFull || ya < height)
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2, &c3, plane);
-                if (kFull || ya + 1 < height)
+                if (kFull || in_bounds<kVariant>(ya, height, dy))
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
+                if (kFull || in_bounds<kVariant>(ya + 1, height, dy))
                     emit_row4<true, kVariant, kFull>(strip, lo + static_cast<uint32_t>(pitch), xu, width, syb.x,
-                                                     syb.y, p01, p23, &c0, &c1, &c2, &c3, plane);
+                                                     syb.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
             } else {
-                if (kFull || ya < height)
+                if (kFull || in_bounds<kVariant>(ya, height, dy))
                     emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2,
-                                                      &c3, plane);
-                if (kFull || ya + 1 < height)
+                                                      &c3, plane, dx);
+                if (kFull || in_bounds<kVariant>(ya + 1, height, dy))
                     emit_row4<false, kVariant, kFull>(strip, lo + static_cast<uint32_t>(pitch), xu, width, syb.x,
-                                                      syb.y, p01, p23, &c0, &c1, &c2, &c3, plane);
+                                                      syb.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
             }
         }
     } else {
@@ -562,10 +611,10 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const uint32_t g23 = sat_pk_u8(static_cast<uint32_t>(sy.y));
             const uint32_t lo = static_cast<uint32_t>(y) * static_cast<uint32_t>(pitch) +
                                 static_cast<uint32_t>(cu4 * 4 * kPx);
-            if (kFull || y_base + y < height)
+            if (kFull || in_bounds<kVariant>(y_base + y, height, dy))
                 store4<kFull, kVariant>(strip, lo, x_base + cu4 * 4, width, perm(g01, g01, 0x0c000000u),
                                         perm(g01, g01, 0x0c010101u), perm(g23, g23, 0x0c000000u),
-                                        perm(g23, g23, 0x0c010101u), plane);
+                                        perm(g23, g23, 0x0c010101u), plane, dx);
         }
     }
 }
@@ -608,7 +657,7 @@ __device__ __forceinline__ uint32_t scaled_pair(const char* __restrict__ slots, 
 template <int kSampling, int kLog, bool kFull, int kVariant>
 __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slots, int lane,
                                                     uint8_t* __restrict__ out, int pitch, int width, int height,
-                                                    int y_base, int x_base)
+                                                    int y_base, int x_base, int dx = 0, int dy = 0)
 {
     static_assert(kSampling == 0 || kSampling == 1 || kSampling == 3, "scaled decode: 4:4:4, 4:2:0 and gray");
     using G = KGeom<kSampling>;
@@ -616,7 +665,7 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
     constexpr int kUnits = kUW * (G::kMcuH >> kLog);
     constexpr int kPx = kOutBytes<kVariant>;
     uint8_t* const strip = out + static_cast<int64_t>(y_base) * pitch + static_cast<int64_t>(x_base) * kPx;
-    const int64_t plane = (kVariant & kOutPlanar) != 0 ? static_cast<int64_t>(pitch) * height : 0;
+    const int64_t plane = (kVariant & kOutPlanar) != 0 ? static_cast<int64_t>(pitch) * plane_rows<kVariant>(height, dy) : 0;
 #pragma unroll
     for (int it = 0; it < (kUnits + 63) / 64; ++it) {
         const int u = it * 64 + lane;
@@ -627,14 +676,14 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
         const int x = cu4 * 4;                           // within the scaled strip
         const uint32_t lo = static_cast<uint32_t>(y) * static_cast<uint32_t>(pitch) + static_cast<uint32_t>(x * kPx);
         const int xu = x_base + x;
-        const bool live = valid && (kFull || y_base + y < height);
+        const bool live = valid && (kFull || in_bounds<kVariant>(y_base + y, height, dy));
         const uint32_t y01 = scaled_pair<kSampling, kLog, 0>(slots, x, y);
         const uint32_t y23 = scaled_pair<kSampling, kLog, 0>(slots, x + 2, y);
         if constexpr (kSampling == 3) {
             const uint32_t g01 = sat_pk_u8(y01), g23 = sat_pk_u8(y23);
             if (live)
                 store4<kFull, kVariant>(strip, lo, xu, width, perm(g01, g01, 0x0c000000u), perm(g01, g01, 0x0c010101u),
-                                        perm(g23, g23, 0x0c000000u), perm(g23, g23, 0x0c010101u), plane);
+                                        perm(g23, g23, 0x0c000000u), perm(g23, g23, 0x0c010101u), plane, dx);
         } else if constexpr (kSampling == 0) {
             const uint32_t u01 = scaled_pair<0, kLog, 1>(slots, x, y), u23 = scaled_pair<0, kLog, 1>(slots, x + 2, y);
             const uint32_t v01 = scaled_pair<0, kLog, 2>(slots, x, y), v23 = scaled_pair<0, kLog, 2>(slots, x + 2, y);
@@ -646,9 +695,9 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
             const bool flagged = __builtin_amdgcn_ballot_w64(live && (p01.flagged | p23.flagged) != 0) != 0;
             if (live) {
                 if (flagged)   // wave-uniform, rare
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
             }
         } else {
             // 4:2:0: chroma samples x/2 and x/2 + 1 of chroma row y/2 serve 2 px each
@@ -660,9 +709,9 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
             const bool flagged = __builtin_amdgcn_ballot_w64(live && (p0.flagged | p1.flagged) != 0) != 0;
             if (live) {
                 if (flagged)   // wave-uniform, rare
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
             }
         }
     }
@@ -975,8 +1024,11 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
 {
     using L = KLayout;
     constexpr int kLog = kScaleLog<kVariant>;
-    static_assert(kLog == 0 || (kFmt == 0 && (kVariant & ~(kVarScale | kOutBgr24 | kOutRgb24 | kOutPlanar)) == 0),
+    static_assert(kLog == 0 || (kFmt == 0 && (kVariant & ~(kVarScale | kVarRoi | kOutBgr24 | kOutRgb24 | kOutPlanar)) == 0),
                   "scaled kernels: int16 zigzag input, output format bits only");
+    constexpr bool kRoi = (kVariant & kVarRoi) != 0;
+    static_assert(!kRoi || (kFmt == 0 && (kVariant & ~(kVarScale | kVarRoi | kOutBgr24 | kOutRgb24 | kOutPlanar)) == 0),
+                  "ROI kernels: int16 zigzag input, output format and scale bits only");
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerGroup * L::wave_lds];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -1019,7 +1071,7 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
         for (int k = 0; k < 4; ++k) q[c][k] = 0;
 
     FrameCursor pc;   // frame of the task being prefetched
-    cursor_seek(pc, frames, nframes, total_tasks, t_begin);
+    cursor_seek<kRoi>(pc, frames, nframes, total_tasks, t_begin);
 
     int4 pre[6];      // prefetch registers (kFmt 0): 6 x 16 B per lane = 6 KiB per wave
     auto prefetch = [&](const TaskGeom& g) {
@@ -1041,7 +1093,7 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
         }
     };
     if constexpr (kFmt == 0) {
-        prefetch(task_geom<kSampling, kLog>(pc, t_begin));
+        prefetch(task_geom<kSampling, kLog, kRoi>(pc, t_begin));
         // the first task's table rows load beside its coefficients, so a wave
         // start waits for one memory round trip, not two
         q_tables[0] = pc.qt0; q_tables[1] = pc.qt1; q_tables[2] = pc.qt2;
@@ -1053,7 +1105,7 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
     for (int64_t task = t_begin, next_task; task >= 0; task = next_task) {
         next_task = task + t_step < t_end ? task + t_step : -1;   // -1: this is the wave's last task
         const FrameCursor cc = pc;
-        const TaskGeom tg = task_geom<kSampling, kLog>(cc, task);
+        const TaskGeom tg = task_geom<kSampling, kLog, kRoi>(cc, task);
         if constexpr (kFmt == 0) {
             if (cc.qt0 != q_tables[0] || cc.qt1 != q_tables[1] || cc.qt2 != q_tables[2]) {
                 q_tables[0] = cc.qt0; q_tables[1] = cc.qt1; q_tables[2] = cc.qt2;
@@ -1067,18 +1119,24 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
             }
             wave_lds_sync();
             if (next_task >= 0) {   // the next task's loads fly during this task
-                while (next_task >= pc.end) cursor_load(pc, frames, nframes, total_tasks, pc.idx + 1);
-                prefetch(task_geom<kSampling, kLog>(pc, next_task));
+                while (next_task >= pc.end) cursor_load<kRoi>(pc, frames, nframes, total_tasks, pc.idx + 1);
+                prefetch(task_geom<kSampling, kLog, kRoi>(pc, next_task));
             }
         } else {
             if (next_task >= 0)
-                while (next_task >= pc.end) cursor_load(pc, frames, nframes, total_tasks, pc.idx + 1);
+                while (next_task >= pc.end) cursor_load<kRoi>(pc, frames, nframes, total_tasks, pc.idx + 1);
         }
 
         constexpr int kRows = KGeom<kSampling>::kMcuH >> kLog;
         constexpr int kStripW = KGeom<kSampling>::kStripW >> kLog;
         uint8_t* fout = out + cc.out_base;
-        const bool full = cc.vec_ok && tg.x_base + kStripW <= cc.width && tg.y_base + kRows <= cc.height;
+        bool full = cc.vec_ok && tg.x_base + kStripW <= cc.width && tg.y_base + kRows <= cc.height;
+        int dx = 0, dy = 0;
+        if constexpr (kRoi) {   // inside the ROI on the left and top as well
+            dx = cc.dx;
+            dy = cc.dy;
+            full = full && tg.x_base >= dx && tg.y_base >= dy;
+        }
         if constexpr ((kVariant & kAblNoIdct) == 0)
             idct_stage<kSampling, kFmt, kVariant, kLog>(slots, rowbuf, lane, zoff, q,
                                                         static_cast<const int*>(coefs) + tg.blk0 * 64, tg.nblk,
@@ -1089,16 +1147,18 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
         } else if constexpr (kLog > 0) {
             if (full)
                 colour_stage_scaled<kSampling, kLog, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height,
-                                                                     tg.y_base, tg.x_base);
+                                                                     tg.y_base, tg.x_base, dx, dy);
             else {
                 colour_stage_scaled<kSampling, kLog, false, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height,
-                                                                      tg.y_base, tg.x_base);
+                                                                      tg.y_base, tg.x_base, dx, dy);
                 __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): edge strips drain their stores, as below
             }
         } else if (full)
-            colour_stage<kSampling, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base);
+            colour_stage<kSampling, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base,
+                                                    0, dx, dy);
         else {
-            colour_stage<kSampling, false, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base);
+            colour_stage<kSampling, false, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base,
+                                                     0, dx, dy);
             // Edge strips issue a data-dependent number of stores; drain them
             // here so the loop head's wait for the prefetched coefficients can
             // be a fixed vmcnt (the full path's stores may stay in flight).

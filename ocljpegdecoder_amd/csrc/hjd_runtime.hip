@@ -92,6 +92,7 @@ struct hjd_plan {
     int autotune_launches = 0;  // kernel launches of the last hjd_plan_autotune
     int autotune_cached = 0;    // 1: that call reused a cached choice
     int scale = 1;              // hjd_plan_create_scaled: 1, 2, 4 or 8
+    int roi = 0;                // hjd_plan_create_roi with rectangles: the RoiDev table follows d_frames
 };
 
 constexpr int64_t kDefaultLatencyMaxTasks = 1024;   // measured: profiles/r01_latency_kernel.json
@@ -239,9 +240,67 @@ constexpr int kStageShift = 8;
 
 int hjd_internal::ctx_num_cu(const hjd_ctx* ctx) { return ctx->num_cu; }
 
+// The ROI's task set: MCU rows myf..myl times the strips
+// that cover MCU columns mxf..mxl, anchored at mxf.
+int hjd_internal::roi_geom(int width, int height, int sampling, int scale, const hjd_rect* roi, RoiGeom* g)
+{
+    int mw, mh, bpm, tasks_mcus;
+    int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
+    if (rc) return rc;
+    const int lg = scale_log2(scale);
+    if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    if (scale > 1 && !scaled_sampling_ok(sampling))
+        return set_error(HJD_E_INVALID, "scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not sampling %d", scale,
+                         sampling);
+    if (!roi || !g) return set_error(HJD_E_INVALID, "roi is NULL");
+    const int sw = scaled_dim(width, scale), sh = scaled_dim(height, scale);
+    if (roi->w < 1 || roi->h < 1)
+        return set_error(HJD_E_INVALID, "roi (%d,%d,%d,%d): empty rectangle (w, h >= 1)", roi->x, roi->y, roi->w, roi->h);
+    if (roi->x < 0 || roi->y < 0)
+        return set_error(HJD_E_INVALID, "roi (%d,%d,%d,%d): negative origin", roi->x, roi->y, roi->w, roi->h);
+    if (static_cast<int64_t>(roi->x) + roi->w > sw || static_cast<int64_t>(roi->y) + roi->h > sh)
+        return set_error(HJD_E_INVALID, "roi (%d,%d,%d,%d) reaches past the %dx%d output grid", roi->x, roi->y, roi->w,
+                         roi->h, sw, sh);
+    SamplingGeom sg;
+    sampling_geom(sampling, &sg);
+    const int pw = sg.mcu_px_w >> lg, ph = sg.mcu_px_h >> lg;   // MCU size on the output grid
+    g->mxf = roi->x / pw;
+    g->myf = roi->y / ph;
+    const int mxl = (roi->x + roi->w - 1) / pw, myl = (roi->y + roi->h - 1) / ph;
+    g->strips = (mxl - g->mxf + 1 + tasks_mcus - 1) / tasks_mcus;
+    g->rows = myl - g->myf + 1;
+    g->dx = roi->x - g->mxf * pw;
+    g->dy = roi->y - g->myf * ph;
+    g->mcu_w = mw;
+    g->rem_w = mw - g->mxf;
+    g->bpm = bpm;
+    g->tasks = static_cast<int64_t>(g->strips) * g->rows;
+    g->blocks = static_cast<int64_t>(g->rows) * std::min(g->strips * tasks_mcus, g->rem_w) * bpm;
+    return HJD_OK;
+}
+
+// Re-anchor a whole-frame record at the ROI's first MCU (hjd::RoiDev).
+// d.out_base and d.pitch already describe the ROI's own destination.
+static void apply_roi(FrameDev& d, hjd_internal::RoiRecord& side, const hjd_internal::RoiGeom& g, const hjd_rect& roi,
+                      int out_format, uintptr_t base_bits)
+{
+    d.coef_base += (static_cast<int64_t>(g.myf) * g.mcu_w + g.mxf) * g.bpm;
+    d.out_base -= static_cast<int64_t>(g.dy) * d.pitch +
+                  static_cast<int64_t>(g.dx) * hjd_internal::out_format_row_bytes(out_format);
+    d.width = g.dx + roi.w;
+    d.height = g.dy + roi.h;
+    d.mcu_w = g.rem_w;
+    d.strips = g.strips;
+    d.vec_ok = hjd_internal::out_vector_ok(out_format, d.pitch, d.out_base, base_bits) ? 1 : 0;
+    side.row_stride = g.mcu_w;
+    side.dx = g.dx;
+    side.dy = g.dy;
+    side.reserved = 0;
+}
+
 int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int64_t coef_base, int64_t out_base,
                                         int pitch, const int qt_index[3], FrameRecord* rec, int out_format,
-                                        uintptr_t base_bits, int scale)
+                                        uintptr_t base_bits, int scale, const hjd_rect* roi, RoiRecord* side)
 {
     int mw, mh, bpm, tasks_mcus;
     int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
@@ -264,6 +323,14 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
     d.strips = (mw + tasks_mcus - 1) / tasks_mcus;
     for (int c = 0; c < 3; ++c) d.qt[c] = qt_index ? qt_index[c] : 0;
     d.vec_ok = out_vector_ok(out_format, pitch, out_base, base_bits) ? 1 : 0;
+    if (roi) {
+        RoiGeom g;
+        if (!side) return set_error(HJD_E_INVALID, "a ROI record needs its side record");
+        rc = roi_geom(width, height, sampling, scale, roi, &g);
+        if (rc) return rc;
+        apply_roi(d, *side, g, *roi, out_format, base_bits);
+        mh = g.rows;
+    }
     memcpy(rec, &d, sizeof(d));
     return static_cast<int64_t>(d.strips) * mh;
 }
@@ -271,7 +338,7 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
 int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_format, int variant,
                                 const void* d_coefs, const int32_t* d_qt_nat, const FrameRecord* d_frames,
                                 int nframes, int64_t tasks, void* d_out, void* stream, int grid_blocks, int out_format,
-                                int kernel_mode, int scale)
+                                int kernel_mode, int scale, bool roi)
 {
     HJD_HIP(hipSetDevice(device));
     const int fmt = input_format == HJD_IN_Q16_ZIGZAG ? 0 : 1;
@@ -290,6 +357,33 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
     const int64_t split_n = (variant & 2) ? static_cast<int64_t>(grid) : static_cast<int64_t>(grid) * hjd::kWavesPerGroup;
     const int64_t split_t = (variant & 2) ? (tasks + hjd::kWavesPerGroup - 1) / hjd::kWavesPerGroup : tasks;
     const int64_t chunk = split_t / split_n, rem = split_t % split_n;
+    if (roi) {   // ROI decode: the persistent kernel only
+        const int lg = scale_log2(scale);
+        if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+        if (lg > 0 && !scaled_sampling_ok(sampling))
+            return set_error(HJD_E_INVALID, "scaled decode serves 4:4:4, 4:2:0 and gray, not sampling %d", sampling);
+        if (fmt != 0) return set_error(HJD_E_INVALID, "ROI decode takes HJD_IN_Q16_ZIGZAG input only");
+        if (variant != 0) return set_error(HJD_E_INVALID, "ROI decode has no kernel variants");
+        if (kernel_mode == HJD_KERNEL_LATENCY) return set_error(HJD_E_INVALID, "ROI decode has no latency kernel");
+#define HJD_KR1(S, V, L) hjd::decode_kernel<S, 0, (V) | ((L) << hjd::kScaleShift) | hjd::kVarRoi>
+#define HJD_KR4(S, L) HJD_KR1(S, 0, L), HJD_KR1(S, hjd::kOutBgr24, L), HJD_KR1(S, hjd::kOutRgb24, L), \
+                      HJD_KR1(S, hjd::kOutPlanar, L)
+#define HJD_KR(L) HJD_KR4(0, L), HJD_KR4(1, L), HJD_KR4(3, L)
+        // scale 1: [sampling index][output format]; scaled: [log2 scale - 1][4:4:4, 4:2:0, gray][output format]
+        static const KP kRoi1[24] = {HJD_KR4(0, 0), HJD_KR4(1, 0), HJD_KR4(2, 0), HJD_KR4(3, 0), HJD_KR4(4, 0),
+                                     HJD_KR4(5, 0)};
+        static const KP kRoiScaled[36] = {HJD_KR(1), HJD_KR(2), HJD_KR(3)};
+#undef HJD_KR
+#undef HJD_KR4
+#undef HJD_KR1
+        const int srow = sampling == HJD_YUV444 ? 0 : sampling == HJD_YUV420 ? 1 : 2;
+        const KP k = lg == 0 ? kRoi1[4 * sg.index + out_format] : kRoiScaled[12 * (lg - 1) + 4 * srow + out_format];
+        hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream), d_coefs,
+                           d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
+                           static_cast<uint8_t*>(d_out), chunk, rem);
+        HJD_HIP(hipGetLastError());
+        return HJD_OK;
+    }
     if (scale != 1) {   // scaled decode: the persistent kernel only, [log2 scale - 1][sampling][output format]
         const int lg = scale_log2(scale);
         if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
@@ -482,14 +576,31 @@ int hjd_scaled_size(int width, int height, int scale, int* out_w, int* out_h)
     return HJD_OK;
 }
 
+int hjd_roi_geometry(int width, int height, int sampling, int scale, const hjd_rect* roi, int64_t* tasks,
+                     int64_t* blocks)
+{
+    hjd_internal::RoiGeom g;
+    int rc = hjd_internal::roi_geom(width, height, sampling, scale, roi, &g);
+    if (rc) return rc;
+    if (tasks) *tasks = g.tasks;
+    if (blocks) *blocks = g.blocks;
+    return HJD_OK;
+}
+
 int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                     const int32_t* qtables, int nq, hjd_plan** out)
 {
-    return hjd_plan_create_scaled(ctx, frames, nframes, input_format, qtables, nq, 1, out);
+    return hjd_plan_create_roi(ctx, frames, nframes, input_format, qtables, nq, 1, nullptr, out);
 }
 
 int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                            const int32_t* qtables, int nq, int scale, hjd_plan** out)
+{
+    return hjd_plan_create_roi(ctx, frames, nframes, input_format, qtables, nq, scale, nullptr, out);
+}
+
+int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
+                        const int32_t* qtables, int nq, int scale, const hjd_rect* rois, hjd_plan** out)
 {
     if (!ctx || !out || (!frames && nframes > 0) || nframes < 0)
         return fail(HJD_E_INVALID, "invalid plan arguments");
@@ -499,10 +610,13 @@ int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, i
         return fail(HJD_E_INVALID, "scaled decode (scale %d) takes HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL", scale);
     if (input_format != HJD_IN_Q16_ZIGZAG && input_format != HJD_IN_I32_NATURAL)
         return fail(HJD_E_INVALID, "unknown input format %d", input_format);
+    if (rois && input_format == HJD_IN_I32_NATURAL)
+        return fail(HJD_E_INVALID, "ROI decode takes HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
     if (input_format == HJD_IN_Q16_ZIGZAG && (!qtables || nq <= 0))
         return fail(HJD_E_INVALID, "quantisation tables required for HJD_IN_Q16_ZIGZAG");
 
     std::vector<FrameDev> fd(static_cast<size_t>(std::max(nframes, 1)));
+    std::vector<hjd_internal::RoiRecord> sides(rois ? fd.size() : 0);
     int64_t tasks = 0, pixels = 0, blocks = 0;
     int sampling = nframes > 0 ? frames[0].sampling : HJD_YUV420;
     const int out_format = nframes > 0 ? frames[0].out_format : HJD_OUT_BGRX;
@@ -524,7 +638,14 @@ int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, i
             return fail(HJD_E_INVALID,
                         "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not 4:2:2, 4:1:1 or 4:4:0 "
                         "(sampling %d)", i, scale, f.sampling);
-        const int sw = hjd_internal::scaled_dim(f.width, scale), sh = hjd_internal::scaled_dim(f.height, scale);
+        int sw = hjd_internal::scaled_dim(f.width, scale), sh = hjd_internal::scaled_dim(f.height, scale);
+        hjd_internal::RoiGeom rg;
+        if (rois) {   // the output is the ROI: pitch and payload refer to it
+            rc = hjd_internal::roi_geom(f.width, f.height, f.sampling, scale, &rois[i], &rg);
+            if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
+            sw = rois[i].w;
+            sh = rois[i].h;
+        }
         if (f.out_pitch < static_cast<int64_t>(rbytes) * sw || (f.out_pitch & amask) || (f.out_offset & amask))
             return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
         FrameDev& d = fd[i];
@@ -544,9 +665,15 @@ int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, i
         d.strips = (mw + tasks_mcus - 1) / tasks_mcus;
         for (int c = 0; c < 3; ++c) d.qt[c] = input_format == HJD_IN_Q16_ZIGZAG ? f.qt_index[c] : 0;
         d.vec_ok = hjd_internal::out_vector_ok(out_format, f.out_pitch, static_cast<int64_t>(f.out_offset)) ? 1 : 0;
-        tasks += static_cast<int64_t>(d.strips) * mh;
+        if (rois) {
+            apply_roi(d, sides[i], rg, rois[i], out_format, 0);
+            tasks += rg.tasks;
+            blocks += rg.blocks;
+        } else {
+            tasks += static_cast<int64_t>(d.strips) * mh;
+            blocks += static_cast<int64_t>(mw) * mh * bpm;
+        }
         pixels += static_cast<int64_t>(sw) * sh;
-        blocks += static_cast<int64_t>(mw) * mh * bpm;
     }
 
     HJD_HIP(hipSetDevice(ctx->device));
@@ -557,6 +684,7 @@ int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, i
     p->sampling = sampling;
     p->out_format = out_format;
     p->scale = scale;
+    p->roi = rois ? 1 : 0;
     p->nframes = nframes;
     p->tasks = tasks;
     p->pixels = pixels;
@@ -570,9 +698,15 @@ int hjd_plan_create_scaled(hjd_ctx* ctx, const hjd_frame* frames, int nframes, i
         for (int t = 0; t < nq; ++t)
             for (int k = 0; k < 64; ++k) qnat[t * 64 + kZigzag[k]] = qtables[t * 64 + k];
 
-    hipError_t e = hipMalloc(&p->d_frames, fd.size() * sizeof(FrameDev));
+    // a ROI plan's RoiDev table follows the nframes records (frames + nframes)
+    static_assert(sizeof(hjd_internal::RoiRecord) == sizeof(hjd::RoiDev), "side record layout");
+    const size_t side_off = static_cast<size_t>(nframes) * sizeof(FrameDev);
+    hipError_t e = hipMalloc(&p->d_frames, fd.size() * sizeof(FrameDev) + sides.size() * sizeof(hjd::RoiDev));
     if (e == hipSuccess) e = hipMalloc(&p->d_qt, qnat.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemcpy(p->d_frames, fd.data(), fd.size() * sizeof(FrameDev), hipMemcpyHostToDevice);
+    if (e == hipSuccess && rois && nframes > 0)
+        e = hipMemcpy(reinterpret_cast<char*>(p->d_frames) + side_off, sides.data(),
+                      static_cast<size_t>(nframes) * sizeof(hjd::RoiDev), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->d_qt, qnat.data(), qnat.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(p->d_frames);
@@ -602,6 +736,7 @@ int hjd_plan_set_variant(hjd_plan* plan, int variant)
         return fail(HJD_E_INVALID, "kernel variants are BGRX-only");
     if (variant != 0 && plan->scale != 1)
         return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no kernel variants", plan->scale);
+    if (variant != 0 && plan->roi) return fail(HJD_E_INVALID, "a ROI plan has no kernel variants");
     plan->variant = variant;
     return HJD_OK;
 }
@@ -622,6 +757,7 @@ int hjd_plan_set_kernel(hjd_plan* plan, int mode)
         return fail(HJD_E_INVALID, "unknown kernel mode %d", mode);
     if (mode == HJD_KERNEL_LATENCY && plan->scale != 1)
         return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no latency kernel", plan->scale);
+    if (mode == HJD_KERNEL_LATENCY && plan->roi) return fail(HJD_E_INVALID, "a ROI plan has no latency kernel");
     plan->kernel_mode = mode;
     return HJD_OK;
 }
@@ -629,6 +765,7 @@ int hjd_plan_set_kernel(hjd_plan* plan, int mode)
 int64_t hjd_plan_tasks(const hjd_plan* plan) { return plan ? plan->tasks : -1; }
 int64_t hjd_plan_pixels(const hjd_plan* plan) { return plan ? plan->pixels : -1; }
 int hjd_plan_scale(const hjd_plan* plan) { return plan ? plan->scale : -1; }
+int hjd_plan_has_roi(const hjd_plan* plan) { return plan ? plan->roi : -1; }
 int64_t hjd_plan_coef_bytes(const hjd_plan* plan) { return plan ? plan->coef_bytes : -1; }
 
 // Grid of the fused kernel: short contiguous task chunks per wave and many
@@ -675,7 +812,7 @@ static int grid_for_chunk(int64_t tasks, int64_t per_wave, bool occupancy_floor)
 // A default launch of this plan takes the persistent kernel (not the latency one).
 static bool plan_is_persistent(const hjd_plan* p)
 {
-    return p->kernel_mode == HJD_KERNEL_PERSISTENT || p->scale != 1 ||   // a scaled plan has no latency kernel
+    return p->kernel_mode == HJD_KERNEL_PERSISTENT || p->scale != 1 || p->roi ||   // scaled / ROI: no latency kernel
            (p->kernel_mode == HJD_KERNEL_AUTO && p->tasks > latency_max_tasks());
 }
 
@@ -701,7 +838,8 @@ int hjd_plan_launch(hjd_plan* plan, const void* d_coefs, void* d_out, void* stre
                                        plan->variant, d_coefs, plan->d_qt,
                                        reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
                                        plan->nframes, plan->tasks, d_out, stream, grid_blocks, plan->out_format,
-                                       plan->scale != 1 ? HJD_KERNEL_PERSISTENT : plan->kernel_mode, plan->scale);
+                                       plan->scale != 1 || plan->roi ? HJD_KERNEL_PERSISTENT : plan->kernel_mode,
+                                       plan->scale, plan->roi != 0);
 }
 
 // The fused kernel's launch adapted to the device it runs on (VERDICT r3:
@@ -726,11 +864,12 @@ namespace {
 struct TuneKey {
     int device, sampling, input_format, out_format, keep_variant, nframes;
     int64_t tasks;
-    int scale;
+    int scale, roi;
     bool operator<(const TuneKey& o) const
     {
-        return std::tie(device, sampling, input_format, out_format, keep_variant, nframes, tasks, scale) <
-               std::tie(o.device, o.sampling, o.input_format, o.out_format, o.keep_variant, o.nframes, o.tasks, o.scale);
+        return std::tie(device, sampling, input_format, out_format, keep_variant, nframes, tasks, scale, roi) <
+               std::tie(o.device, o.sampling, o.input_format, o.out_format, o.keep_variant, o.nframes, o.tasks, o.scale,
+                        o.roi);
     }
 };
 std::mutex g_tune_mu;
@@ -763,7 +902,7 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
     if (plan->tasks == 0 || !plan_is_persistent(plan)) return report();
     const int keep = plan->variant & ~1;
     const TuneKey key{plan->ctx->device, plan->sampling, plan->input_format, plan->out_format, keep, plan->nframes,
-                      plan->tasks, plan->scale};
+                      plan->tasks, plan->scale, plan->roi};
     if (tune_cache_enabled()) {
         std::lock_guard<std::mutex> lock(g_tune_mu);
         auto it = g_tune.find(key);
@@ -788,7 +927,7 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
         for (const Cand& c : cands) dup |= c.grid == g;
         if (dup) continue;
         // the store policy is a BGRX variant bit; scaled plans have no variants (chunks only)
-        for (int st = 0; st < (plan->out_format == HJD_OUT_BGRX && plan->scale == 1 ? 2 : 1); ++st)
+        for (int st = 0; st < (plan->out_format == HJD_OUT_BGRX && plan->scale == 1 && !plan->roi ? 2 : 1); ++st)
             cands.push_back({pw, st, g, 1e30f});
     }
     HJD_HIP(hipSetDevice(plan->ctx->device));
@@ -809,7 +948,7 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
                                                    plan->input_format, v, d_coefs, plan->d_qt,
                                                    reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
                                                    plan->nframes, plan->tasks, d_out, s, c.grid, plan->out_format,
-                                                   HJD_KERNEL_PERSISTENT, plan->scale);
+                                                   HJD_KERNEL_PERSISTENT, plan->scale, plan->roi != 0);
             };
             float ms = 0;
             if ((rc = go()) || (rc = hipEventRecord(e0, s) == hipSuccess ? HJD_OK : HJD_E_HIP) || (rc = go()) ||
@@ -879,6 +1018,7 @@ int hjd_debug_plan_launch_stages(hjd_plan* plan, int stages, const void* d_coefs
         return fail(HJD_E_INVALID, "unknown stage variant %d", stages);
     if (plan->scale != 1)
         return fail(HJD_E_INVALID, "stage variants are not built for scaled plans (scale %d)", plan->scale);
+    if (plan->roi) return fail(HJD_E_INVALID, "stage variants are not built for ROI plans");
     if (plan->input_format != HJD_IN_Q16_ZIGZAG || plan->out_format != HJD_OUT_BGRX ||
         (plan->sampling != HJD_YUV420 && plan->sampling != HJD_YUV444))
         return fail(HJD_E_INVALID, "stage variants: 4:2:0 / 4:4:4, int16 zigzag in, BGRX out");

@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import HjdJpegInfo, check
+from ._lib import HjdJpegInfo, HjdRect, check
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _i16p = ctypes.POINTER(ctypes.c_int16)
@@ -303,10 +303,12 @@ class GpuDecoder:
         check(self.lib.hjd_gdec_set_scale(self.handle, int(scale)), "hjd_gdec_set_scale")
         self.scale = int(scale)
 
-    def decode(self, datas: Sequence[bytes], outs, stream=None):
+    def decode(self, datas: Sequence[bytes], outs, stream=None, rois=None):
         """outs: contiguous device tensors, one row per image row: (H, W) int32
         (or (H, pitch/4)) for BGRX, (H, pitch) uint8 for BGR24, (H, W, 3)
-        uint8 for RGB24, (3, H, W) uint8 for planar RGB."""
+        uint8 for RGB24, (3, H, W) uint8 for planar RGB.  rois: one (x, y, w, h)
+        per image on the grid of the decoder's scale (hjd_gdec_decode_roi);
+        outs are then sized (h, w)."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         if len(outs) != n:
@@ -316,11 +318,19 @@ class GpuDecoder:
                 raise ValueError("outputs must be contiguous device tensors")
         ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
         pitches = (ctypes.c_int32 * n)(*[_out_pitch(o, self.out_format) for o in outs])
-        check(self.lib.hjd_gdec_decode(self.handle, arr_d, arr_s, n, ptrs, pitches, _stream_handle(stream)),
-              "hjd_gdec_decode")
+        if rois is None:
+            check(self.lib.hjd_gdec_decode(self.handle, arr_d, arr_s, n, ptrs, pitches, _stream_handle(stream)),
+                  "hjd_gdec_decode")
+        else:
+            if len(rois) != n:
+                raise ValueError("one ROI per JPEG")
+            rects = (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
+            check(self.lib.hjd_gdec_decode_roi(self.handle, arr_d, arr_s, n, rects, ptrs, pitches,
+                                               _stream_handle(stream)), "hjd_gdec_decode_roi")
         self._n = n
 
-    def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1):
+    def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1,
+                   rois=None):
         """Decode to uint8 RGB tensors: layout "chw" gives (3, H, W) per image
         (OUT_RGB_PLANAR), "hwc" gives (H, W, 3) (OUT_RGB24).  scale 2, 4 or 8
         decodes at 1/scale (H and W below are then scaled_size's; the
@@ -328,7 +338,10 @@ class GpuDecoder:
         one new device tensor per image is returned as a list.  With `out`, a
         contiguous uint8 device tensor (N, 3, H, W) ("chw") or (N, H, W, 3)
         ("hwc"), image i is decoded into out[i] and `out` is returned;
-        ValueError if an image's size differs from it.  Asynchronous like
+        ValueError if an image's size differs from it.  rois: one (x, y, w, h)
+        per image on the (scaled) grid; tensors are sized per ROI, and with
+        `out` every ROI's (h, w) must equal out's while the files' own sizes
+        may differ.  Asynchronous like
         decode(): call sync() before reading.  The decoder's output format is
         restored afterwards."""
         import torch
@@ -343,6 +356,10 @@ class GpuDecoder:
             check(self.lib.hjd_jpeg_parse(ctypes.cast(addr, _u8p), size, ctypes.byref(c)), "hjd_jpeg_parse")
             infos.append(JpegInfo.from_c(c))
         sizes = [scaled_size(i.width, i.height, scale) for i in infos]   # (W', H')
+        if rois is not None:
+            if len(rois) != len(infos):
+                raise ValueError("one ROI per JPEG")
+            sizes = [(int(r[2]), int(r[3])) for r in rois]
         if out is None:
             dev = torch.device("cuda", self.ctx.device)
             outs = [torch.empty((3, h, w) if chw else (h, w, 3), dtype=torch.uint8, device=dev) for w, h in sizes]
@@ -362,7 +379,7 @@ class GpuDecoder:
         self.set_scale(scale)
         self.set_output_format(OUT_RGB_PLANAR if chw else OUT_RGB24)
         try:
-            self.decode(datas, outs, stream)
+            self.decode(datas, outs, stream, rois=rois)
         finally:
             self.set_output_format(prev)
             self.set_scale(prev_scale)
