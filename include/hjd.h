@@ -75,7 +75,36 @@ enum hjd_out_format {
      * guarded byte-store path for every strip: correct, but slower.  (The
      * buffer passed to hjd_plan_launch stays 16-byte aligned for every
      * format; frames sit in it at any out_offset.) */
-    HJD_OUT_RGB_PLANAR = 3
+    HJD_OUT_RGB_PLANAR = 3,
+    /* Normalised float planes (extension): three planes R, G, B of IEEE half
+     * (F16, 2 bytes) or float (F32, 4 bytes) elements, laid out as
+     * HJD_OUT_RGB_PLANAR's with out_pitch the BYTES of one plane's row (>= 2*w
+     * or 4*w; plane c at out_offset + c * out_pitch * h, 64-bit).  Let u8 be
+     * the byte HJD_OUT_RGB_PLANAR writes for that channel and pixel (under the
+     * same scale and ROI) and a[c], b[c] the plan's six fp32 constants
+     * (hjd_plan_set_normalize; default a = 1, b = 0):
+     *     F32: out = fma((float)u8, a[c], b[c])   -- ONE correctly rounded fp32
+     *          operation, round-to-nearest-even; not a multiply, then an add;
+     *     F16: that fp32 value converted to half, round-to-nearest-even;
+     *          overflow gives +-inf, half subnormals are kept.  Both roundings
+     *          are part of the definition.
+     * (An fp32-subnormal result follows the kernels' default mode, which keeps
+     * fp32 subnormals.)  The integer pipeline is untouched: the converted
+     * bytes are the bit-exact ones of the byte formats.
+     *
+     * out_offset and out_pitch must be multiples of the element size
+     * (HJD_E_INVALID otherwise).  Frames whose out_offset and out_pitch (and
+     * output pointer) are multiples of 8 (F16) or 16 (F32) take full-width
+     * vector stores on interior strips (with a ROI: and dx % 4 == 0, as the
+     * other formats); any other frame takes the guarded element stores.
+     *
+     * HJD_IN_Q16_ZIGZAG input only; every sampling at scale 1 (persistent and
+     * latency kernel), 4:4:4 / 4:2:0 / gray scaled, ROIs as the other formats.
+     * Refused with HJD_E_INVALID: HJD_IN_I32_NATURAL, kernel variants, the
+     * stream pipelines (hjd_stream / hjd_gstream set_output_format) and the
+     * idct.h shim.  There is no interleaved (H, W, 3) float layout. */
+    HJD_OUT_RGB_PLANAR_F16 = 5,   /* 4 is not a format: it stays HJD_E_INVALID, as before these two */
+    HJD_OUT_RGB_PLANAR_F32 = 6
 };
 
 /* Kernel selection of a plan (hjd_plan_set_kernel).  Both kernels produce
@@ -110,7 +139,8 @@ typedef struct hjd_frame {
     int32_t width;        /* visible pixels (output is cropped to W x H) */
     int32_t height;
     int32_t out_pitch;    /* bytes per output row, >= 4*width (BGR24: 3*width), multiple of 4;
-                           * RGB24: >= 3*width, planar RGB: >= width, any value (see hjd_out_format) */
+                           * RGB24: >= 3*width, planar RGB: >= width, any value; float planar: >= 2*width
+                           * (F16) or 4*width (F32), multiple of the element size (see hjd_out_format) */
     int32_t sampling;     /* enum hjd_sampling (not HJD_OTHER) */
     int32_t qt_index[3];  /* per component (Y, Cb, Cr): index into the qtable set */
     int32_t out_format;   /* enum hjd_out_format (HJD_OUT_BGRX = 0); the same for all frames of a plan */
@@ -222,6 +252,18 @@ int hjd_roi_geometry(int width, int height, int sampling, int scale, const hjd_r
 int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                         const int32_t* qtables, int nq, int scale, const hjd_rect* rois, hjd_plan** out);
 int hjd_plan_has_roi(const hjd_plan* plan);        /* 1: created with rois */
+/* Validates one frame's geometry and output layout (format, out_pitch,
+ * out_offset, the input format it can take) exactly as hjd_plan_create_roi
+ * would for a plan of `scale` with `roi` (NULL: none).  Host only: needs no
+ * device. */
+int hjd_frame_check(const hjd_frame* frame, int input_format, int scale, const hjd_rect* roi);
+/* The constants of a HJD_OUT_RGB_PLANAR_F16 / _F32 plan, per channel R, G, B
+ * (see hjd_out_format): out = fma((float)u8, a[c], b[c]).  A new plan has
+ * a = 1, b = 0.  ToTensor is a = 1/255, b = 0; mean/std normalisation
+ * a = 1/(255 std), b = -mean/std.  Synchronous (waits for the device, then
+ * updates the plan's table); applies to the launches that follow.
+ * HJD_E_INVALID for non-finite constants and for a plan of a byte format. */
+int hjd_plan_set_normalize(hjd_plan* plan, const float a[3], const float b[3]);
 int hjd_plan_destroy(hjd_plan* plan);
 /* Tuning hook: kernel variant bits (0 = default).  bit 0: plain instead of
  * non-temporal output stores; bit 1: workgroup-interleaved task order.

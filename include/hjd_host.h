@@ -120,7 +120,9 @@ int hjd_debug_worker_cpus(const char* sysfs_root, const char* bus, const char* c
 /* Pixel format of subsequent submits: HJD_OUT_BGRX (default), HJD_OUT_BGR24
  * (d_out 4-byte aligned, pitch >= 3*width), HJD_OUT_RGB24 (any d_out, any
  * pitch >= 3*width) or HJD_OUT_RGB_PLANAR (any d_out, any pitch >= width; the
- * three planes at d_out + c * pitch * height); jobs already queued keep theirs. */
+ * three planes at d_out + c * pitch * height); jobs already queued keep theirs.
+ * The float formats (HJD_OUT_RGB_PLANAR_F16 / _F32) are not served by streams:
+ * HJD_E_INVALID. */
 int hjd_stream_set_output_format(hjd_stream* s, int out_format);
 
 /* ---- GPU entropy decoding ----------------------
@@ -172,8 +174,18 @@ int hjd_gdec_sync(hjd_gdec* g, int32_t* status);
  * >= 3*width) or HJD_OUT_RGB_PLANAR (any d_outs, any pitches >= width; image
  * i's planes at d_outs[i] + c * pitches[i] * height).  The two RGB formats
  * take vector stores where pointer and pitch are multiples of 4 and byte
- * stores otherwise (include/hjd.h). */
+ * stores otherwise (include/hjd.h).  HJD_OUT_RGB_PLANAR_F16 / _F32: planes of
+ * half / float elements normalised with the decoder's constants
+ * (hjd_gdec_set_normalize); d_outs and pitches multiples of the element size,
+ * pitches >= 2*width / 4*width bytes, vector stores where both are multiples
+ * of 8 / 16. */
 int hjd_gdec_set_output_format(hjd_gdec* g, int out_format);
+/* The constants a[c], b[c] (R, G, B) of the float formats for the following
+ * hjd_gdec_decode and hjd_gdec_decode_roi calls: out = fma((float)u8, a[c],
+ * b[c]) (include/hjd.h, hjd_out_format).  Default a = 1, b = 0; they are kept
+ * across format changes and ignored by the byte formats.  An issued call
+ * keeps its constants.  HJD_E_INVALID for non-finite values. */
+int hjd_gdec_set_normalize(hjd_gdec* g, const float a[3], const float b[3]);
 /* Decode scale of the following hjd_gdec_decode calls: 1 (default), 2, 4 or 8
  * (the scaled decode of include/hjd.h, hjd_plan_create_scaled).  Image i comes
  * out ceil(width/scale) x ceil(height/scale); pitches[] and the planar plane
@@ -226,7 +238,8 @@ int hjd_gstream_sync(hjd_gstream* s, int64_t stats[5]);
  * HJD_OUT_RGB_PLANAR; with the 3-byte formats the D2H sink moves 3 bytes per
  * pixel (planar: 3 * height rows of width bytes, the planes out_pitch *
  * height apart in h_out).  Only between hjd_gstream_sync and the next submit
- * (HJD_E_STATE otherwise). */
+ * (HJD_E_STATE otherwise).  The float formats are not served by streams:
+ * HJD_E_INVALID. */
 int hjd_gstream_set_output_format(hjd_gstream* s, int out_format);
 /* Scan bytes the host CPU has read + written so far (destuffing into pinned
  * staging: 2 per scan byte; a frame whose bytes are pinned host memory is

@@ -22,6 +22,8 @@ from .backend import (  # noqa: E402
     OUT_BYTES,
     OUT_RGB24,
     OUT_RGB_PLANAR,
+    OUT_RGB_PLANAR_F16,
+    OUT_RGB_PLANAR_F32,
     GRAY,
     YUV411_H4V1,
     YUV420,
@@ -40,7 +42,9 @@ from .backend import (  # noqa: E402
     device_count,
     device_worker_cpus,
     frame_blocks,
+    frame_check,
     mcu_geometry,
+    norm_constants,
     roi_geometry,
     scaled_size,
     stream_worker_threads,
@@ -56,6 +60,7 @@ __all__ = [
     "decode_coefs_batch", "decode_coefs_into", "decode_jpeg", "emulate_entropy",
     "parse", "pinned_bytes",
     "Context", "FrameSpec", "Plan", "autotune_cache_clear", "decode_frame", "device_count", "frame_blocks", "mcu_geometry", "worker_cpus", "cpu_share", "debug_tuning",
-    "device_worker_cpus", "stream_worker_threads", "scaled_size", "roi_geometry",
+    "device_worker_cpus", "stream_worker_threads", "scaled_size", "roi_geometry", "norm_constants", "frame_check",
+    "OUT_RGB_PLANAR_F16", "OUT_RGB_PLANAR_F32",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

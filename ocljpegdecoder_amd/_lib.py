@@ -104,6 +104,9 @@ SIGNATURES = {
                                            c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(HjdRect),
                                            ctypes.POINTER(ctypes.c_void_p)]),
     "hjd_plan_has_roi": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_frame_check": (ctypes.c_int, [ctypes.POINTER(HjdFrame), ctypes.c_int, ctypes.c_int, ctypes.POINTER(HjdRect)]),
+    "hjd_plan_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float)]),
     "hjd_plan_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_plan_set_variant": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "hjd_plan_set_kernel": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -203,6 +206,7 @@ def _bind_host(lib):
         "hjd_gdec_sync": (ctypes.c_int, [vp, c_i32p]),
         "hjd_gdec_set_output_format": (ctypes.c_int, [vp, ctypes.c_int]),
         "hjd_gdec_set_scale": (ctypes.c_int, [vp, ctypes.c_int]),
+        "hjd_gdec_set_normalize": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
         "hjd_gdec_decode_roi": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int,
                                                ctypes.POINTER(HjdRect), ctypes.POINTER(vp), c_i32p, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),

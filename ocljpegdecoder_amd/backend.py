@@ -36,22 +36,61 @@ OUT_BGRX = 0    # 4 B/px: B, G, R, 0 (the reference's RGB32 / 32-bpp BMP rows)
 OUT_BGR24 = 1   # 3 B/px: B, G, R (extension: 24-bpp BMP rows)
 OUT_RGB24 = 2   # 3 B/px: R, G, B interleaved (extension: an (H, W, 3) uint8 array)
 OUT_RGB_PLANAR = 3   # three uint8 planes R, G, B at pitch * height (extension: a (3, H, W) uint8 array)
-OUT_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3, OUT_RGB24: 3, OUT_RGB_PLANAR: 3}   # bytes per pixel overall
-_ROW_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3, OUT_RGB24: 3, OUT_RGB_PLANAR: 1}  # bytes per pixel within a row
+# extensions: three planes R, G, B of normalised half / float elements, out = fma(float(u8), a[c], b[c])
+OUT_RGB_PLANAR_F16 = 5   # a (3, H, W) float16 array (4 is not a format)
+OUT_RGB_PLANAR_F32 = 6   # a (3, H, W) float32 array
+OUT_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3, OUT_RGB24: 3, OUT_RGB_PLANAR: 3,
+             OUT_RGB_PLANAR_F16: 6, OUT_RGB_PLANAR_F32: 12}   # bytes per pixel overall
+_ROW_BYTES = {OUT_BGRX: 4, OUT_BGR24: 3, OUT_RGB24: 3, OUT_RGB_PLANAR: 1,
+              OUT_RGB_PLANAR_F16: 2, OUT_RGB_PLANAR_F32: 4}   # bytes per pixel within a row
+_PLANAR = (OUT_RGB_PLANAR, OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32)
 
 
 def default_pitch(width: int, out_format: int = OUT_BGRX) -> int:
     """Tightest legal row pitch: bytes of one row rounded up to 4 (BGRX,
     BGR24); the RGB formats take any pitch, so theirs is the contiguous one
-    (3*width, planar: width)."""
-    if out_format in (OUT_RGB24, OUT_RGB_PLANAR):
+    (3*width, planar: width; float planar: 2*width or 4*width)."""
+    if out_format in (OUT_RGB24,) + _PLANAR:
         return _ROW_BYTES[out_format] * width
     return (OUT_BYTES[out_format] * width + 3) & ~3
 
 
 def out_rows(height: int, out_format: int) -> int:
     """Rows of `pitch` bytes a frame occupies (planar: three planes)."""
-    return 3 * height if out_format == OUT_RGB_PLANAR else height
+    return 3 * height if out_format in _PLANAR else height
+
+
+def norm_constants(mean=None, std=None):
+    """(a, b): the float formats' constants as two float32 triples (R, G, B),
+    out = fma(float(u8), a, b).  Without arguments a = fp32(1/255), b = 0
+    (ToTensor); with mean and std (scalars or triples, on the [0, 1] scale)
+    a_c = fp32(1 / (255 std_c)), b_c = fp32(-mean_c / std_c), each computed in
+    float64 and rounded once."""
+    m = np.broadcast_to(np.asarray(0.0 if mean is None else mean, dtype=np.float64), (3,))
+    s = np.broadcast_to(np.asarray(1.0 if std is None else std, dtype=np.float64), (3,))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        a = (1.0 / (255.0 * s)).astype(np.float32)
+        b = (-m / s).astype(np.float32) + np.float32(0)   # no -0 from mean = 0
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError(f"normalisation constants are not finite: mean={mean}, std={std}")
+    return a, b
+
+
+def _norm_arrays(normalize):
+    """normalize = (a, b) as two ctypes float[3] arrays (scalars broadcast)."""
+    a, b = normalize
+    a = np.broadcast_to(np.asarray(a, dtype=np.float32), (3,))
+    b = np.broadcast_to(np.asarray(b, dtype=np.float32), (3,))
+    return (ctypes.c_float * 3)(*a.tolist()), (ctypes.c_float * 3)(*b.tolist())
+
+
+def frame_check(spec, input_format: int = 0, scale: int = 1):
+    """hjd_frame_check: raise HjdError unless a plan of `scale` would take this
+    FrameSpec's geometry and output layout.  Host only."""
+    c = spec.to_c(scale)
+    r = HjdRect(*[int(v) for v in spec.roi]) if spec.roi is not None else None
+    check(_lib.load().hjd_frame_check(ctypes.byref(c), int(input_format), int(scale),
+                                      ctypes.byref(r) if r is not None else None), "hjd_frame_check")
 
 
 def mcu_geometry(width: int, height: int, sampling: int):
@@ -224,8 +263,10 @@ class Plan:
     """A validated batch of frames with its device-side frame table (hjd_plan)."""
 
     def __init__(self, ctx: Context, frames: Sequence[FrameSpec], input_format: int = IN_Q16_ZIGZAG,
-                 qtables: Optional[np.ndarray] = None, scale: int = 1):
-        """scale 2, 4 or 8: a scaled plan (hjd_plan_create_scaled).  Frames
+                 qtables: Optional[np.ndarray] = None, scale: int = 1, normalize=None):
+        """normalize = (a, b): the constants of a float-format plan
+        (set_normalize; norm_constants() makes them).
+        scale 2, 4 or 8: a scaled plan (hjd_plan_create_scaled).  Frames
         carry the source size; every frame comes out scaled_size(W, H, scale)
         and out_pitch (0: default_pitch of the scaled width) refers to that.
         A plan is a ROI plan (hjd_plan_create_roi) when any frame has a roi;
@@ -270,6 +311,15 @@ class Plan:
             sw, sh = f.out_size(scale)
             self.out_bytes_needed = max(self.out_bytes_needed, f.out_offset + (out_rows(sh, f.out_format) - 1) *
                                         c.out_pitch + _ROW_BYTES[f.out_format] * sw)
+        if normalize is not None:
+            self.set_normalize(*normalize)
+
+    def set_normalize(self, a, b):
+        """hjd_plan_set_normalize: the constants (R, G, B triples, or scalars)
+        of an OUT_RGB_PLANAR_F16 / _F32 plan for the launches that follow:
+        out = fma(float(u8), a, b); a new plan has a = 1, b = 0."""
+        ca, cb = _norm_arrays((a, b))
+        check(self.lib.hjd_plan_set_normalize(self.handle, ca, cb), "hjd_plan_set_normalize")
 
     def _check_tensor(self, t, what, elem_bytes, nbytes_needed):
         if isinstance(t, int):
@@ -417,15 +467,27 @@ def debug_tuning(name: str, value):
 
 
 def decode_frame(ctx: Context, coefs, qt: np.ndarray, width: int, height: int, sampling: int,
-                 input_format: int = IN_Q16_ZIGZAG, stream=None, scale: int = 1, roi=None):
+                 input_format: int = IN_Q16_ZIGZAG, stream=None, scale: int = 1, roi=None,
+                 out_format: int = OUT_BGRX, normalize=None):
     """Decode one frame already resident on the device; returns an int32 (H, W)
     device tensor holding BGRX words (0x00RRGGBB); scale 2, 4 or 8: (H', W') =
     scaled_size(width, height, scale), reversed; roi (x, y, w, h) on that
-    grid: an (h, w) tensor."""
+    grid: an (h, w) tensor.  out_format OUT_RGB_PLANAR_F16 / _F32: a (3, H, W)
+    float16 / float32 tensor normalised with normalize = (a, b)
+    (norm_constants(); None: a = 1, b = 0)."""
     import torch
-    spec = FrameSpec(width, height, sampling, qt_index=(0, 1, 2), roi=roi)
-    plan = Plan(ctx, [spec], input_format, qtables=qt if input_format == IN_Q16_ZIGZAG else None, scale=scale)
+    if out_format not in (OUT_BGRX, OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32):
+        raise ValueError("decode_frame gives BGRX words or float planes")
+    if normalize is not None and out_format == OUT_BGRX:
+        raise ValueError("normalize needs out_format OUT_RGB_PLANAR_F16 or OUT_RGB_PLANAR_F32")
+    spec = FrameSpec(width, height, sampling, qt_index=(0, 1, 2), roi=roi, out_format=out_format)
+    plan = Plan(ctx, [spec], input_format, qtables=qt if input_format == IN_Q16_ZIGZAG else None, scale=scale,
+                normalize=normalize)
     width, height = spec.out_size(scale)
-    out = torch.empty((height, width), dtype=torch.int32, device=coefs.device)
+    if out_format == OUT_BGRX:
+        out = torch.empty((height, width), dtype=torch.int32, device=coefs.device)
+    else:
+        out = torch.empty((3, height, width), device=coefs.device,
+                          dtype=torch.float16 if out_format == OUT_RGB_PLANAR_F16 else torch.float32)
     plan.launch(coefs, out, stream)
     return out, plan

@@ -434,8 +434,9 @@ Caps make_caps(int max_frames, int64_t max_scan_bytes, int64_t max_blocks, int s
     c.max_tiles = max_scan_bytes / kTileBytes + max_frames;
     const size_t per_frame = (sizeof(EntFrame) + sizeof(HuffLut) * kMaxTables + 8) * kMaxScans + sizeof(FrameRecord) +
                              sizeof(hjd_internal::RoiRecord) + 192 * 4 + sizeof(RawFrame) + 4;
+    // + one NormRecord per pixel-kernel sampling class (float output formats)
     c.hdr_cap = align_up(per_frame * max_frames + 4 * static_cast<size_t>(c.max_segs + c.max_wgs + c.max_tiles) +
-                             10 * kAlign, kAlign);
+                             6 * sizeof(hjd_internal::NormRecord) + 10 * kAlign, kAlign);
     c.data = c.hdr_cap;
     return c;
 }
@@ -2428,6 +2429,19 @@ struct hjd_gdec {
     const hjd_rect* rois = nullptr;
     bool roi_batch = false;
     static constexpr size_t kRoiSlot = sizeof(FrameRecord) + sizeof(hjd_internal::RoiRecord);
+    // Float output formats (hjd_gdec_set_normalize): the constants; every
+    // class's block is then followed by a NormRecord, so class k's block
+    // starts k records further (norm_batch: the issued batch was laid out
+    // that way).
+    hjd_internal::NormRecord norm = hjd_internal::norm_identity();
+    bool norm_batch = false;
+    static_assert(kClasses == 6, "hdr_cap reserves six NormRecords");
+    // Byte offset, from the start of the record area, of class k's block, r0 records before it.
+    size_t class_block(int k, int r0) const
+    {
+        return (roi_batch ? kRoiSlot : sizeof(FrameRecord)) * static_cast<size_t>(r0) +
+               (norm_batch ? sizeof(hjd_internal::NormRecord) * static_cast<size_t>(k) : 0);
+    }
 };
 
 int hjd_gdec::wait_staging()
@@ -2594,7 +2608,9 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
     o.seg = align_up(o.tabs + sizeof(HuffLut) * ntab, kAlign);
     o.wg = align_up(o.seg + 4 * nseg, kAlign);
     o.recs = align_up(o.wg + 4 * nwg, kAlign);
-    o.qt = align_up(o.recs + (d_outs ? (rois ? kRoiSlot : sizeof(FrameRecord)) * n : 0), kAlign);
+    const bool fnorm = d_outs && hjd_internal::out_format_float_bytes(out_format) != 0;
+    o.qt = align_up(o.recs + (d_outs ? (rois ? kRoiSlot : sizeof(FrameRecord)) * n : 0) +
+                        (fnorm ? kClasses * sizeof(hjd_internal::NormRecord) : 0), kAlign);
     size_t ntiles = 0;
     for (const Prepared& p : frames)
         if (p.destuff != kDestuffHost)
@@ -2658,12 +2674,12 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
         out_base[k] = nullptr;
     }
     roi_batch = d_outs && rois;
+    norm_batch = fnorm;
     if (d_outs) {   // pixel-kernel records grouped by sampling class (one launch each)
-        FrameRecord* recs = reinterpret_cast<FrameRecord*>(h_stage + o.recs);
         int32_t* qtn = reinterpret_cast<int32_t*>(h_stage + o.qt);
         const int obytes = hjd_internal::out_format_row_bytes(out_format);
         const uintptr_t amask = hjd_internal::out_format_align_mask(out_format);
-        const int pmask = hjd_internal::out_format_any_alignment(out_format) ? 0 : 3;
+        const int pmask = hjd_internal::out_format_pitch_mask(out_format);
         for (int i = 0; i < n; ++i) {
             const Prepared& p = frames[i];
             const int out_w = rois ? rois[i].w : hjd_internal::scaled_dim(p.width, scale);
@@ -2673,6 +2689,7 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
                 return set_error(HJD_E_INVALID,
                                  "frame %d: bad output buffer or pitch (BGRX: 16-byte aligned, >= 4*width; "
                                  "BGR24: 4-byte aligned, >= 3*width; RGB24: >= 3*width; planar RGB: >= width; "
+                                 "float planar: element-aligned, >= 2*width (F16) or 4*width (F32); "
                                  "width = the scaled width, or the ROI's)", i);
             ++nrec[sampling_class(p.sampling)];
         }
@@ -2694,16 +2711,16 @@ int hjd_gdec::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, vo
             if (t < 0) return static_cast<int>(t);
             rec.task_begin = tasks[sidx];
             tasks[sidx] += t;
-            if (rois) {   // class k's block: nrec[k] records, then nrec[k] side records
-                const int k0 = r[sidx] - written[sidx];   // records of the classes before this one
-                uint8_t* blockp = h_stage + o.recs + kRoiSlot * static_cast<size_t>(k0);
-                reinterpret_cast<FrameRecord*>(blockp)[written[sidx]] = rec;
+            // class k's block: nrec[k] records, then (ROI) nrec[k] side records, then (float) the NormRecord
+            const int k0 = r[sidx] - written[sidx];   // records of the classes before this one
+            uint8_t* blockp = h_stage + o.recs + class_block(sidx, k0);
+            reinterpret_cast<FrameRecord*>(blockp)[written[sidx]] = rec;
+            if (rois)
                 reinterpret_cast<hjd_internal::RoiRecord*>(blockp + sizeof(FrameRecord) * nrec[sidx])[written[sidx]] = side;
-                ++written[sidx];
-                ++r[sidx];
-            } else {
-                recs[r[sidx]++] = rec;
-            }
+            if (fnorm)
+                memcpy(blockp + (rois ? kRoiSlot : sizeof(FrameRecord)) * nrec[sidx], &norm, sizeof(norm));
+            ++written[sidx];
+            ++r[sidx];
             for (int c = 0; c < 3; ++c)
                 for (int k = 0; k < 64; ++k) qtn[(3 * i + c) * 64 + kZigzag[k]] = p.qt[c][k];
         }
@@ -3116,8 +3133,7 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
             rc = hjd_internal::launch_decode(
                 g->device, g->num_cu, hjd_gdec::kClassSampling[sidx], HJD_IN_Q16_ZIGZAG, 0, coefs,
                 reinterpret_cast<const int32_t*>(g->d_blob + g->H.qt),
-                reinterpret_cast<const FrameRecord*>(
-                    g->d_blob + g->H.recs + (g->roi_batch ? hjd_gdec::kRoiSlot : sizeof(FrameRecord)) * r0),
+                reinterpret_cast<const FrameRecord*>(g->d_blob + g->H.recs + g->class_block(sidx, r0)),
                 g->nrec[sidx], g->tasks[sidx], g->out_base[sidx], s, 0, g->out_format,
                 g->roi_batch ? HJD_KERNEL_PERSISTENT : HJD_KERNEL_AUTO, g->scale, g->roi_batch);
             if (rc) return rc;
@@ -3347,6 +3363,18 @@ int hjd_gdec_set_output_format(hjd_gdec* g, int out_format)
     if (!g) return set_error(HJD_E_INVALID, "gdec is NULL");
     if (!hjd_internal::out_format_bytes(out_format)) return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
     g->out_format = out_format;   // applies to the next decode; an issued one keeps its format
+    return HJD_OK;
+}
+
+int hjd_gdec_set_normalize(hjd_gdec* g, const float a[3], const float b[3])
+{
+    const int rc = hjd_internal::norm_check(a, b);
+    if (rc) return rc;
+    if (!g) return set_error(HJD_E_INVALID, "gdec is NULL");
+    for (int c = 0; c < 3; ++c) {   // staged with the next call's records; an issued one keeps its own
+        g->norm.a[c] = a[c];
+        g->norm.b[c] = b[c];
+    }
     return HJD_OK;
 }
 
@@ -4002,6 +4030,9 @@ int hjd_gstream_set_output_format(hjd_gstream* st, int out_format)
 {
     if (!st) return set_error(HJD_E_INVALID, "gstream is NULL");
     if (!hjd_internal::out_format_bytes(out_format)) return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
+    if (hjd_internal::out_format_float_bytes(out_format))
+        return set_error(HJD_E_INVALID, "hjd_gstream does not serve the float output formats (format %d): use hjd_gdec "
+                                        "or a plan", out_format);
     std::lock_guard<std::mutex> api(st->api_mu);
     std::lock_guard<std::mutex> lk(st->mu);
     if (st->open || st->batches_in_flight)

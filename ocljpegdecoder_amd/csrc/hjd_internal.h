@@ -87,42 +87,74 @@ inline bool scaled_sampling_ok(int sampling) { return sampling == 0 || sampling 
 int launch_decode(int device, int num_cu, int sampling, int input_format, int variant, const void* d_coefs,
                   const int32_t* d_qt_nat, const FrameRecord* d_frames, int nframes, int64_t tasks, void* d_out,
                   void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0, int scale = 1,
-                  bool roi = false);   // roi: the RoiRecord table follows d_frames[nframes - 1]
+                  bool roi = false);   // roi: the RoiRecord table follows d_frames[nframes - 1]; a float
+                                       // out_format: the NormRecord follows that (or the frame records)
+
+// HJD_OUT_RGB_PLANAR_F16 (5) / _F32 (6): element bytes of a float planar format (else 0; 4 is no format).
+inline int out_format_float_bytes(int out_format) { return out_format == 5 ? 2 : out_format == 6 ? 4 : 0; }
 
 // Bytes per output pixel of an HJD_OUT_* format overall (0 if unknown).
 inline int out_format_bytes(int out_format)
 {
-    return out_format == 0 ? 4 : out_format >= 1 && out_format <= 3 ? 3 : 0;
+    return out_format == 0 ? 4 : out_format >= 1 && out_format <= 3 ? 3 : 3 * out_format_float_bytes(out_format);
 }
 
+// Three planes R, G, B at out_pitch * height (uint8 or float elements).
+inline bool out_format_planar(int out_format) { return out_format == 3 || out_format_float_bytes(out_format) != 0; }
+
 // Bytes per pixel within one output row: planar rows hold one component.
-inline int out_format_row_bytes(int out_format) { return out_format == 3 ? 1 : out_format_bytes(out_format); }
+inline int out_format_row_bytes(int out_format)
+{
+    return out_format == 3 ? 1 : out_format_float_bytes(out_format) ? out_format_float_bytes(out_format)
+                                                                   : out_format_bytes(out_format);
+}
 
 // Rows of `out_pitch` bytes a frame of `height` pixel rows occupies (planar:
 // the three planes follow each other at out_pitch * height).
 inline int64_t out_format_rows(int out_format, int height)
 {
-    return out_format == 3 ? 3 * static_cast<int64_t>(height) : height;
+    return out_format_planar(out_format) ? 3 * static_cast<int64_t>(height) : height;
 }
 
 // HJD_OUT_RGB24 / HJD_OUT_RGB_PLANAR: any pitch, offset and pointer are legal
-// (the others need 4-byte pitches and 4- or 16-byte aligned rows).
+// (the others need 4-byte pitches and 4- or 16-byte aligned rows; the float
+// planar formats multiples of their element size: out_format_pitch_mask).
 inline bool out_format_any_alignment(int out_format) { return out_format == 2 || out_format == 3; }
+
+// Mask a pitch and an offset of this format must be clear of.
+inline int out_format_pitch_mask(int out_format)
+{
+    return out_format_float_bytes(out_format) ? out_format_float_bytes(out_format) - 1
+                                              : out_format_any_alignment(out_format) ? 0 : 3;
+}
 
 // Required alignment mask of an output pointer / offset of this format.
 inline uintptr_t out_format_align_mask(int out_format)
 {
-    return out_format == 0 ? 15 : out_format == 1 ? 3 : 0;
+    return out_format == 0 ? 15 : out_format == 1 ? 3 : out_format_float_bytes(out_format) ? out_format_float_bytes(out_format) - 1 : 0;
 }
 
-// Rows of this format can take the kernel's full-width vector stores.
+// Rows of this format can take the kernel's full-width vector stores (BGRX
+// and F32 planar: 16-byte aligned rows, F16 planar: 8, the others: 4).
 // out_base: the frame's offset; base_bits: low bits of the address out_base
 // is relative to, where that address is not known to be 16-byte aligned.
 inline bool out_vector_ok(int out_format, int64_t pitch, int64_t out_base, uintptr_t base_bits = 0)
 {
     const int64_t bits = pitch | out_base | static_cast<int64_t>(base_bits & 15);
-    return out_format == 0 ? (bits & 15) == 0 : (bits & 3) == 0;
+    return out_format == 0 || out_format == 6 ? (bits & 15) == 0 : out_format == 5 ? (bits & 7) == 0 : (bits & 3) == 0;
 }
+
+// The constants of the float formats as the kernels read them (layout of
+// hjd::NormDev): the record follows the frame table (and a ROI plan's
+// RoiRecord table).
+struct NormRecord {
+    float a[3], b[3];
+    float reserved[2];
+};
+// a = 1, b = 0: the C default (out = (float)u8).
+inline NormRecord norm_identity() { return NormRecord{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}}; }
+// HJD_OK, or HJD_E_INVALID (NULL or non-finite constants) with the cause in the error string.
+int norm_check(const float* a, const float* b);
 
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe

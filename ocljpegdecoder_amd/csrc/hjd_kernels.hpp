@@ -231,6 +231,13 @@ constexpr int kVarScale = 3 << kScaleShift;
 // bounds dx, dy of the re-anchored frame (RoiDev); int16 zigzag input, output
 // format and scale bits only.
 constexpr int kVarRoi = 1 << 13;
+// Normalised float output (HJD_OUT_RGB_PLANAR_F16 / _F32):
+// only with kOutPlanar and int16 zigzag input.  The planes hold 2- or 4-byte
+// elements out = fma((float)u8, a[c], b[c]) (F16: then rounded to half,
+// nearest-even); a, b come from the NormDev record behind the frame table.
+constexpr int kOutF16 = 1 << 14;
+constexpr int kOutF32 = 1 << 15;
+constexpr int kOutFloat = kOutF16 | kOutF32;
 // Column x / row y of the (re-anchored) frame is stored: below width /
 // height, and in a ROI kernel not below d (one unsigned compare does both).
 template <int kVariant>
@@ -254,7 +261,102 @@ template <int kVariant>
 constexpr int kScaleLog = (kVariant & kVarScale) >> kScaleShift;
 // Bytes per pixel within one output row (planar: of one plane's row).
 template <int kVariant>
-constexpr int kOutBytes = (kVariant & kOutPlanar) != 0 ? 1 : (kVariant & (kOutBgr24 | kOutRgb24)) != 0 ? 3 : 4;
+constexpr int kOutBytes = (kVariant & kOutF32) != 0 ? 4 : (kVariant & kOutF16) != 0 ? 2 : (kVariant & kOutPlanar) != 0 ? 1
+                          : (kVariant & (kOutBgr24 | kOutRgb24)) != 0 ? 3 : 4;
+
+// The plan-level constants of the float formats, per channel R, G, B: the
+// 32-byte record that follows the frame table (and the RoiDev table of a ROI
+// plan).  Only the float instantiations read it.
+struct NormDev {
+    float a[3], b[3];
+    float reserved[2];   // 0
+};
+static_assert(sizeof(NormDev) == 32, "NormDev layout");
+
+// Once per wave, with scalar loads.  A gfx9 VALU op reads at most one SGPR
+// and each fma takes a[c] from one, so b has to be in a VGPR: kPinB keeps it
+// there for the whole kernel (F16), else the compiler copies it where a store
+// needs it (F32, whose four-dword values per plane leave no VGPRs to spare:
+// pinned, the 4:2:0 ROI kernel spilled one).
+template <bool kRoi, bool kPinB>
+__device__ __forceinline__ NormDev norm_load(const FrameDev* __restrict__ fr, int nframes)
+{
+    const char* p = reinterpret_cast<const char*>(fr + nframes);
+    if constexpr (kRoi) p += static_cast<size_t>(nframes) * sizeof(RoiDev);
+    NormDev n = *reinterpret_cast<const NormDev*>(p);
+    if constexpr (kPinB) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) asm("" : "+v"(n.b[c]));
+    }
+    return n;
+}
+
+// Channel c (0 R, 1 G, 2 B) of BGRX word p as the normalised fp32 value: the
+// byte is converted in place (v_cvt_f32_ubyte2/1/0), then one fused
+// multiply-add, correctly rounded (never a multiply followed by an add).
+template <int kC>
+__device__ __forceinline__ float norm_px(uint32_t p, const NormDev& nk)
+{
+    return __builtin_fmaf(static_cast<float>((p >> (16 - 8 * kC)) & 0xffu), nk.a[kC], nk.b[kC]);
+}
+// fp32 -> IEEE half in the low 16 bits, rounded to nearest-even under the
+// kernels' default mode (overflow to inf, subnormals kept).  The instruction
+// is spelled out so that the fp32 value -- the definition's first rounding --
+// exists: left to the compiler, the convert folds into v_fma_mixlo_f16 or
+// pairs up as gfx950's v_cvt_pk_f16_f32, and the latter's results differed
+// from fp32-then-half rounding on MI355X where the fp32 value is a half tie
+// (tests/test_gpu_norm_outputs.py test_half_is_rounded_twice).
+__device__ __forceinline__ uint32_t half_bits(float f)
+{
+    uint32_t w;
+    asm("v_cvt_f16_f32_e32 %0, %1" : "=v"(w) : "v"(f));
+    return w;
+}
+// Two fp32 values as two halves in one dword (low half first): the second
+// convert writes the high half in place (SDWA), so no pack instruction.
+__device__ __forceinline__ uint32_t pack_half2(float lo, float hi)
+{
+    uint32_t w = half_bits(lo);
+    asm("v_cvt_f16_f32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(w) : "v"(hi));
+    return w;
+}
+
+// store4 of the float formats, one channel: kFull, the lane's four pixels as
+// one dwordx2 (F16: rows 8-byte aligned) or dwordx4 (F32: 16-byte) to the
+// channel's plane row; else guarded element stores.
+template <bool kFull, int kVariant, int kC, typename GB>
+__device__ __forceinline__ void store4_norm(GB* grow, uint32_t loff, int x, int width, int dx, const uint32_t (&px)[4],
+                                            const NormDev& nk)
+{
+    const float f[4] = {norm_px<kC>(px[0], nk), norm_px<kC>(px[1], nk), norm_px<kC>(px[2], nk), norm_px<kC>(px[3], nk)};
+    if constexpr ((kVariant & kOutF16) != 0) {
+        if constexpr (kFull) {
+            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+            typedef __attribute__((address_space(1))) u32x2 gvec2;
+            const u32x2 v = {pack_half2(f[0], f[1]), pack_half2(f[2], f[3])};
+            __builtin_nontemporal_store(v, (gvec2*)(grow + loff));
+        } else {
+            typedef __attribute__((address_space(1))) uint16_t ghalf;
+            ghalf* d = (ghalf*)(grow + loff);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (in_bounds<kVariant>(x + k, width, dx)) d[k] = static_cast<uint16_t>(half_bits(f[k]));
+        }
+    } else {
+        if constexpr (kFull) {
+            typedef float f32x4 __attribute__((ext_vector_type(4)));
+            typedef __attribute__((address_space(1))) f32x4 gvec4;
+            const f32x4 v = {f[0], f[1], f[2], f[3]};
+            __builtin_nontemporal_store(v, (gvec4*)(grow + loff));
+        } else {
+            typedef __attribute__((address_space(1))) float gfloat;
+            gfloat* d = (gfloat*)(grow + loff);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (in_bounds<kVariant>(x + k, width, dx)) d[k] = f[k];
+        }
+    }
+}
 
 // 4 horizontally adjacent pixels (BGRX words p0..p3) at row + loff.  `row` is wave-uniform
 // (SGPRs) and loff a 32-bit per-lane byte offset, so the store uses the
@@ -270,9 +372,11 @@ constexpr int kOutBytes = (kVariant & kOutPlanar) != 0 ? 1 : (kVariant & (kOutBg
 // the three plane rows row + c * plane (each base wave-uniform, in SGPRs); or
 // guarded bytes.  kFull of the RGB formats needs 4-byte aligned rows (and
 // planes) only; their edge path stores bytes and takes any alignment.
+// Float planar (kOutF16 / kOutF32): store4_norm per plane, constants nk.
 template <bool kFull, int kVariant = 0>
 __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff, int x, int width, uint32_t p0,
-                                       uint32_t p1, uint32_t p2, uint32_t p3, int64_t plane = 0, int dx = 0)
+                                       uint32_t p1, uint32_t p2, uint32_t p3, int64_t plane = 0, int dx = 0,
+                                       const NormDev& nk = NormDev{})
 {
     // Pin the row base in SGPRs as a global (addrspace 1) pointer and the lane
     // offset as a 32-bit VGPR in this block: otherwise LLVM hoists
@@ -294,7 +398,12 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ row, uint32_t loff,
         gbyte* grow_b = grow_g + plane;
         asm("" : "+s"(grow_g));
         asm("" : "+s"(grow_b));
-        if constexpr (kFull) {
+        if constexpr ((kVariant & kOutFloat) != 0) {
+            const uint32_t px[4] = {p0, p1, p2, p3};
+            store4_norm<kFull, kVariant, 0>(grow, loff, x, width, dx, px, nk);
+            store4_norm<kFull, kVariant, 1>(grow_g, loff, x, width, dx, px, nk);
+            store4_norm<kFull, kVariant, 2>(grow_b, loff, x, width, dx, px, nk);
+        } else if constexpr (kFull) {
             const uint32_t bg01 = perm(p1, p0, 0x05010400u);   // b0 b1 g0 g1
             const uint32_t bg23 = perm(p3, p2, 0x05010400u);   // b2 b3 g2 g3
             const uint32_t r01 = perm(p1, p0, 0x0c0c0602u);    // r0 r1 0 0
@@ -383,12 +492,13 @@ template <bool kCheck, int kVariant, bool kFull>
 __device__ __forceinline__ void emit_row4(uint8_t* __restrict__ row, uint32_t loff, int xa, int width, uint32_t y01,
                                           uint32_t y23, const ChromaPair& p01, const ChromaPair& p23,
                                           const ChromaTerms* c0, const ChromaTerms* c1, const ChromaTerms* c2,
-                                          const ChromaTerms* c3, int64_t plane, int dx = 0)
+                                          const ChromaTerms* c3, int64_t plane, int dx = 0,
+                                          const NormDev& nk = NormDev{})
 {
     uint32_t q0, q1, q2, q3;
     pixels2<kCheck>(y01, p01, c0, c1, q0, q1);
     pixels2<kCheck>(y23, p23, c2, c3, q2, q3);
-    store4<kFull, kVariant>(row, loff, xa, width, q0, q1, q2, q3, plane, dx);
+    store4<kFull, kVariant>(row, loff, xa, width, q0, q1, q2, q3, plane, dx, nk);
 }
 
 // kStride / u0: this wave converts colour units u0, u0 + kStride, ... of the
@@ -397,7 +507,7 @@ __device__ __forceinline__ void emit_row4(uint8_t* __restrict__ row, uint32_t lo
 template <int kSampling, bool kFull, int kVariant, int kStride = 1>
 __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int lane, uint8_t* __restrict__ out,
                                              int pitch, int width, int height, int y_base, int x_base, int u0 = 0,
-                                             int dx = 0, int dy = 0)
+                                             int dx = 0, int dy = 0, const NormDev& nk = NormDev{})
 {
     const int cg = lane & 31;     // 4-pixel column group within the 128-px strip
     const int x0 = cg * 4;
@@ -435,16 +545,16 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int ya0 = y_base + y0;
             if (__builtin_amdgcn_ballot_w64((p0.flagged | p1.flagged) != 0)) {   // wave-uniform, rare
                 if (kFull || in_bounds<kVariant>(ya0, height, dy))
-                    emit_row4<true, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                    emit_row4<true, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx, nk);
                 if (kFull || in_bounds<kVariant>(ya0 + 1, height, dy))
                     emit_row4<true, kVariant, kFull>(row0 + pitch, loff, xa, width, yb.x, yb.y, p0, p1, &c0, &c0, &c1,
-                                                     &c1, plane, dx);
+                                                     &c1, plane, dx, nk);
             } else {
                 if (kFull || in_bounds<kVariant>(ya0, height, dy))
-                    emit_row4<false, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                    emit_row4<false, kVariant, kFull>(row0, loff, xa, width, ya.x, ya.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx, nk);
                 if (kFull || in_bounds<kVariant>(ya0 + 1, height, dy))
                     emit_row4<false, kVariant, kFull>(row0 + pitch, loff, xa, width, yb.x, yb.y, p0, p1, &c0, &c0,
-                                                      &c1, &c1, plane, dx);
+                                                      &c1, &c1, plane, dx, nk);
             }
         }
     } else if constexpr (kSampling == 0) {
@@ -477,10 +587,10 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
                 if (kFull || in_bounds<kVariant>(ya, height, dy)) {
                     if (__builtin_amdgcn_ballot_w64((p01.flagged | p23.flagged) != 0))
                         emit_row4<true, kVariant, kFull>(row, loff, xa, width, sy.x, sy.y, p01, p23, &c0, &c1, &c2,
-                                                         &c3, plane, dx);
+                                                         &c3, plane, dx, nk);
                     else
                         emit_row4<false, kVariant, kFull>(row, loff, xa, width, sy.x, sy.y, p01, p23, &c0, &c1, &c2,
-                                                          &c3, plane, dx);
+                                                          &c3, plane, dx, nk);
                 }
             }
         }
@@ -513,9 +623,9 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const bool flagged = __builtin_amdgcn_ballot_w64((p0.flagged | p1.flagged) != 0) != 0;
             if (kFull || in_bounds<kVariant>(y_base + y, height, dy)) {
                 if (flagged)
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx, nk);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p1, &c0, &c0, &c1, &c1, plane, dx, nk);
             }
         }
     } else if constexpr (kSampling == 4) {
@@ -542,9 +652,9 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int xu = x_base + lane * 4;
             if (kFull || in_bounds<kVariant>(y_base + y, height, dy)) {
                 if (__builtin_amdgcn_ballot_w64(p0.flagged != 0))
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane, dx);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane, dx, nk);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane, dx);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sy.x, sy.y, p0, p0, &c0, &c0, &c0, &c0, plane, dx, nk);
             }
         }
     } else if constexpr (kSampling == 5) {
@@ -581,17 +691,17 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const int ya = y_base + y0;
             if (__builtin_amdgcn_ballot_w64((p01.flagged | p23.flagged) != 0)) {   // wave-uniform, rare
                 if (kFull || in_bounds<kVariant>(ya, height, dy))
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx, nk);
                 if (kFull || in_bounds<kVariant>(ya + 1, height, dy))
                     emit_row4<true, kVariant, kFull>(strip, lo + static_cast<uint32_t>(pitch), xu, width, syb.x,
-                                                     syb.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
+                                                     syb.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx, nk);
             } else {
                 if (kFull || in_bounds<kVariant>(ya, height, dy))
                     emit_row4<false, kVariant, kFull>(strip, lo, xu, width, sya.x, sya.y, p01, p23, &c0, &c1, &c2,
-                                                      &c3, plane, dx);
+                                                      &c3, plane, dx, nk);
                 if (kFull || in_bounds<kVariant>(ya + 1, height, dy))
                     emit_row4<false, kVariant, kFull>(strip, lo + static_cast<uint32_t>(pitch), xu, width, syb.x,
-                                                      syb.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
+                                                      syb.y, p01, p23, &c0, &c1, &c2, &c3, plane, dx, nk);
             }
         }
     } else {
@@ -614,7 +724,7 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             if (kFull || in_bounds<kVariant>(y_base + y, height, dy))
                 store4<kFull, kVariant>(strip, lo, x_base + cu4 * 4, width, perm(g01, g01, 0x0c000000u),
                                         perm(g01, g01, 0x0c010101u), perm(g23, g23, 0x0c000000u),
-                                        perm(g23, g23, 0x0c010101u), plane, dx);
+                                        perm(g23, g23, 0x0c010101u), plane, dx, nk);
         }
     }
 }
@@ -657,7 +767,8 @@ __device__ __forceinline__ uint32_t scaled_pair(const char* __restrict__ slots, 
 template <int kSampling, int kLog, bool kFull, int kVariant>
 __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slots, int lane,
                                                     uint8_t* __restrict__ out, int pitch, int width, int height,
-                                                    int y_base, int x_base, int dx = 0, int dy = 0)
+                                                    int y_base, int x_base, int dx = 0, int dy = 0,
+                                                    const NormDev& nk = NormDev{})
 {
     static_assert(kSampling == 0 || kSampling == 1 || kSampling == 3, "scaled decode: 4:4:4, 4:2:0 and gray");
     using G = KGeom<kSampling>;
@@ -683,7 +794,7 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
             const uint32_t g01 = sat_pk_u8(y01), g23 = sat_pk_u8(y23);
             if (live)
                 store4<kFull, kVariant>(strip, lo, xu, width, perm(g01, g01, 0x0c000000u), perm(g01, g01, 0x0c010101u),
-                                        perm(g23, g23, 0x0c000000u), perm(g23, g23, 0x0c010101u), plane, dx);
+                                        perm(g23, g23, 0x0c000000u), perm(g23, g23, 0x0c010101u), plane, dx, nk);
         } else if constexpr (kSampling == 0) {
             const uint32_t u01 = scaled_pair<0, kLog, 1>(slots, x, y), u23 = scaled_pair<0, kLog, 1>(slots, x + 2, y);
             const uint32_t v01 = scaled_pair<0, kLog, 2>(slots, x, y), v23 = scaled_pair<0, kLog, 2>(slots, x + 2, y);
@@ -695,9 +806,9 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
             const bool flagged = __builtin_amdgcn_ballot_w64(live && (p01.flagged | p23.flagged) != 0) != 0;
             if (live) {
                 if (flagged)   // wave-uniform, rare
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane, dx, nk);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane, dx);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p01, p23, &c0, &c1, &c2, &c3, plane, dx, nk);
             }
         } else {
             // 4:2:0: chroma samples x/2 and x/2 + 1 of chroma row y/2 serve 2 px each
@@ -709,9 +820,9 @@ __device__ __forceinline__ void colour_stage_scaled(const char* __restrict__ slo
             const bool flagged = __builtin_amdgcn_ballot_w64(live && (p0.flagged | p1.flagged) != 0) != 0;
             if (live) {
                 if (flagged)   // wave-uniform, rare
-                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                    emit_row4<true, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane, dx, nk);
                 else
-                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane, dx);
+                    emit_row4<false, kVariant, kFull>(strip, lo, xu, width, y01, y23, p0, p1, &c0, &c0, &c1, &c1, plane, dx, nk);
             }
         }
     }
@@ -1024,11 +1135,17 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
 {
     using L = KLayout;
     constexpr int kLog = kScaleLog<kVariant>;
-    static_assert(kLog == 0 || (kFmt == 0 && (kVariant & ~(kVarScale | kVarRoi | kOutBgr24 | kOutRgb24 | kOutPlanar)) == 0),
+    static_assert(kLog == 0 ||
+                      (kFmt == 0 && (kVariant & ~(kVarScale | kVarRoi | kOutBgr24 | kOutRgb24 | kOutPlanar | kOutFloat)) == 0),
                   "scaled kernels: int16 zigzag input, output format bits only");
     constexpr bool kRoi = (kVariant & kVarRoi) != 0;
-    static_assert(!kRoi || (kFmt == 0 && (kVariant & ~(kVarScale | kVarRoi | kOutBgr24 | kOutRgb24 | kOutPlanar)) == 0),
+    static_assert(!kRoi ||
+                      (kFmt == 0 && (kVariant & ~(kVarScale | kVarRoi | kOutBgr24 | kOutRgb24 | kOutPlanar | kOutFloat)) == 0),
                   "ROI kernels: int16 zigzag input, output format and scale bits only");
+    constexpr bool kNorm = (kVariant & kOutFloat) != 0;
+    static_assert(!kNorm || (kFmt == 0 && (kVariant & kOutPlanar) != 0 && (kVariant & kOutFloat) != kOutFloat &&
+                             (kVariant & ~(kVarScale | kVarRoi | kOutPlanar | kOutFloat | kVarD16)) == 0),
+                  "float kernels: planar, one element size, int16 zigzag input");
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerGroup * L::wave_lds];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -1069,6 +1186,9 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int k = 0; k < 4; ++k) q[c][k] = 0;
+
+    NormDev nk{};     // float formats: the plan's constants
+    if constexpr (kNorm) nk = norm_load<kRoi, (kVariant & kOutF16) != 0>(frames, nframes);
 
     FrameCursor pc;   // frame of the task being prefetched
     cursor_seek<kRoi>(pc, frames, nframes, total_tasks, t_begin);
@@ -1147,18 +1267,18 @@ __global__ __launch_bounds__(kGroupThreads, KLayout::min_waves) void decode_kern
         } else if constexpr (kLog > 0) {
             if (full)
                 colour_stage_scaled<kSampling, kLog, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height,
-                                                                     tg.y_base, tg.x_base, dx, dy);
+                                                                     tg.y_base, tg.x_base, dx, dy, nk);
             else {
                 colour_stage_scaled<kSampling, kLog, false, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height,
-                                                                      tg.y_base, tg.x_base, dx, dy);
+                                                                      tg.y_base, tg.x_base, dx, dy, nk);
                 __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): edge strips drain their stores, as below
             }
         } else if (full)
             colour_stage<kSampling, true, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base,
-                                                    0, dx, dy);
+                                                    0, dx, dy, nk);
         else {
             colour_stage<kSampling, false, kVariant>(slots, lane, fout, cc.pitch, cc.width, cc.height, tg.y_base, tg.x_base,
-                                                     0, dx, dy);
+                                                     0, dx, dy, nk);
             // Edge strips issue a data-dependent number of stores; drain them
             // here so the loop head's wait for the prefetched coefficients can
             // be a fixed vmcnt (the full path's stores may stay in flight).
@@ -1193,6 +1313,11 @@ __global__ __launch_bounds__(kLatThreads) void decode_kernel_lat(const void* __r
     char* rowbuf = lds + kTaskBlocks * kSlotBytes + wave * 8 * kRowBufBlock;
     const int64_t task = blockIdx.x;
     if (task >= total_tasks) return;
+    static_assert((kVariant & kOutFloat) == 0 || (kFmt == 0 && (kVariant & ~kOutFloat) == kOutPlanar &&
+                                                  (kVariant & kOutFloat) != kOutFloat),
+                  "float kernels: planar, one element size, int16 zigzag input");
+    NormDev nk{};     // float formats: the plan's constants
+    if constexpr ((kVariant & kOutFloat) != 0) nk = norm_load<false, (kVariant & kOutF16) != 0>(frames, nframes);
     FrameCursor cc;
     cursor_seek(cc, frames, nframes, total_tasks, task);
     const TaskGeom tg = task_geom<kSampling>(cc, task);
@@ -1259,10 +1384,10 @@ __global__ __launch_bounds__(kLatThreads) void decode_kernel_lat(const void* __r
     uint8_t* fout = out + cc.out_base;
     if (cc.vec_ok && tg.x_base + kStripW <= cc.width && tg.y_base + kRows <= cc.height)
         colour_stage<kSampling, true, kVariant, kLatWaves>(slots, lane, fout, cc.pitch, cc.width, cc.height,
-                                                            tg.y_base, tg.x_base, wave);
+                                                            tg.y_base, tg.x_base, wave, 0, 0, nk);
     else
         colour_stage<kSampling, false, kVariant, kLatWaves>(slots, lane, fout, cc.pitch, cc.width, cc.height,
-                                                             tg.y_base, tg.x_base, wave);
+                                                             tg.y_base, tg.x_base, wave, 0, 0, nk);
 }
 
 // IDCT only, out of place (the reference's batch_idct): one wave = 8 blocks.

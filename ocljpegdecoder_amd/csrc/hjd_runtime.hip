@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -69,6 +70,16 @@ int hjd_internal::set_error(int code, const char* fmt, ...)
     return code;
 }
 
+int hjd_internal::norm_check(const float* a, const float* b)
+{
+    if (!a || !b) return set_error(HJD_E_INVALID, "normalisation constants: a or b is NULL");
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(a[c]) || !std::isfinite(b[c]))
+            return set_error(HJD_E_INVALID, "normalisation constants must be finite (channel %d: a = %g, b = %g)", c,
+                             static_cast<double>(a[c]), static_cast<double>(b[c]));
+    return HJD_OK;
+}
+
 struct hjd_ctx {
     int device = 0;
     int num_cu = 256;
@@ -93,6 +104,7 @@ struct hjd_plan {
     int autotune_cached = 0;    // 1: that call reused a cached choice
     int scale = 1;              // hjd_plan_create_scaled: 1, 2, 4 or 8
     int roi = 0;                // hjd_plan_create_roi with rectangles: the RoiDev table follows d_frames
+    size_t norm_off = 0;        // float formats: byte offset of the NormDev record in d_frames (after both tables)
 };
 
 constexpr int64_t kDefaultLatencyMaxTasks = 1024;   // measured: profiles/r01_latency_kernel.json
@@ -346,7 +358,7 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
     SamplingGeom sg;
     if (!sampling_geom(sampling, &sg)) return set_error(HJD_E_INVALID, "unsupported sampling %d", sampling);
     const int grid = grid_blocks > 0 ? grid_blocks : grid_for_chunk(tasks, default_per_wave(sampling, fmt));
-    if (out_format < HJD_OUT_BGRX || out_format > HJD_OUT_RGB_PLANAR)
+    if (!out_format_bytes(out_format))
         return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
     using K = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*);   // latency kernels
     using KP = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*, int64_t, int64_t);
@@ -357,6 +369,53 @@ int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_
     const int64_t split_n = (variant & 2) ? static_cast<int64_t>(grid) : static_cast<int64_t>(grid) * hjd::kWavesPerGroup;
     const int64_t split_t = (variant & 2) ? (tasks + hjd::kWavesPerGroup - 1) / hjd::kWavesPerGroup : tasks;
     const int64_t chunk = split_t / split_n, rem = split_t % split_n;
+    if (out_format_float_bytes(out_format)) {   // normalised float planes: int16 input, no variants
+        const int lg = scale_log2(scale);
+        const int fi = out_format == HJD_OUT_RGB_PLANAR_F16 ? 0 : 1;
+        if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+        if (fmt != 0) return set_error(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input only");
+        if (variant != 0) return set_error(HJD_E_INVALID, "kernel variants are BGRX-only");
+        if (lg > 0 && !scaled_sampling_ok(sampling))
+            return set_error(HJD_E_INVALID, "scaled decode serves 4:4:4, 4:2:0 and gray, not sampling %d", sampling);
+        if ((roi || lg > 0) && kernel_mode == HJD_KERNEL_LATENCY)
+            return set_error(HJD_E_INVALID, "scaled and ROI decode have no latency kernel");
+#define HJD_KN(S, X) hjd::decode_kernel<S, 0, hjd::kOutPlanar | hjd::kOutF16 | (X)>, \
+                     hjd::decode_kernel<S, 0, hjd::kOutPlanar | hjd::kOutF32 | (X)>
+#define HJD_KN6(X) HJD_KN(0, X), HJD_KN(1, X), HJD_KN(2, X), HJD_KN(3, X), HJD_KN(4, X), HJD_KN(5, X)
+#define HJD_KN3(L, X) HJD_KN(0, ((L) << hjd::kScaleShift) | (X)), HJD_KN(1, ((L) << hjd::kScaleShift) | (X)), \
+                      HJD_KN(3, ((L) << hjd::kScaleShift) | (X))
+        // scale 1: [sampling index][F16, F32]; scaled: [log2 scale - 1][4:4:4, 4:2:0, gray][F16, F32]
+        static const KP kNorm1[12] = {HJD_KN6(0)};
+        static const KP kNormD16[2] = {HJD_KN(0, hjd::kVarD16)};
+        static const KP kNormScaled[18] = {HJD_KN3(1, 0), HJD_KN3(2, 0), HJD_KN3(3, 0)};
+        static const KP kNormRoi1[12] = {HJD_KN6(hjd::kVarRoi)};
+        static const KP kNormRoiScaled[18] = {HJD_KN3(1, hjd::kVarRoi), HJD_KN3(2, hjd::kVarRoi),
+                                              HJD_KN3(3, hjd::kVarRoi)};
+#undef HJD_KN3
+#undef HJD_KN6
+#undef HJD_KN
+        if (!roi && lg == 0 && latency) {
+#define HJD_KNL(S) hjd::decode_kernel_lat<S, 0, hjd::kOutPlanar | hjd::kOutF16>, \
+                   hjd::decode_kernel_lat<S, 0, hjd::kOutPlanar | hjd::kOutF32>
+            static const K kNormLat[12] = {HJD_KNL(0), HJD_KNL(1), HJD_KNL(2), HJD_KNL(3), HJD_KNL(4), HJD_KNL(5)};
+#undef HJD_KNL
+            if (tasks > (int64_t(1) << 31) - 1) return set_error(HJD_E_INVALID, "too many tasks for the latency kernel");
+            hipLaunchKernelGGL(kNormLat[2 * sg.index + fi], dim3(static_cast<uint32_t>(tasks)), dim3(hjd::kLatThreads), 0,
+                               static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
+                               reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out));
+            HJD_HIP(hipGetLastError());
+            return HJD_OK;
+        }
+        const int srow = sampling == HJD_YUV444 ? 0 : sampling == HJD_YUV420 ? 1 : 2;
+        KP k = lg > 0 ? (roi ? kNormRoiScaled : kNormScaled)[6 * (lg - 1) + 2 * srow + fi]
+                      : (roi ? kNormRoi1 : kNorm1)[2 * sg.index + fi];
+        if (!roi && lg == 0 && sampling == HJD_YUV444 && hjd_internal::d16_gather_selected(device)) k = kNormD16[fi];
+        hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream), d_coefs,
+                           d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
+                           static_cast<uint8_t*>(d_out), chunk, rem);
+        HJD_HIP(hipGetLastError());
+        return HJD_OK;
+    }
     if (roi) {   // ROI decode: the persistent kernel only
         const int lg = scale_log2(scale);
         if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
@@ -587,6 +646,52 @@ int hjd_roi_geometry(int width, int height, int sampling, int scale, const hjd_r
     return HJD_OK;
 }
 
+// One frame's geometry and output layout, as a plan of `scale` (and ROIs)
+// takes it: sw x sh is what the frame writes (the ROI's size, else the scaled
+// frame's), rg the ROI's geometry.  i: the frame's index, for the message.
+static int check_frame(const hjd_frame& f, int input_format, int scale, const hjd_rect* roi, int i,
+                       hjd_internal::RoiGeom* rg, int* sw, int* sh)
+{
+    int mw, mh, bpm, tasks_mcus;
+    int rc = geometry(f.width, f.height, f.sampling, mw, mh, bpm, tasks_mcus);
+    if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
+    const int rbytes = hjd_internal::out_format_row_bytes(f.out_format);
+    if (!rbytes) return fail(HJD_E_INVALID, "unknown output format %d", f.out_format);
+    if (hjd_internal::out_format_float_bytes(f.out_format) && input_format != HJD_IN_Q16_ZIGZAG)
+        return fail(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
+    if (scale > 1 && !hjd_internal::scaled_sampling_ok(f.sampling))
+        return fail(HJD_E_INVALID,
+                    "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not 4:2:2, 4:1:1 or 4:4:0 "
+                    "(sampling %d)", i, scale, f.sampling);
+    *sw = hjd_internal::scaled_dim(f.width, scale);
+    *sh = hjd_internal::scaled_dim(f.height, scale);
+    if (roi) {   // the output is the ROI: pitch and payload refer to it
+        rc = hjd_internal::roi_geom(f.width, f.height, f.sampling, scale, roi, rg);
+        if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
+        *sw = roi->w;
+        *sh = roi->h;
+    }
+    // BGRX / BGR24: 4-byte pitches and offsets; the RGB formats take any; the
+    // float planes multiples of their element size
+    const uint64_t amask = static_cast<uint64_t>(hjd_internal::out_format_pitch_mask(f.out_format));
+    if (f.out_pitch < static_cast<int64_t>(rbytes) * *sw || (f.out_pitch & amask) || (f.out_offset & amask))
+        return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
+    return HJD_OK;
+}
+
+int hjd_frame_check(const hjd_frame* frame, int input_format, int scale, const hjd_rect* roi)
+{
+    if (!frame) return fail(HJD_E_INVALID, "frame is NULL");
+    if (hjd_internal::scale_log2(scale) < 0) return fail(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    if (input_format != HJD_IN_Q16_ZIGZAG && input_format != HJD_IN_I32_NATURAL)
+        return fail(HJD_E_INVALID, "unknown input format %d", input_format);
+    if ((scale > 1 || roi) && input_format == HJD_IN_I32_NATURAL)
+        return fail(HJD_E_INVALID, "scaled and ROI decode take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
+    hjd_internal::RoiGeom rg;
+    int sw, sh;
+    return check_frame(*frame, input_format, scale, roi, 0, &rg, &sw, &sh);
+}
+
 int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
                     const int32_t* qtables, int nq, hjd_plan** out)
 {
@@ -622,9 +727,8 @@ int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int 
     const int out_format = nframes > 0 ? frames[0].out_format : HJD_OUT_BGRX;
     const int obytes = hjd_internal::out_format_bytes(out_format);
     if (!obytes) return fail(HJD_E_INVALID, "unknown output format %d", out_format);
-    const int rbytes = hjd_internal::out_format_row_bytes(out_format);
-    // BGRX / BGR24: 4-byte pitches and offsets; the RGB formats take any
-    const uint64_t amask = hjd_internal::out_format_any_alignment(out_format) ? 0 : 3;
+    if (hjd_internal::out_format_float_bytes(out_format) && input_format != HJD_IN_Q16_ZIGZAG)
+        return fail(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
     for (int i = 0; i < nframes; ++i) {
         const hjd_frame& f = frames[i];
         int mw, mh, bpm, tasks_mcus;
@@ -634,20 +738,10 @@ int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int 
             return fail(HJD_E_INVALID, "frame %d: mixed sampling in one plan (use one plan per sampling)", i);
         if (f.out_format != out_format)
             return fail(HJD_E_INVALID, "frame %d: mixed output formats in one plan (use one plan per format)", i);
-        if (scale > 1 && !hjd_internal::scaled_sampling_ok(f.sampling))
-            return fail(HJD_E_INVALID,
-                        "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not 4:2:2, 4:1:1 or 4:4:0 "
-                        "(sampling %d)", i, scale, f.sampling);
-        int sw = hjd_internal::scaled_dim(f.width, scale), sh = hjd_internal::scaled_dim(f.height, scale);
+        int sw, sh;
         hjd_internal::RoiGeom rg;
-        if (rois) {   // the output is the ROI: pitch and payload refer to it
-            rc = hjd_internal::roi_geom(f.width, f.height, f.sampling, scale, &rois[i], &rg);
-            if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
-            sw = rois[i].w;
-            sh = rois[i].h;
-        }
-        if (f.out_pitch < static_cast<int64_t>(rbytes) * sw || (f.out_pitch & amask) || (f.out_offset & amask))
-            return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
+        rc = check_frame(f, input_format, scale, rois ? &rois[i] : nullptr, i, &rg, &sw, &sh);
+        if (rc) return rc;
         FrameDev& d = fd[i];
         if (input_format == HJD_IN_Q16_ZIGZAG) {
             for (int c = 0; c < 3; ++c)
@@ -701,12 +795,20 @@ int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int 
     // a ROI plan's RoiDev table follows the nframes records (frames + nframes)
     static_assert(sizeof(hjd_internal::RoiRecord) == sizeof(hjd::RoiDev), "side record layout");
     const size_t side_off = static_cast<size_t>(nframes) * sizeof(FrameDev);
-    hipError_t e = hipMalloc(&p->d_frames, fd.size() * sizeof(FrameDev) + sides.size() * sizeof(hjd::RoiDev));
+    // a float plan's NormDev record follows both tables; a = 1, b = 0 until hjd_plan_set_normalize
+    static_assert(sizeof(hjd_internal::NormRecord) == sizeof(hjd::NormDev), "norm record layout");
+    const bool norm = hjd_internal::out_format_float_bytes(out_format) != 0;
+    p->norm_off = norm ? side_off + (rois ? static_cast<size_t>(nframes) * sizeof(hjd::RoiDev) : 0) : 0;
+    const hjd_internal::NormRecord ident = hjd_internal::norm_identity();
+    hipError_t e = hipMalloc(&p->d_frames, std::max(fd.size() * sizeof(FrameDev) + sides.size() * sizeof(hjd::RoiDev),
+                                                    p->norm_off) + (norm ? sizeof(hjd::NormDev) : 0));
     if (e == hipSuccess) e = hipMalloc(&p->d_qt, qnat.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemcpy(p->d_frames, fd.data(), fd.size() * sizeof(FrameDev), hipMemcpyHostToDevice);
     if (e == hipSuccess && rois && nframes > 0)
         e = hipMemcpy(reinterpret_cast<char*>(p->d_frames) + side_off, sides.data(),
                       static_cast<size_t>(nframes) * sizeof(hjd::RoiDev), hipMemcpyHostToDevice);
+    if (e == hipSuccess && norm)
+        e = hipMemcpy(reinterpret_cast<char*>(p->d_frames) + p->norm_off, &ident, sizeof(ident), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->d_qt, qnat.data(), qnat.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(p->d_frames);
@@ -732,12 +834,33 @@ int hjd_plan_set_variant(hjd_plan* plan, int variant)
 {
     if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
     if (variant < 0 || variant > 3) return fail(HJD_E_INVALID, "unknown kernel variant %d", variant);
-    if (variant != 0 && hjd_internal::out_format_any_alignment(plan->out_format))
+    if (variant != 0 && (hjd_internal::out_format_any_alignment(plan->out_format) ||
+                         hjd_internal::out_format_float_bytes(plan->out_format)))
         return fail(HJD_E_INVALID, "kernel variants are BGRX-only");
     if (variant != 0 && plan->scale != 1)
         return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no kernel variants", plan->scale);
     if (variant != 0 && plan->roi) return fail(HJD_E_INVALID, "a ROI plan has no kernel variants");
     plan->variant = variant;
+    return HJD_OK;
+}
+
+int hjd_plan_set_normalize(hjd_plan* plan, const float a[3], const float b[3])
+{
+    int rc = hjd_internal::norm_check(a, b);
+    if (rc) return rc;
+    if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
+    if (!hjd_internal::out_format_float_bytes(plan->out_format))
+        return fail(HJD_E_INVALID, "hjd_plan_set_normalize: output format %d is not HJD_OUT_RGB_PLANAR_F16 / _F32",
+                    plan->out_format);
+    hjd_internal::NormRecord r = hjd_internal::norm_identity();
+    for (int c = 0; c < 3; ++c) {
+        r.a[c] = a[c];
+        r.b[c] = b[c];
+    }
+    HJD_HIP(hipSetDevice(plan->ctx->device));
+    // synchronous, like the plan's own upload: launches already enqueued keep what they read
+    HJD_HIP(hipDeviceSynchronize());
+    HJD_HIP(hipMemcpy(reinterpret_cast<char*>(plan->d_frames) + plan->norm_off, &r, sizeof(r), hipMemcpyHostToDevice));
     return HJD_OK;
 }
 

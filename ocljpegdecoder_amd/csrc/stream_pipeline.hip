@@ -352,6 +352,9 @@ int hjd_stream_set_output_format(hjd_stream* st, int out_format)
 {
     if (!st) return set_error(HJD_E_INVALID, "stream is NULL");
     if (!hjd_internal::out_format_bytes(out_format)) return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
+    if (hjd_internal::out_format_float_bytes(out_format))
+        return set_error(HJD_E_INVALID, "hjd_stream does not serve the float output formats (format %d): use hjd_gdec "
+                                        "or a plan", out_format);
     st->out_format = out_format;   // each job keeps the format it was submitted with
     return HJD_OK;
 }

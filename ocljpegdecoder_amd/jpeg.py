@@ -24,6 +24,12 @@ from ._lib import HjdJpegInfo, HjdRect, check
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _i16p = ctypes.POINTER(ctypes.c_int16)
 
+try:   # decode_rgb's default dtype (the package has loaded torch already where it is installed)
+    import torch as _torch
+    _UINT8 = _torch.uint8
+except ImportError:
+    _UINT8 = None
+
 
 @dataclass
 class JpegInfo:
@@ -139,14 +145,19 @@ def _out_pitch(out, out_format: int) -> int:
     return out.shape[-1] * item
 
 
-def decode_jpeg(ctx, data: bytes, stream=None, out_format: int = 0):
+def decode_jpeg(ctx, data: bytes, stream=None, out_format: int = 0, normalize=None):
     """JPEG bytes -> device pixels (host Huffman, then the fused kernel on the
     device): an (H, W) int32 tensor of BGRX words, or with out_format=OUT_BGR24
     an (H, pitch) uint8 tensor of B,G,R bytes (pitch = (3W+3)&~3, the 24-bpp
     BMP row), with OUT_RGB24 an (H, W, 3) uint8 tensor and with OUT_RGB_PLANAR
-    a (3, H, W) uint8 tensor (both contiguous)."""
+    a (3, H, W) uint8 tensor (both contiguous); with OUT_RGB_PLANAR_F16 / _F32
+    a (3, H, W) float16 / float32 tensor normalised with normalize = (a, b)
+    (norm_constants(); None: a = 1, b = 0)."""
     import torch
-    from .backend import IN_Q16_ZIGZAG, OUT_BGR24, OUT_RGB24, OUT_RGB_PLANAR, FrameSpec, Plan, default_pitch
+    from .backend import (IN_Q16_ZIGZAG, OUT_BGR24, OUT_RGB24, OUT_RGB_PLANAR, OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32,
+                          FrameSpec, Plan, default_pitch)
+    if normalize is not None and out_format not in (OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32):
+        raise ValueError("normalize needs out_format OUT_RGB_PLANAR_F16 or OUT_RGB_PLANAR_F32")
     coefs, info = decode_coefs(data)
     dev = torch.device("cuda", ctx.device)
     d_coefs = torch.from_numpy(coefs).to(dev)
@@ -156,10 +167,13 @@ def decode_jpeg(ctx, data: bytes, stream=None, out_format: int = 0):
         out = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=dev)
     elif out_format == OUT_RGB_PLANAR:
         out = torch.empty((3, info.height, info.width), dtype=torch.uint8, device=dev)
+    elif out_format in (OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32):
+        out = torch.empty((3, info.height, info.width), device=dev,
+                          dtype=torch.float16 if out_format == OUT_RGB_PLANAR_F16 else torch.float32)
     else:
         out = torch.empty((info.height, info.width), dtype=torch.int32, device=dev)
     plan = Plan(ctx, [FrameSpec(info.width, info.height, info.sampling, qt_index=(0, 1, 2), out_format=out_format)],
-                IN_Q16_ZIGZAG, qtables=info.qt)
+                IN_Q16_ZIGZAG, qtables=info.qt, normalize=normalize)
     plan.launch(d_coefs, out, stream)
     return out
 
@@ -289,12 +303,23 @@ class GpuDecoder:
         self._n = 0
         self.out_format = 0
         self.scale = 1
+        self.normalize = ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0))   # the C default: out = float(u8)
 
     def set_output_format(self, out_format: int):
-        """OUT_BGRX (default), OUT_BGR24, OUT_RGB24 or OUT_RGB_PLANAR for the
+        """OUT_BGRX (default), OUT_BGR24, OUT_RGB24, OUT_RGB_PLANAR or the
+        float planes OUT_RGB_PLANAR_F16 / _F32 (set_normalize) for the
         following decode() calls."""
         check(self.lib.hjd_gdec_set_output_format(self.handle, int(out_format)), "hjd_gdec_set_output_format")
         self.out_format = int(out_format)
+
+    def set_normalize(self, a, b):
+        """hjd_gdec_set_normalize: the constants (R, G, B triples, or scalars;
+        norm_constants() makes them) of the float formats for the following
+        decode() calls: out = fma(float(u8), a, b).  Default a = 1, b = 0."""
+        from .backend import _norm_arrays
+        ca, cb = _norm_arrays((a, b))
+        check(self.lib.hjd_gdec_set_normalize(self.handle, ca, cb), "hjd_gdec_set_normalize")
+        self.normalize = (tuple(ca), tuple(cb))
 
     def set_scale(self, scale: int):
         """Decode scale of the following decode() calls: 1 (default), 2, 4 or 8
@@ -306,7 +331,8 @@ class GpuDecoder:
     def decode(self, datas: Sequence[bytes], outs, stream=None, rois=None):
         """outs: contiguous device tensors, one row per image row: (H, W) int32
         (or (H, pitch/4)) for BGRX, (H, pitch) uint8 for BGR24, (H, W, 3)
-        uint8 for RGB24, (3, H, W) uint8 for planar RGB.  rois: one (x, y, w, h)
+        uint8 for RGB24, (3, H, W) uint8 for planar RGB, (3, H, W) float16 /
+        float32 for the float planes.  rois: one (x, y, w, h)
         per image on the grid of the decoder's scale (hjd_gdec_decode_roi);
         outs are then sized (h, w)."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
@@ -330,25 +356,45 @@ class GpuDecoder:
         self._n = n
 
     def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1,
-                   rois=None):
-        """Decode to uint8 RGB tensors: layout "chw" gives (3, H, W) per image
-        (OUT_RGB_PLANAR), "hwc" gives (H, W, 3) (OUT_RGB24).  scale 2, 4 or 8
+                   rois=None, dtype=_UINT8, mean=None, std=None):
+        """Decode to RGB tensors: layout "chw" gives (3, H, W) per image
+        (OUT_RGB_PLANAR), "hwc" gives (H, W, 3) (OUT_RGB24).  dtype
+        torch.uint8 (default), or torch.float16 / torch.float32
+        ("chw" only): the network's input in the same launch,
+        (u8 / 255 - mean) / std per channel, exactly fma(float(u8), a, b) with
+        (a, b) = norm_constants(mean, std), for F16 then rounded to half
+        (OUT_RGB_PLANAR_F16 / _F32); mean and std (scalars or R, G, B triples)
+        default to 0 and 1, and need a float dtype.  scale 2, 4 or 8
         decodes at 1/scale (H and W below are then scaled_size's; the
         decoder's own scale is restored afterwards).  Without `out`,
         one new device tensor per image is returned as a list.  With `out`, a
-        contiguous uint8 device tensor (N, 3, H, W) ("chw") or (N, H, W, 3)
+        contiguous device tensor of that dtype (N, 3, H, W) ("chw") or (N, H, W, 3)
         ("hwc"), image i is decoded into out[i] and `out` is returned;
         ValueError if an image's size differs from it.  rois: one (x, y, w, h)
         per image on the (scaled) grid; tensors are sized per ROI, and with
         `out` every ROI's (h, w) must equal out's while the files' own sizes
         may differ.  Asynchronous like
-        decode(): call sync() before reading.  The decoder's output format is
-        restored afterwards."""
+        decode(): call sync() before reading.  The decoder's output format
+        and constants are restored afterwards."""
         import torch
-        from .backend import OUT_RGB24, OUT_RGB_PLANAR, scaled_size
+        from .backend import (OUT_RGB24, OUT_RGB_PLANAR, OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32, norm_constants,
+                              scaled_size)
         if layout not in ("chw", "hwc"):
             raise ValueError('layout must be "chw" or "hwc"')
         chw = layout == "chw"
+        if dtype is None:
+            dtype = torch.uint8
+        if dtype not in (torch.uint8, torch.float16, torch.float32):
+            raise ValueError("dtype must be torch.uint8, torch.float16 or torch.float32")
+        if dtype == torch.uint8:
+            if mean is not None or std is not None:
+                raise ValueError("mean and std need dtype torch.float16 or torch.float32")
+            fmt, norm = (OUT_RGB_PLANAR if chw else OUT_RGB24), None
+        else:
+            if not chw:
+                raise ValueError('the float dtypes are planar: layout must be "chw"')
+            fmt = OUT_RGB_PLANAR_F16 if dtype == torch.float16 else OUT_RGB_PLANAR_F32
+            norm = norm_constants(mean, std)
         infos = []
         for d in datas:   # headers only; any input decode() takes (bytes, arrays, pinned tensors)
             addr, size, _k = _ptr_size(d)
@@ -362,11 +408,11 @@ class GpuDecoder:
             sizes = [(int(r[2]), int(r[3])) for r in rois]
         if out is None:
             dev = torch.device("cuda", self.ctx.device)
-            outs = [torch.empty((3, h, w) if chw else (h, w, 3), dtype=torch.uint8, device=dev) for w, h in sizes]
+            outs = [torch.empty((3, h, w) if chw else (h, w, 3), dtype=dtype, device=dev) for w, h in sizes]
         else:
-            if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.ndim == 4
+            if not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.ndim == 4
                     and out.shape[1 if chw else 3] == 3):
-                raise ValueError("out must be a contiguous uint8 device tensor (N, 3, H, W) or (N, H, W, 3)")
+                raise ValueError(f"out must be a contiguous {dtype} device tensor (N, 3, H, W) or (N, H, W, 3)")
             if out.shape[0] != len(infos):
                 raise ValueError(f"out holds {out.shape[0]} images, {len(infos)} JPEGs given")
             oh, ow = (out.shape[2], out.shape[3]) if chw else (out.shape[1], out.shape[2])
@@ -375,14 +421,18 @@ class GpuDecoder:
                     raise ValueError(f"image {k} is {w}x{h}" + (f" at scale {scale}" if scale != 1 else "") +
                                      f", out is {ow}x{oh}")
             outs = [out[k] for k in range(len(infos))]
-        prev, prev_scale = self.out_format, self.scale
+        prev, prev_scale, prev_norm = self.out_format, self.scale, self.normalize
         self.set_scale(scale)
-        self.set_output_format(OUT_RGB_PLANAR if chw else OUT_RGB24)
+        self.set_output_format(fmt)
         try:
+            if norm is not None:
+                self.set_normalize(*norm)
             self.decode(datas, outs, stream, rois=rois)
         finally:
             self.set_output_format(prev)
             self.set_scale(prev_scale)
+            if norm is not None:
+                self.set_normalize(*prev_norm)
         return outs if out is None else out
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
