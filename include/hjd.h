@@ -399,6 +399,19 @@ int hjd_debug_d16_gather(int device, int* probe_zeroes, int* selected);
  * unknown name returns HJD_E_INVALID. */
 int hjd_debug_set_tuning(const char* name, const char* value);
 
+/* The library's pixel kernels are one table keyed by their template arguments
+ * {latency (1: decode_kernel_lat, 0: decode_kernel), sampling index S, input
+ * format F, variant word V}.  hjd_debug_kernel_key checks a launch shape as a
+ * launch would and selects its entry, with `d16` in place of the device's
+ * probe (hjd_debug_d16_gather's `selected`); it launches nothing.  stages: as
+ * hjd_debug_plan_launch_stages, or 0.  key[4] = the entry's {latency, S, F, V};
+ * HJD_E_INVALID for a shape no kernel serves.  hjd_debug_kernel_table writes
+ * the keys of the table, four ints each and at most `cap` of them (keys may be
+ * NULL), and returns their count.  Neither needs a GPU. */
+int hjd_debug_kernel_key(int sampling, int input_format, int out_format, int scale, int roi, int variant, int stages,
+                         int kernel_mode, int64_t tasks, int grid_blocks, int d16, int32_t key[4]);
+int hjd_debug_kernel_table(int32_t* keys, int cap);
+
 #ifdef __cplusplus
 }
 #endif

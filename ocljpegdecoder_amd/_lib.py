@@ -132,6 +132,8 @@ SIGNATURES = {
                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "hjd_debug_d16_gather": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p]),
     "hjd_debug_set_tuning": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p]),
+    "hjd_debug_kernel_key": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_i32p]),
+    "hjd_debug_kernel_table": (ctypes.c_int, [c_i32p, ctypes.c_int]),
     "hjd_debug_clock_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_void_p]),
 }

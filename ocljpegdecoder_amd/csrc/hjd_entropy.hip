@@ -3130,12 +3130,20 @@ int gdec_issue(hjd_gdec* g, void* const* d_outs, const int32_t* pitches, int16_t
         int r0 = 0;
         for (int sidx = 0; sidx < hjd_gdec::kClasses; ++sidx) {
             if (!g->nrec[sidx]) continue;
-            rc = hjd_internal::launch_decode(
-                g->device, g->num_cu, hjd_gdec::kClassSampling[sidx], HJD_IN_Q16_ZIGZAG, 0, coefs,
-                reinterpret_cast<const int32_t*>(g->d_blob + g->H.qt),
-                reinterpret_cast<const FrameRecord*>(g->d_blob + g->H.recs + g->class_block(sidx, r0)),
-                g->nrec[sidx], g->tasks[sidx], g->out_base[sidx], s, 0, g->out_format,
-                g->roi_batch ? HJD_KERNEL_PERSISTENT : HJD_KERNEL_AUTO, g->scale, g->roi_batch);
+            hjd_internal::DecodeLaunch l;   // int16 input, HJD_KERNEL_AUTO, the default grid
+            l.sampling = hjd_gdec::kClassSampling[sidx];
+            l.out_format = g->out_format;
+            l.scale = g->scale;
+            l.roi = g->roi_batch;
+            l.tasks = g->tasks[sidx];
+            l.device = g->device;
+            l.d_coefs = coefs;
+            l.d_qt_nat = reinterpret_cast<const int32_t*>(g->d_blob + g->H.qt);
+            l.d_frames = reinterpret_cast<const FrameRecord*>(g->d_blob + g->H.recs + g->class_block(sidx, r0));
+            l.nframes = g->nrec[sidx];
+            l.d_out = g->out_base[sidx];
+            l.stream = s;
+            rc = hjd_internal::launch_decode(l);
             if (rc) return rc;
             r0 += g->nrec[sidx];
         }
@@ -3309,12 +3317,14 @@ int hjd_gdec_decode(hjd_gdec* g, const uint8_t* const* datas, const size_t* size
         // a scaled call refuses a file the scaled kernels do not serve before
         // anything is staged or enqueued (a malformed file fails in staging)
         hjd_internal::ScanHeader h;
-        for (int i = 0; i < n; ++i)
-            if (datas[i] && hjd_internal::parse_scan_header(datas[i], sizes[i], &h) == HJD_OK &&
-                !hjd_internal::scaled_sampling_ok(h.sampling))
-                return set_error(HJD_E_INVALID,
-                                 "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not sampling %d", i,
-                                 g->scale, h.sampling);
+        hjd_internal::DecodeShape shape;
+        shape.scale = g->scale;
+        for (int i = 0; i < n; ++i) {
+            if (!datas[i] || hjd_internal::parse_scan_header(datas[i], sizes[i], &h) != HJD_OK) continue;
+            shape.sampling = h.sampling;
+            if (hjd_internal::shape_check(shape) != HJD_OK)
+                return set_error(HJD_E_INVALID, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        }
     }
     return gdec_run(g, datas, sizes, n, d_outs, pitches, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -3381,7 +3391,10 @@ int hjd_gdec_set_normalize(hjd_gdec* g, const float a[3], const float b[3])
 int hjd_gdec_set_scale(hjd_gdec* g, int scale)
 {
     if (!g) return set_error(HJD_E_INVALID, "gdec is NULL");
-    if (hjd_internal::scale_log2(scale) < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    hjd_internal::DecodeShape shape;
+    shape.scale = scale;
+    int rc = hjd_internal::shape_check(shape);
+    if (rc) return rc;
     g->scale = scale;   // applies to the next decode; an issued one keeps its scale
     return HJD_OK;
 }

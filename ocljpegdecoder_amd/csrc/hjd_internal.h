@@ -5,9 +5,9 @@
 #include <atomic>
 #include <vector>
 
-struct hjd_ctx;
+#include "hjd.h"
+
 struct hjd_jpeg_info;
-struct hjd_rect;
 
 namespace hjd_internal {
 
@@ -82,32 +82,78 @@ inline int scaled_dim(int d, int scale) { return (d + scale - 1) / scale; }
 // Samplings (enum hjd_sampling) the scaled kernels serve: 4:4:4, 4:2:0, gray.
 inline bool scaled_sampling_ok(int sampling) { return sampling == 0 || sampling == 1 || sampling == 4; }
 
-// Launch the fused kernel on device-resident frame records / natural-order
-// qtables (no host synchronisation, safe to call from any host thread).
-int launch_decode(int device, int num_cu, int sampling, int input_format, int variant, const void* d_coefs,
-                  const int32_t* d_qt_nat, const FrameRecord* d_frames, int nframes, int64_t tasks, void* d_out,
-                  void* stream, int grid_blocks, int out_format = 0, int kernel_mode = 0, int scale = 1,
-                  bool roi = false);   // roi: the RoiRecord table follows d_frames[nframes - 1]; a float
-                                       // out_format: the NormRecord follows that (or the frame records)
+// What a launch of the fused pixel kernel decodes, apart from its buffers: the
+// shape the legality rules (shape_check) and the kernel selection
+//  are functions of.
+struct DecodeShape {
+    int sampling = HJD_YUV420;             // enum hjd_sampling
+    int input_format = HJD_IN_Q16_ZIGZAG;
+    int out_format = HJD_OUT_BGRX;
+    int scale = 1;                         // 1, 2, 4 or 8
+    bool roi = false;                      // the RoiRecord table follows d_frames[nframes - 1]
+    int variant = 0;                       // kernel variant bits 0-1 (hjd_plan_set_variant)
+    int stages = 0;                        // stage-skipping measurement variant (hjd_debug_plan_launch_stages), or 0
+    int kernel_mode = HJD_KERNEL_AUTO;
+    int64_t tasks = 0;
+    int grid_blocks = 0;                   // workgroups of the persistent kernel; 0: the shape's default
+};
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: the one
+// statement of which shapes the kernels serve.  tasks and grid_blocks count
+// only where variant bits meet a byte format other than BGRX: such a launch
+// is legal if it takes the latency kernel, which ignores the bits.
+int shape_check(const DecodeShape& s);
 
-// HJD_OUT_RGB_PLANAR_F16 (5) / _F32 (6): element bytes of a float planar format (else 0; 4 is no format).
-inline int out_format_float_bytes(int out_format) { return out_format == 5 ? 2 : out_format == 6 ? 4 : 0; }
+// One launch: the shape, the device and its buffers.  d_frames: nframes frame
+// records, then (roi) their RoiRecord table, then (a float out_format) the
+// NormRecord; d_qt_nat: natural-order tables.
+struct DecodeLaunch : DecodeShape {
+    int device = 0;
+    const void* d_coefs = nullptr;
+    const int32_t* d_qt_nat = nullptr;
+    const FrameRecord* d_frames = nullptr;
+    int nframes = 0;
+    void* d_out = nullptr;
+    void* stream = nullptr;
+};
+// Check the shape, select its kernel from the table and launch it (no host
+// synchronisation, safe to call from any host thread).
+int launch_decode(const DecodeLaunch& l);
 
+// Properties of the output formats: one row per HJD_OUT_* value.
+struct OutFormat {
+    int bytes;         // per pixel overall (0: not a format)
+    int row_bytes;     // per pixel within one output row: planar rows hold one component
+    bool planar;       // three planes R, G, B at out_pitch * height (uint8 or float elements)
+    int float_bytes;   // element bytes of a float planar format (else 0)
+    int pitch_mask;    // a pitch and an offset must be clear of it
+    int align_mask;    // an output pointer / offset must be clear of it
+    int vector_mask;   // rows clear of it can take the kernel's full-width vector stores
+};
+constexpr OutFormat kNoOutFormat = {0, 0, false, 0, 3, 0, 3};
+constexpr OutFormat kOutFormats[] = {
+    {4, 4, false, 0, 3, 15, 15},   // HJD_OUT_BGRX: 4-byte pitches, 16-byte aligned rows
+    {3, 3, false, 0, 3, 3, 3},     // HJD_OUT_BGR24: 4-byte pitches and rows
+    {3, 3, false, 0, 0, 0, 3},     // HJD_OUT_RGB24: any pitch, offset and pointer
+    {3, 1, true, 0, 0, 0, 3},      // HJD_OUT_RGB_PLANAR: any
+    kNoOutFormat,                  // 4 is not a format
+    {6, 2, true, 2, 1, 1, 7},      // HJD_OUT_RGB_PLANAR_F16: multiples of the element size
+    {12, 4, true, 4, 3, 3, 15},    // HJD_OUT_RGB_PLANAR_F32
+};
+constexpr int kOutFormatRows = sizeof(kOutFormats) / sizeof(kOutFormats[0]);
+static_assert(kOutFormatRows == HJD_OUT_RGB_PLANAR_F32 + 1 && HJD_OUT_RGB_PLANAR == 3 && HJD_OUT_RGB_PLANAR_F16 == 5,
+              "one row per HJD_OUT_* value");
+inline const OutFormat& out_format_row(int out_format)   // 7 and above (and below 0): unknown
+{
+    return out_format >= 0 && out_format < kOutFormatRows ? kOutFormats[out_format] : kNoOutFormat;
+}
+
+// Element bytes of a float planar format (else 0).
+inline int out_format_float_bytes(int out_format) { return out_format_row(out_format).float_bytes; }
 // Bytes per output pixel of an HJD_OUT_* format overall (0 if unknown).
-inline int out_format_bytes(int out_format)
-{
-    return out_format == 0 ? 4 : out_format >= 1 && out_format <= 3 ? 3 : 3 * out_format_float_bytes(out_format);
-}
-
-// Three planes R, G, B at out_pitch * height (uint8 or float elements).
-inline bool out_format_planar(int out_format) { return out_format == 3 || out_format_float_bytes(out_format) != 0; }
-
-// Bytes per pixel within one output row: planar rows hold one component.
-inline int out_format_row_bytes(int out_format)
-{
-    return out_format == 3 ? 1 : out_format_float_bytes(out_format) ? out_format_float_bytes(out_format)
-                                                                   : out_format_bytes(out_format);
-}
+inline int out_format_bytes(int out_format) { return out_format_row(out_format).bytes; }
+inline bool out_format_planar(int out_format) { return out_format_row(out_format).planar; }
+// Bytes per pixel within one output row.
+inline int out_format_row_bytes(int out_format) { return out_format_row(out_format).row_bytes; }
 
 // Rows of `out_pitch` bytes a frame of `height` pixel rows occupies (planar:
 // the three planes follow each other at out_pitch * height).
@@ -116,32 +162,21 @@ inline int64_t out_format_rows(int out_format, int height)
     return out_format_planar(out_format) ? 3 * static_cast<int64_t>(height) : height;
 }
 
-// HJD_OUT_RGB24 / HJD_OUT_RGB_PLANAR: any pitch, offset and pointer are legal
-// (the others need 4-byte pitches and 4- or 16-byte aligned rows; the float
-// planar formats multiples of their element size: out_format_pitch_mask).
-inline bool out_format_any_alignment(int out_format) { return out_format == 2 || out_format == 3; }
-
-// Mask a pitch and an offset of this format must be clear of.
-inline int out_format_pitch_mask(int out_format)
+// HJD_OUT_RGB24 / HJD_OUT_RGB_PLANAR: any pitch, offset and pointer are legal.
+inline bool out_format_any_alignment(int out_format)
 {
-    return out_format_float_bytes(out_format) ? out_format_float_bytes(out_format) - 1
-                                              : out_format_any_alignment(out_format) ? 0 : 3;
+    return out_format_bytes(out_format) && !out_format_row(out_format).pitch_mask;
 }
+inline int out_format_pitch_mask(int out_format) { return out_format_row(out_format).pitch_mask; }
+inline uintptr_t out_format_align_mask(int out_format) { return out_format_row(out_format).align_mask; }
 
-// Required alignment mask of an output pointer / offset of this format.
-inline uintptr_t out_format_align_mask(int out_format)
-{
-    return out_format == 0 ? 15 : out_format == 1 ? 3 : out_format_float_bytes(out_format) ? out_format_float_bytes(out_format) - 1 : 0;
-}
-
-// Rows of this format can take the kernel's full-width vector stores (BGRX
-// and F32 planar: 16-byte aligned rows, F16 planar: 8, the others: 4).
+// Rows of this format can take the kernel's full-width vector stores.
 // out_base: the frame's offset; base_bits: low bits of the address out_base
 // is relative to, where that address is not known to be 16-byte aligned.
 inline bool out_vector_ok(int out_format, int64_t pitch, int64_t out_base, uintptr_t base_bits = 0)
 {
     const int64_t bits = pitch | out_base | static_cast<int64_t>(base_bits & 15);
-    return out_format == 0 || out_format == 6 ? (bits & 15) == 0 : out_format == 5 ? (bits & 7) == 0 : (bits & 3) == 0;
+    return (bits & out_format_row(out_format).vector_mask) == 0;
 }
 
 // The constants of the float formats as the kernels read them (layout of

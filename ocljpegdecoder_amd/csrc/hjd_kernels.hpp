@@ -534,9 +534,11 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
             const uint32_t cu = *reinterpret_cast<const uint32_t*>(slots + (m * 6 + 4) * kSlotBytes + coff);
             const uint32_t cv = *reinterpret_cast<const uint32_t*>(slots + (m * 6 + 5) * kSlotBytes + coff);
             uint8_t* row0 = strip + static_cast<int64_t>(4 * it) * pitch;   // wave-uniform
-            if constexpr ((kVariant & kAblNoCsc) != 0) {
-                store4<kFull, kVariant>(row0, loff, xa, width, ya.x, ya.y, cu, cv);
-                store4<kFull, kVariant>(row0 + pitch, loff, xa, width, yb.x, yb.y, cu, cv);
+            if constexpr ((kVariant & kAblNoCsc) != 0) {   // the rows are guarded as the product's are
+                if (kFull || in_bounds<kVariant>(y_base + y0, height, dy))
+                    store4<kFull, kVariant>(row0, loff, xa, width, ya.x, ya.y, cu, cv);
+                if (kFull || in_bounds<kVariant>(y_base + y0 + 1, height, dy))
+                    store4<kFull, kVariant>(row0 + pitch, loff, xa, width, yb.x, yb.y, cu, cv);
                 continue;
             }
             const ChromaTerms c0 = chroma_terms<0>(cu, cv);
@@ -573,8 +575,9 @@ __device__ __forceinline__ void colour_stage(const char* __restrict__ slots, int
                 const uint2 su = *reinterpret_cast<const uint2*>(base + kSlotBytes);
                 const uint2 sv = *reinterpret_cast<const uint2*>(base + 2 * kSlotBytes);
                 if constexpr ((kVariant & kAblNoCsc) != 0) {
-                    store4<kFull, kVariant>(strip + static_cast<int64_t>(4 * it + h) * pitch, loff, xa, width, sy.x,
-                                            sy.y, su.x ^ sv.x, su.y ^ sv.y);
+                    if (kFull || in_bounds<kVariant>(y_base + y, height, dy))
+                        store4<kFull, kVariant>(strip + static_cast<int64_t>(4 * it + h) * pitch, loff, xa, width, sy.x,
+                                                sy.y, su.x ^ sv.x, su.y ^ sv.y);
                     continue;
                 }
                 const ChromaTerms c0 = chroma_terms<0>(su.x, sv.x);

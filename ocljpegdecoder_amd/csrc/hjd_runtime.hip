@@ -24,6 +24,7 @@
 #include "hjd_kernels.hpp"
 
 using hjd::FrameDev;
+using hjd_internal::DecodeShape;
 using hjd_internal::SamplingGeom;
 using hjd_internal::sampling_geom;
 
@@ -246,11 +247,20 @@ static int geometry(int width, int height, int sampling, int& mcu_w, int& mcu_h,
 static int64_t default_per_wave(int sampling, int fmt);
 static int grid_for_chunk(int64_t tasks, int64_t per_wave, bool occupancy_floor = true);
 
-// launch_decode variant bits 8 and up: a stage-skipping measurement variant
-// (hjd_debug_plan_launch_stages), stages << kStageShift | plan variant bits.
-constexpr int kStageShift = 8;
-
 int hjd_internal::ctx_num_cu(const hjd_ctx* ctx) { return ctx->num_cu; }
+
+// A shape as shape_check takes it, with the default kernel mode and no variant.
+static DecodeShape make_shape(int sampling, int scale, int input_format = HJD_IN_Q16_ZIGZAG,
+                                            int out_format = HJD_OUT_BGRX, bool roi = false)
+{
+    DecodeShape s;
+    s.sampling = sampling;
+    s.scale = scale;
+    s.input_format = input_format;
+    s.out_format = out_format;
+    s.roi = roi;
+    return s;
+}
 
 // The ROI's task set: MCU rows myf..myl times the strips
 // that cover MCU columns mxf..mxl, anchored at mxf.
@@ -259,11 +269,8 @@ int hjd_internal::roi_geom(int width, int height, int sampling, int scale, const
     int mw, mh, bpm, tasks_mcus;
     int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
     if (rc) return rc;
+    if ((rc = shape_check(make_shape(sampling, scale)))) return rc;
     const int lg = scale_log2(scale);
-    if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-    if (scale > 1 && !scaled_sampling_ok(sampling))
-        return set_error(HJD_E_INVALID, "scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not sampling %d", scale,
-                         sampling);
     if (!roi || !g) return set_error(HJD_E_INVALID, "roi is NULL");
     const int sw = scaled_dim(width, scale), sh = scaled_dim(height, scale);
     if (roi->w < 1 || roi->h < 1)
@@ -317,10 +324,7 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
     int mw, mh, bpm, tasks_mcus;
     int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
     if (rc) return rc;
-    if (scale_log2(scale) < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-    if (scale > 1 && !scaled_sampling_ok(sampling))
-        return set_error(HJD_E_INVALID, "scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not sampling %d", scale,
-                         sampling);
+    if ((rc = shape_check(make_shape(sampling, scale)))) return rc;
     static_assert(sizeof(FrameRecord) == sizeof(FrameDev), "record layout");
     FrameDev d;
     memset(&d, 0, sizeof(d));
@@ -347,203 +351,182 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
     return static_cast<int64_t>(d.strips) * mh;
 }
 
-int hjd_internal::launch_decode(int device, int num_cu, int sampling, int input_format, int variant,
-                                const void* d_coefs, const int32_t* d_qt_nat, const FrameRecord* d_frames,
-                                int nframes, int64_t tasks, void* d_out, void* stream, int grid_blocks, int out_format,
-                                int kernel_mode, int scale, bool roi)
+// ---------------------------------------------------------------------------
+// The fused pixel kernel's launch: which shapes are legal
+// (shape_check), the table of every decode_kernel / decode_kernel_lat the
+// library instantiates, keyed by its template arguments, and the selection of
+// one entry for a shape (select_key).
+// ---------------------------------------------------------------------------
+// A shape takes the latency kernel (one workgroup per task): on request, or a
+// small HJD_KERNEL_AUTO launch of whole full-size frames with the default grid.
+static bool takes_latency(const DecodeShape& s)
 {
-    HJD_HIP(hipSetDevice(device));
-    const int fmt = input_format == HJD_IN_Q16_ZIGZAG ? 0 : 1;
-    (void)num_cu;
+    return s.stages == 0 && s.scale == 1 && !s.roi &&
+           (s.kernel_mode == HJD_KERNEL_LATENCY ||
+            (s.kernel_mode == HJD_KERNEL_AUTO && s.grid_blocks == 0 && s.tasks <= latency_max_tasks()));
+}
+
+int hjd_internal::shape_check(const DecodeShape& s)
+{
+    const int lg = scale_log2(s.scale);
+    const bool i32 = s.input_format == HJD_IN_I32_NATURAL;
+    const bool whole = lg == 0 && !s.roi;   // whole frames at full size
     SamplingGeom sg;
-    if (!sampling_geom(sampling, &sg)) return set_error(HJD_E_INVALID, "unsupported sampling %d", sampling);
-    const int grid = grid_blocks > 0 ? grid_blocks : grid_for_chunk(tasks, default_per_wave(sampling, fmt));
-    if (!out_format_bytes(out_format))
-        return set_error(HJD_E_INVALID, "unknown output format %d", out_format);
-    using K = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*);   // latency kernels
-    using KP = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*, int64_t, int64_t);
-    const bool latency = kernel_mode == HJD_KERNEL_LATENCY ||
-                         (kernel_mode == HJD_KERNEL_AUTO && grid_blocks == 0 && tasks <= latency_max_tasks());
-    // the task split of the persistent kernels (see decode_kernel): default
-    // order over grid * 4 waves, wg-interleave over grid groups of 4-task quads
-    const int64_t split_n = (variant & 2) ? static_cast<int64_t>(grid) : static_cast<int64_t>(grid) * hjd::kWavesPerGroup;
-    const int64_t split_t = (variant & 2) ? (tasks + hjd::kWavesPerGroup - 1) / hjd::kWavesPerGroup : tasks;
-    const int64_t chunk = split_t / split_n, rem = split_t % split_n;
-    if (out_format_float_bytes(out_format)) {   // normalised float planes: int16 input, no variants
-        const int lg = scale_log2(scale);
-        const int fi = out_format == HJD_OUT_RGB_PLANAR_F16 ? 0 : 1;
-        if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-        if (fmt != 0) return set_error(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input only");
-        if (variant != 0) return set_error(HJD_E_INVALID, "kernel variants are BGRX-only");
-        if (lg > 0 && !scaled_sampling_ok(sampling))
-            return set_error(HJD_E_INVALID, "scaled decode serves 4:4:4, 4:2:0 and gray, not sampling %d", sampling);
-        if ((roi || lg > 0) && kernel_mode == HJD_KERNEL_LATENCY)
-            return set_error(HJD_E_INVALID, "scaled and ROI decode have no latency kernel");
-#define HJD_KN(S, X) hjd::decode_kernel<S, 0, hjd::kOutPlanar | hjd::kOutF16 | (X)>, \
-                     hjd::decode_kernel<S, 0, hjd::kOutPlanar | hjd::kOutF32 | (X)>
-#define HJD_KN6(X) HJD_KN(0, X), HJD_KN(1, X), HJD_KN(2, X), HJD_KN(3, X), HJD_KN(4, X), HJD_KN(5, X)
-#define HJD_KN3(L, X) HJD_KN(0, ((L) << hjd::kScaleShift) | (X)), HJD_KN(1, ((L) << hjd::kScaleShift) | (X)), \
-                      HJD_KN(3, ((L) << hjd::kScaleShift) | (X))
-        // scale 1: [sampling index][F16, F32]; scaled: [log2 scale - 1][4:4:4, 4:2:0, gray][F16, F32]
-        static const KP kNorm1[12] = {HJD_KN6(0)};
-        static const KP kNormD16[2] = {HJD_KN(0, hjd::kVarD16)};
-        static const KP kNormScaled[18] = {HJD_KN3(1, 0), HJD_KN3(2, 0), HJD_KN3(3, 0)};
-        static const KP kNormRoi1[12] = {HJD_KN6(hjd::kVarRoi)};
-        static const KP kNormRoiScaled[18] = {HJD_KN3(1, hjd::kVarRoi), HJD_KN3(2, hjd::kVarRoi),
-                                              HJD_KN3(3, hjd::kVarRoi)};
-#undef HJD_KN3
-#undef HJD_KN6
-#undef HJD_KN
-        if (!roi && lg == 0 && latency) {
-#define HJD_KNL(S) hjd::decode_kernel_lat<S, 0, hjd::kOutPlanar | hjd::kOutF16>, \
-                   hjd::decode_kernel_lat<S, 0, hjd::kOutPlanar | hjd::kOutF32>
-            static const K kNormLat[12] = {HJD_KNL(0), HJD_KNL(1), HJD_KNL(2), HJD_KNL(3), HJD_KNL(4), HJD_KNL(5)};
-#undef HJD_KNL
-            if (tasks > (int64_t(1) << 31) - 1) return set_error(HJD_E_INVALID, "too many tasks for the latency kernel");
-            hipLaunchKernelGGL(kNormLat[2 * sg.index + fi], dim3(static_cast<uint32_t>(tasks)), dim3(hjd::kLatThreads), 0,
-                               static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
-                               reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out));
-            HJD_HIP(hipGetLastError());
-            return HJD_OK;
-        }
-        const int srow = sampling == HJD_YUV444 ? 0 : sampling == HJD_YUV420 ? 1 : 2;
-        KP k = lg > 0 ? (roi ? kNormRoiScaled : kNormScaled)[6 * (lg - 1) + 2 * srow + fi]
-                      : (roi ? kNormRoi1 : kNorm1)[2 * sg.index + fi];
-        if (!roi && lg == 0 && sampling == HJD_YUV444 && hjd_internal::d16_gather_selected(device)) k = kNormD16[fi];
-        hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream), d_coefs,
-                           d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
-                           static_cast<uint8_t*>(d_out), chunk, rem);
-        HJD_HIP(hipGetLastError());
-        return HJD_OK;
-    }
-    if (roi) {   // ROI decode: the persistent kernel only
-        const int lg = scale_log2(scale);
-        if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-        if (lg > 0 && !scaled_sampling_ok(sampling))
-            return set_error(HJD_E_INVALID, "scaled decode serves 4:4:4, 4:2:0 and gray, not sampling %d", sampling);
-        if (fmt != 0) return set_error(HJD_E_INVALID, "ROI decode takes HJD_IN_Q16_ZIGZAG input only");
-        if (variant != 0) return set_error(HJD_E_INVALID, "ROI decode has no kernel variants");
-        if (kernel_mode == HJD_KERNEL_LATENCY) return set_error(HJD_E_INVALID, "ROI decode has no latency kernel");
-#define HJD_KR1(S, V, L) hjd::decode_kernel<S, 0, (V) | ((L) << hjd::kScaleShift) | hjd::kVarRoi>
-#define HJD_KR4(S, L) HJD_KR1(S, 0, L), HJD_KR1(S, hjd::kOutBgr24, L), HJD_KR1(S, hjd::kOutRgb24, L), \
-                      HJD_KR1(S, hjd::kOutPlanar, L)
-#define HJD_KR(L) HJD_KR4(0, L), HJD_KR4(1, L), HJD_KR4(3, L)
-        // scale 1: [sampling index][output format]; scaled: [log2 scale - 1][4:4:4, 4:2:0, gray][output format]
-        static const KP kRoi1[24] = {HJD_KR4(0, 0), HJD_KR4(1, 0), HJD_KR4(2, 0), HJD_KR4(3, 0), HJD_KR4(4, 0),
-                                     HJD_KR4(5, 0)};
-        static const KP kRoiScaled[36] = {HJD_KR(1), HJD_KR(2), HJD_KR(3)};
-#undef HJD_KR
-#undef HJD_KR4
-#undef HJD_KR1
-        const int srow = sampling == HJD_YUV444 ? 0 : sampling == HJD_YUV420 ? 1 : 2;
-        const KP k = lg == 0 ? kRoi1[4 * sg.index + out_format] : kRoiScaled[12 * (lg - 1) + 4 * srow + out_format];
-        hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream), d_coefs,
-                           d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
-                           static_cast<uint8_t*>(d_out), chunk, rem);
-        HJD_HIP(hipGetLastError());
-        return HJD_OK;
-    }
-    if (scale != 1) {   // scaled decode: the persistent kernel only, [log2 scale - 1][sampling][output format]
-        const int lg = scale_log2(scale);
-        if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-        if (!scaled_sampling_ok(sampling))
-            return set_error(HJD_E_INVALID, "scaled decode serves 4:4:4, 4:2:0 and gray, not sampling %d", sampling);
-        if (fmt != 0) return set_error(HJD_E_INVALID, "scaled decode takes HJD_IN_Q16_ZIGZAG input only");
-        if (variant != 0) return set_error(HJD_E_INVALID, "scaled decode has no kernel variants");
-        if (kernel_mode == HJD_KERNEL_LATENCY)
-            return set_error(HJD_E_INVALID, "scaled decode has no latency kernel");
-#define HJD_KS1(S, V, L) hjd::decode_kernel<S, 0, (V) | ((L) << hjd::kScaleShift)>
-#define HJD_KS4(S, L) HJD_KS1(S, 0, L), HJD_KS1(S, hjd::kOutBgr24, L), HJD_KS1(S, hjd::kOutRgb24, L), \
-                      HJD_KS1(S, hjd::kOutPlanar, L)
-#define HJD_KS(L) HJD_KS4(0, L), HJD_KS4(1, L), HJD_KS4(3, L)
-        static const KP kScaled[36] = {HJD_KS(1), HJD_KS(2), HJD_KS(3)};
-#undef HJD_KS
-#undef HJD_KS4
-#undef HJD_KS1
-        const int srow = sampling == HJD_YUV444 ? 0 : sampling == HJD_YUV420 ? 1 : 2;
-        hipLaunchKernelGGL(kScaled[12 * (lg - 1) + 4 * srow + out_format], dim3(grid), dim3(hjd::kGroupThreads), 0,
-                           static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
-                           reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out),
-                           chunk, rem);
-        HJD_HIP(hipGetLastError());
-        return HJD_OK;
-    }
-    if (latency && (variant >> kStageShift) == 0) {   // [output format][sampling index][input format]
-#define HJD_KL(V) hjd::decode_kernel_lat<0, 0, V>, hjd::decode_kernel_lat<0, 1, V>, \
-                  hjd::decode_kernel_lat<1, 0, V>, hjd::decode_kernel_lat<1, 1, V>, \
-                  hjd::decode_kernel_lat<2, 0, V>, hjd::decode_kernel_lat<2, 1, V>, \
-                  hjd::decode_kernel_lat<3, 0, V>, hjd::decode_kernel_lat<3, 1, V>, \
-                  hjd::decode_kernel_lat<4, 0, V>, hjd::decode_kernel_lat<4, 1, V>, \
-                  hjd::decode_kernel_lat<5, 0, V>, hjd::decode_kernel_lat<5, 1, V>
-        static const K kLat[48] = {HJD_KL(0), HJD_KL(hjd::kOutBgr24), HJD_KL(hjd::kOutRgb24),
-                                   HJD_KL(hjd::kOutPlanar)};
-#undef HJD_KL
-        if (tasks > (int64_t(1) << 31) - 1) return set_error(HJD_E_INVALID, "too many tasks for the latency kernel");
-        const K k = kLat[12 * out_format + ((sg.index << 1) | fmt)];
-        hipLaunchKernelGGL(k, dim3(static_cast<uint32_t>(tasks)), dim3(hjd::kLatThreads), 0,
-                           static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
-                           reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out));
-        HJD_HIP(hipGetLastError());
-        return HJD_OK;
-    }
-    if (out_format != HJD_OUT_BGRX) {   // [output format - 1][sampling index][input format], default variant
-#define HJD_KF(V) hjd::decode_kernel<0, 0, V>, hjd::decode_kernel<0, 1, V>, hjd::decode_kernel<1, 0, V>, \
-                  hjd::decode_kernel<1, 1, V>, hjd::decode_kernel<2, 0, V>, hjd::decode_kernel<2, 1, V>, \
-                  hjd::decode_kernel<3, 0, V>, hjd::decode_kernel<3, 1, V>, hjd::decode_kernel<4, 0, V>, \
-                  hjd::decode_kernel<4, 1, V>, hjd::decode_kernel<5, 0, V>, hjd::decode_kernel<5, 1, V>
-        static const KP kTable24[36] = {HJD_KF(hjd::kOutBgr24), HJD_KF(hjd::kOutRgb24), HJD_KF(hjd::kOutPlanar)};
-#undef HJD_KF
-        static const KP kD16[3] = {hjd::decode_kernel<0, 0, hjd::kOutBgr24 | hjd::kVarD16>,
-                                   hjd::decode_kernel<0, 0, hjd::kOutRgb24 | hjd::kVarD16>,
-                                   hjd::decode_kernel<0, 0, hjd::kOutPlanar | hjd::kVarD16>};
-        if ((variant & 3) != 0) return set_error(HJD_E_INVALID, "kernel variants are BGRX-only");
-        KP k24 = kTable24[12 * (out_format - 1) + ((sg.index << 1) | fmt)];
-        if (sampling == HJD_YUV444 && fmt == 0 && hjd_internal::d16_gather_selected(device)) k24 = kD16[out_format - 1];
-        hipLaunchKernelGGL(k24, dim3(grid), dim3(hjd::kGroupThreads), 0,
-                           static_cast<hipStream_t>(stream), d_coefs, d_qt_nat,
-                           reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks, static_cast<uint8_t*>(d_out),
-                           chunk, rem);
-        HJD_HIP(hipGetLastError());
-        return HJD_OK;
-    }
-    if (fmt == 0 && (variant >> kStageShift) != 0) {   // stage-skipping measurement variants
-        if (sg.index > 1) return hjd_internal::set_error(HJD_E_INVALID, "ablation variants are 4:4:4/4:2:0 only");
+    if (lg < 0) return set_error(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", s.scale);
+    if (s.input_format != HJD_IN_Q16_ZIGZAG && !i32)
+        return set_error(HJD_E_INVALID, "unknown input format %d", s.input_format);
+    if (!whole && i32)
+        return set_error(HJD_E_INVALID, "scaled and ROI decode take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
+    if (!out_format_bytes(s.out_format)) return set_error(HJD_E_INVALID, "unknown output format %d", s.out_format);
+    if (out_format_float_bytes(s.out_format) && i32)
+        return set_error(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
+    if (!sampling_geom(s.sampling, &sg))
+        return set_error(HJD_E_INVALID, "unsupported sampling %d (4:4:4, 4:2:0, 4:2:2, gray, 4:1:1 or 4:4:0)",
+                         s.sampling);
+    if (lg > 0 && !scaled_sampling_ok(s.sampling))
+        return set_error(HJD_E_INVALID,
+                         "scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not 4:2:2, 4:1:1 or 4:4:0 (sampling %d)",
+                         s.scale, s.sampling);
+    if (s.variant < 0 || s.variant > 3) return set_error(HJD_E_INVALID, "unknown kernel variant %d", s.variant);
+    // the latency kernels ignore the variant bits, so a byte format passes with them where the launch takes one
+    if (s.variant != 0 && s.out_format != HJD_OUT_BGRX && (out_format_float_bytes(s.out_format) || !takes_latency(s)))
+        return set_error(HJD_E_INVALID, "kernel variants are BGRX-only");
+    if (s.variant != 0 && !whole) return set_error(HJD_E_INVALID, "scaled and ROI decode have no kernel variants");
+    if (s.kernel_mode != HJD_KERNEL_AUTO && s.kernel_mode != HJD_KERNEL_PERSISTENT && s.kernel_mode != HJD_KERNEL_LATENCY)
+        return set_error(HJD_E_INVALID, "unknown kernel mode %d", s.kernel_mode);
+    if (s.kernel_mode == HJD_KERNEL_LATENCY && !whole)
+        return set_error(HJD_E_INVALID, "scaled and ROI decode have no latency kernel");
+    if (s.stages != 0) {   // the stage-skipping measurement variants
         constexpr int kStages[8] = {4, 8, 16, 20, 24, 64, 80, 256};
-        const int stages = variant >> kStageShift;
-        int si = -1;
-        for (int i = 0; i < 8; ++i)
-            if (kStages[i] == stages) si = i;
-        if (si < 0) return hjd_internal::set_error(HJD_E_INVALID, "unknown ablation variant %d", stages);
-#define HJD_ST(S, B) {hjd::decode_kernel<S, 0, 4 | (B)>, hjd::decode_kernel<S, 0, 8 | (B)>,                  \
-                      hjd::decode_kernel<S, 0, 16 | (B)>, hjd::decode_kernel<S, 0, 20 | (B)>,                \
-                      hjd::decode_kernel<S, 0, 24 | (B)>, hjd::decode_kernel<S, 0, 64 | (B)>,                \
-                      hjd::decode_kernel<S, 0, 80 | (B)>, hjd::decode_kernel<S, 0, 256 | (B)>}
-        // [4:2:0, 4:4:4, 4:4:4 d16 gather][stages]
-        static const KP kStageK[3][8] = {HJD_ST(1, 0), HJD_ST(0, 0), HJD_ST(0, hjd::kVarD16)};
-#undef HJD_ST
-        const int col = sampling == HJD_YUV420 ? 0 : hjd_internal::d16_gather_selected(device) ? 2 : 1;   // as the product gathers
-        const KP k = kStageK[col][si];
-        hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream), d_coefs,
-                           d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
-                           static_cast<uint8_t*>(d_out), chunk, rem);
-        HJD_HIP(hipGetLastError());
-        return HJD_OK;
+        if (std::find(kStages, kStages + 8, s.stages) == kStages + 8)
+            return set_error(HJD_E_INVALID, "unknown stage variant %d", s.stages);
+        if (!whole) return set_error(HJD_E_INVALID, "stage variants are not built for scaled and ROI plans");
+        if (i32 || s.out_format != HJD_OUT_BGRX || sg.index > 1 || s.variant != 0)
+            return set_error(HJD_E_INVALID, "stage variants: 4:2:0 / 4:4:4, int16 zigzag in, BGRX out, variant 0");
     }
-    // [sampling index][input format][variant bits 0-1]
-    const int key = (sg.index << 3) | (fmt << 2) | (variant & 3);
-#define HJD_K4(S, F) hjd::decode_kernel<S, F, 0>, hjd::decode_kernel<S, F, 1>, hjd::decode_kernel<S, F, 2>, \
-                     hjd::decode_kernel<S, F, 3>
-    static const KP kTable[48] = {HJD_K4(0, 0), HJD_K4(0, 1), HJD_K4(1, 0), HJD_K4(1, 1),
-                                 HJD_K4(2, 0), HJD_K4(2, 1), HJD_K4(3, 0), HJD_K4(3, 1),
-                                 HJD_K4(4, 0), HJD_K4(4, 1), HJD_K4(5, 0), HJD_K4(5, 1)};
-#undef HJD_K4
-    KP k = kTable[key];
-    if (sampling == HJD_YUV444 && fmt == 0 && (variant & 2) == 0 && hjd_internal::d16_gather_selected(device))
-        k = (variant & 1) ? hjd::decode_kernel<0, 0, hjd::kVarPlainStores | hjd::kVarD16>
-                          : hjd::decode_kernel<0, 0, hjd::kVarD16>;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(hjd::kGroupThreads), 0, static_cast<hipStream_t>(stream),
-                       d_coefs, d_qt_nat, reinterpret_cast<const FrameDev*>(d_frames), nframes, tasks,
-                       static_cast<uint8_t*>(d_out), chunk, rem);
+    return HJD_OK;
+}
+
+namespace {
+
+// The kernels' variant bits of each output format, beside hjd_internal::kOutFormats.
+constexpr int kOutKernelBits[] = {0,  hjd::kOutBgr24, hjd::kOutRgb24, hjd::kOutPlanar,
+                                  -1, hjd::kOutPlanar | hjd::kOutF16, hjd::kOutPlanar | hjd::kOutF32};
+static_assert(sizeof(kOutKernelBits) / sizeof(int) == hjd_internal::kOutFormatRows, "one entry per HJD_OUT_* value");
+
+using KLat = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*);
+using KPer = void (*)(const void*, const int*, const FrameDev*, int, int64_t, uint8_t*, int64_t, int64_t);
+struct KernelEntry {
+    int key[4];   // latency, S, F, V: decode_kernel_lat<S, F, V> or decode_kernel<S, F, V>
+    KLat lat;
+    KPer per;
+    bool operator<(const KernelEntry& o) const { return std::lexicographical_compare(key, key + 4, o.key, o.key + 4); }
+};
+
+// Every pixel kernel of the library, named once.  P / L make a persistent / a
+// latency entry whose key is the template arguments its pointer is taken with.
+#define P(S, F, V) {{0, S, F, (V)}, nullptr, hjd::decode_kernel<S, F, (V)>},
+#define L(S, F, V) {{1, S, F, (V)}, hjd::decode_kernel_lat<S, F, (V)>, nullptr},
+#define ALL6(M, F, V) M(0, F, V) M(1, F, V) M(2, F, V) M(3, F, V) M(4, F, V) M(5, F, V)
+#define SCALED1(M, V) M(0, 0, V) M(1, 0, V) M(3, 0, V)   // 4:4:4, 4:2:0 and gray
+#define SCALED(V) SCALED1(P, (V) | (1 << hjd::kScaleShift)) SCALED1(P, (V) | (2 << hjd::kScaleShift)) \
+                  SCALED1(P, (V) | (3 << hjd::kScaleShift))
+// One output format (bits O) with int16 input: whole frames, persistent (its
+// 4:4:4 d16 twin) and latency; scaled; ROI at scale 1 and scaled.  37 kernels.
+#define FORMAT(O) ALL6(P, 0, O) P(0, 0, (O) | hjd::kVarD16) ALL6(L, 0, O) SCALED(O) ALL6(P, 0, (O) | hjd::kVarRoi) \
+                  SCALED((O) | hjd::kVarRoi)
+#define FORMAT_I32(O) ALL6(P, 1, O) ALL6(L, 1, O)   // int32 input: whole frames only.  12 kernels.
+#define STAGES(S, D) P(S, 0, 4 | (D)) P(S, 0, 8 | (D)) P(S, 0, 16 | (D)) P(S, 0, 20 | (D)) P(S, 0, 24 | (D)) \
+                     P(S, 0, 64 | (D)) P(S, 0, 80 | (D)) P(S, 0, 256 | (D))
+const KernelEntry kKernelList[] = {
+    FORMAT(0) FORMAT(hjd::kOutBgr24) FORMAT(hjd::kOutRgb24) FORMAT(hjd::kOutPlanar)
+    FORMAT(hjd::kOutPlanar | hjd::kOutF16) FORMAT(hjd::kOutPlanar | hjd::kOutF32)
+    FORMAT_I32(0) FORMAT_I32(hjd::kOutBgr24) FORMAT_I32(hjd::kOutRgb24) FORMAT_I32(hjd::kOutPlanar)
+    // BGRX kernel variants (hjd_plan_set_variant), both inputs; the d16 twin keeps the store bit
+    ALL6(P, 0, 1) ALL6(P, 0, 2) ALL6(P, 0, 3) ALL6(P, 1, 1) ALL6(P, 1, 2) ALL6(P, 1, 3)
+    P(0, 0, hjd::kVarPlainStores | hjd::kVarD16)
+    // stage-skipping measurement variants: 4:2:0, 4:4:4 and its d16 twin
+    STAGES(1, 0) STAGES(0, 0) STAGES(0, hjd::kVarD16)
+};
+#undef STAGES
+#undef FORMAT_I32
+#undef FORMAT
+#undef SCALED
+#undef SCALED1
+#undef ALL6
+#undef L
+#undef P
+constexpr int kKernels = sizeof(kKernelList) / sizeof(kKernelList[0]);
+static_assert(kKernels == 6 * 37 + 4 * 12 + 37 + 24, "331 pixel kernels");
+
+// The table sorted by key (once, at its first use).
+const KernelEntry* kernel_table()
+{
+    static const std::vector<KernelEntry> sorted = [] {
+        std::vector<KernelEntry> t(kKernelList, kKernelList + kKernels);
+        std::sort(t.begin(), t.end());
+        return t;
+    }();
+    return sorted.data();
+}
+
+// The table entry a shape takes (HJD_OK), or HJD_E_INVALID.  d16: whether the
+// 4:4:4 kernels gather with d16 loads; < 0: as d16_gather_selected(device) says.
+int select_kernel(const DecodeShape& s, int d16, int device, const KernelEntry** out)
+{
+    int rc = hjd_internal::shape_check(s);
+    if (rc) return rc;
+    SamplingGeom sg;
+    sampling_geom(s.sampling, &sg);
+    KernelEntry want = {{takes_latency(s), sg.index, s.input_format == HJD_IN_Q16_ZIGZAG ? 0 : 1,
+                         kOutKernelBits[s.out_format]}, nullptr, nullptr};
+    int& V = want.key[3];
+    if (want.key[0]) {   // the latency kernels have no variants: bits 0-1 are ignored
+        if (s.tasks > INT32_MAX) return hjd_internal::set_error(HJD_E_INVALID, "too many tasks for the latency kernel");
+    } else {
+        V |= (hjd_internal::scale_log2(s.scale) << hjd::kScaleShift) | (s.roi ? hjd::kVarRoi : 0) | s.variant | s.stages;
+        // the d16 twin: 4:4:4 whole frames from int16 input, contiguous task order
+        if (s.sampling == HJD_YUV444 && want.key[2] == 0 && s.scale == 1 && !s.roi &&
+            (s.variant & hjd::kVarWgInterleave) == 0 && (d16 < 0 ? hjd_internal::d16_gather_selected(device) : d16 != 0))
+            V |= hjd::kVarD16;
+    }
+    const KernelEntry* t = kernel_table();
+    const KernelEntry* e = std::lower_bound(t, t + kKernels, want);
+    if (e == t + kKernels || want < *e)
+        return hjd_internal::set_error(HJD_E_INVALID,
+                                       "no %s kernel <%d, %d, %d> for sampling %d, input format %d, output format %d, "
+                                       "scale %d, roi %d, variant %d, stages %d",
+                                       want.key[0] ? "latency" : "persistent", want.key[1], want.key[2], V, s.sampling,
+                                       s.input_format, s.out_format, s.scale, s.roi, s.variant, s.stages);
+    *out = e;
+    return HJD_OK;
+}
+
+}  // namespace
+
+int hjd_internal::launch_decode(const DecodeLaunch& l)
+{
+    HJD_HIP(hipSetDevice(l.device));
+    const KernelEntry* k;
+    int rc = select_kernel(l, -1, l.device, &k);
+    if (rc) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(l.stream);
+    const FrameDev* frames = reinterpret_cast<const FrameDev*>(l.d_frames);
+    uint8_t* out = static_cast<uint8_t*>(l.d_out);
+    if (k->lat) {
+        hipLaunchKernelGGL(k->lat, dim3(static_cast<uint32_t>(l.tasks)), dim3(hjd::kLatThreads), 0, stream, l.d_coefs,
+                           l.d_qt_nat, frames, l.nframes, l.tasks, out);
+    } else {
+        const int fmt = k->key[2];
+        const int grid = l.grid_blocks > 0 ? l.grid_blocks : grid_for_chunk(l.tasks, default_per_wave(l.sampling, fmt));
+        // the task split of the persistent kernels (see decode_kernel): default
+        // order over grid * 4 waves, wg-interleave over grid groups of 4-task quads
+        const bool quads = (l.variant & hjd::kVarWgInterleave) != 0;
+        const int64_t split_n = quads ? static_cast<int64_t>(grid) : static_cast<int64_t>(grid) * hjd::kWavesPerGroup;
+        const int64_t split_t = quads ? (l.tasks + hjd::kWavesPerGroup - 1) / hjd::kWavesPerGroup : l.tasks;
+        hipLaunchKernelGGL(k->per, dim3(grid), dim3(hjd::kGroupThreads), 0, stream, l.d_coefs, l.d_qt_nat, frames,
+                           l.nframes, l.tasks, out, split_t / split_n, split_t % split_n);
+    }
     HJD_HIP(hipGetLastError());
     return HJD_OK;
 }
@@ -626,7 +609,8 @@ int hjd_frame_blocks(int width, int height, int sampling, int64_t* nblocks)
 
 int hjd_scaled_size(int width, int height, int scale, int* out_w, int* out_h)
 {
-    if (hjd_internal::scale_log2(scale) < 0) return fail(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
+    int rc = hjd_internal::shape_check(make_shape(HJD_YUV420, scale));
+    if (rc) return rc;
     if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
         return fail(HJD_E_INVALID, "invalid dimensions %dx%d", width, height);
     if (!out_w || !out_h) return fail(HJD_E_INVALID, "out_w or out_h is NULL");
@@ -646,50 +630,47 @@ int hjd_roi_geometry(int width, int height, int sampling, int scale, const hjd_r
     return HJD_OK;
 }
 
-// One frame's geometry and output layout, as a plan of `scale` (and ROIs)
-// takes it: sw x sh is what the frame writes (the ROI's size, else the scaled
-// frame's), rg the ROI's geometry.  i: the frame's index, for the message.
-static int check_frame(const hjd_frame& f, int input_format, int scale, const hjd_rect* roi, int i,
-                       hjd_internal::RoiGeom* rg, int* sw, int* sh)
+// One frame of a plan of the checked shape `s` whose first frame is `first`:
+// valid dimensions, the plan's sampling and output format, a sampling the
+// shape serves, a valid rectangle, and a pitch and offset that fit what the
+// frame writes (the ROI's size, else the scaled frame's).  pixels, blocks:
+// what it writes and reads.  i: the frame's index, for the message.
+static int check_frame(const hjd_frame& f, const hjd_frame& first, DecodeShape s, const hjd_rect* roi,
+                       int i, int64_t* pixels, int64_t* blocks)
 {
     int mw, mh, bpm, tasks_mcus;
     int rc = geometry(f.width, f.height, f.sampling, mw, mh, bpm, tasks_mcus);
     if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
-    const int rbytes = hjd_internal::out_format_row_bytes(f.out_format);
-    if (!rbytes) return fail(HJD_E_INVALID, "unknown output format %d", f.out_format);
-    if (hjd_internal::out_format_float_bytes(f.out_format) && input_format != HJD_IN_Q16_ZIGZAG)
-        return fail(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
-    if (scale > 1 && !hjd_internal::scaled_sampling_ok(f.sampling))
-        return fail(HJD_E_INVALID,
-                    "frame %d: scaled decode (scale %d) serves 4:4:4, 4:2:0 and gray, not 4:2:2, 4:1:1 or 4:4:0 "
-                    "(sampling %d)", i, scale, f.sampling);
-    *sw = hjd_internal::scaled_dim(f.width, scale);
-    *sh = hjd_internal::scaled_dim(f.height, scale);
-    if (roi) {   // the output is the ROI: pitch and payload refer to it
-        rc = hjd_internal::roi_geom(f.width, f.height, f.sampling, scale, roi, rg);
-        if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
-        *sw = roi->w;
-        *sh = roi->h;
-    }
-    // BGRX / BGR24: 4-byte pitches and offsets; the RGB formats take any; the
-    // float planes multiples of their element size
+    if (f.sampling != first.sampling)
+        return fail(HJD_E_INVALID, "frame %d: mixed sampling in one plan (use one plan per sampling)", i);
+    if (f.out_format != first.out_format)
+        return fail(HJD_E_INVALID, "frame %d: mixed output formats in one plan (use one plan per format)", i);
+    hjd_internal::RoiGeom rg;
+    s.sampling = f.sampling;
+    rc = hjd_internal::shape_check(s);
+    if (!rc && roi) rc = hjd_internal::roi_geom(f.width, f.height, f.sampling, s.scale, roi, &rg);
+    if (rc) return fail(rc, "frame %d: %s", i, std::string(g_last_error).c_str());
+    // the output is the ROI where there is one: pitch and payload refer to it
+    const int sw = roi ? roi->w : hjd_internal::scaled_dim(f.width, s.scale);
+    const int sh = roi ? roi->h : hjd_internal::scaled_dim(f.height, s.scale);
     const uint64_t amask = static_cast<uint64_t>(hjd_internal::out_format_pitch_mask(f.out_format));
-    if (f.out_pitch < static_cast<int64_t>(rbytes) * *sw || (f.out_pitch & amask) || (f.out_offset & amask))
+    if (f.out_pitch < static_cast<int64_t>(hjd_internal::out_format_row_bytes(f.out_format)) * sw ||
+        (f.out_pitch & amask) || (f.out_offset & amask))
         return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
+    *pixels = static_cast<int64_t>(sw) * sh;
+    *blocks = roi ? rg.blocks : static_cast<int64_t>(mw) * mh * bpm;
     return HJD_OK;
 }
 
 int hjd_frame_check(const hjd_frame* frame, int input_format, int scale, const hjd_rect* roi)
 {
     if (!frame) return fail(HJD_E_INVALID, "frame is NULL");
-    if (hjd_internal::scale_log2(scale) < 0) return fail(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-    if (input_format != HJD_IN_Q16_ZIGZAG && input_format != HJD_IN_I32_NATURAL)
-        return fail(HJD_E_INVALID, "unknown input format %d", input_format);
-    if ((scale > 1 || roi) && input_format == HJD_IN_I32_NATURAL)
-        return fail(HJD_E_INVALID, "scaled and ROI decode take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
-    hjd_internal::RoiGeom rg;
-    int sw, sh;
-    return check_frame(*frame, input_format, scale, roi, 0, &rg, &sw, &sh);
+    // the plan's rules first, on 4:2:0, which every shape serves; check_frame adds the frame's sampling
+    const DecodeShape shape = make_shape(HJD_YUV420, scale, input_format, frame->out_format, roi != nullptr);
+    int rc = hjd_internal::shape_check(shape);
+    if (rc) return rc;
+    int64_t pixels, blocks;
+    return check_frame(*frame, *frame, shape, roi, 0, &pixels, &blocks);
 }
 
 int hjd_plan_create(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int input_format,
@@ -710,64 +691,35 @@ int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int 
     if (!ctx || !out || (!frames && nframes > 0) || nframes < 0)
         return fail(HJD_E_INVALID, "invalid plan arguments");
     *out = nullptr;
-    if (hjd_internal::scale_log2(scale) < 0) return fail(HJD_E_INVALID, "scale %d is not 1, 2, 4 or 8", scale);
-    if (scale > 1 && input_format == HJD_IN_I32_NATURAL)
-        return fail(HJD_E_INVALID, "scaled decode (scale %d) takes HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL", scale);
-    if (input_format != HJD_IN_Q16_ZIGZAG && input_format != HJD_IN_I32_NATURAL)
-        return fail(HJD_E_INVALID, "unknown input format %d", input_format);
-    if (rois && input_format == HJD_IN_I32_NATURAL)
-        return fail(HJD_E_INVALID, "ROI decode takes HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
-    if (input_format == HJD_IN_Q16_ZIGZAG && (!qtables || nq <= 0))
-        return fail(HJD_E_INVALID, "quantisation tables required for HJD_IN_Q16_ZIGZAG");
-
-    std::vector<FrameDev> fd(static_cast<size_t>(std::max(nframes, 1)));
-    std::vector<hjd_internal::RoiRecord> sides(rois ? fd.size() : 0);
-    int64_t tasks = 0, pixels = 0, blocks = 0;
+    const bool q16 = input_format == HJD_IN_Q16_ZIGZAG;
     int sampling = nframes > 0 ? frames[0].sampling : HJD_YUV420;
     const int out_format = nframes > 0 ? frames[0].out_format : HJD_OUT_BGRX;
-    const int obytes = hjd_internal::out_format_bytes(out_format);
-    if (!obytes) return fail(HJD_E_INVALID, "unknown output format %d", out_format);
-    if (hjd_internal::out_format_float_bytes(out_format) && input_format != HJD_IN_Q16_ZIGZAG)
-        return fail(HJD_E_INVALID, "the float output formats take HJD_IN_Q16_ZIGZAG input, not HJD_IN_I32_NATURAL");
+    // the plan's rules first, on 4:2:0, which every shape serves; check_frame adds each frame's sampling
+    const DecodeShape shape = make_shape(HJD_YUV420, scale, input_format, out_format, rois != nullptr);
+    int rc = hjd_internal::shape_check(shape);
+    if (rc) return rc;
+    if (q16 && (!qtables || nq <= 0)) return fail(HJD_E_INVALID, "quantisation tables required for HJD_IN_Q16_ZIGZAG");
+
+    std::vector<hjd_internal::FrameRecord> fd(static_cast<size_t>(std::max(nframes, 1)));
+    std::vector<hjd_internal::RoiRecord> sides(rois ? fd.size() : 0);
+    int64_t tasks = 0, pixels = 0, blocks = 0;
     for (int i = 0; i < nframes; ++i) {
         const hjd_frame& f = frames[i];
-        int mw, mh, bpm, tasks_mcus;
-        int rc = geometry(f.width, f.height, f.sampling, mw, mh, bpm, tasks_mcus);
-        if (rc) return fail(rc, "frame %d: %s", i, g_last_error.c_str());
-        if (f.sampling != sampling)
-            return fail(HJD_E_INVALID, "frame %d: mixed sampling in one plan (use one plan per sampling)", i);
-        if (f.out_format != out_format)
-            return fail(HJD_E_INVALID, "frame %d: mixed output formats in one plan (use one plan per format)", i);
-        int sw, sh;
-        hjd_internal::RoiGeom rg;
-        rc = check_frame(f, input_format, scale, rois ? &rois[i] : nullptr, i, &rg, &sw, &sh);
+        int64_t fpixels, fblocks;
+        rc = check_frame(f, frames[0], shape, rois ? &rois[i] : nullptr, i, &fpixels, &fblocks);
         if (rc) return rc;
-        FrameDev& d = fd[i];
-        if (input_format == HJD_IN_Q16_ZIGZAG) {
-            for (int c = 0; c < 3; ++c)
-                if (f.qt_index[c] < 0 || f.qt_index[c] >= nq)
-                    return fail(HJD_E_INVALID, "frame %d: qt_index[%d]=%d out of range", i, c, f.qt_index[c]);
-        }
-        d.coef_base = static_cast<int64_t>(f.coef_offset);
-        d.out_base = static_cast<int64_t>(f.out_offset);
-        d.task_begin = tasks;
-        d.width = sw;
-        d.height = sh;
-        d.pitch = f.out_pitch;
-        d.sampling = f.sampling;
-        d.mcu_w = mw;
-        d.strips = (mw + tasks_mcus - 1) / tasks_mcus;
-        for (int c = 0; c < 3; ++c) d.qt[c] = input_format == HJD_IN_Q16_ZIGZAG ? f.qt_index[c] : 0;
-        d.vec_ok = hjd_internal::out_vector_ok(out_format, f.out_pitch, static_cast<int64_t>(f.out_offset)) ? 1 : 0;
-        if (rois) {
-            apply_roi(d, sides[i], rg, rois[i], out_format, 0);
-            tasks += rg.tasks;
-            blocks += rg.blocks;
-        } else {
-            tasks += static_cast<int64_t>(d.strips) * mh;
-            blocks += static_cast<int64_t>(mw) * mh * bpm;
-        }
-        pixels += static_cast<int64_t>(sw) * sh;
+        for (int c = 0; q16 && c < 3; ++c)
+            if (f.qt_index[c] < 0 || f.qt_index[c] >= nq)
+                return fail(HJD_E_INVALID, "frame %d: qt_index[%d]=%d out of range", i, c, f.qt_index[c]);
+        const int64_t t = hjd_internal::make_frame_record(
+            f.width, f.height, f.sampling, static_cast<int64_t>(f.coef_offset), static_cast<int64_t>(f.out_offset),
+            f.out_pitch, q16 ? f.qt_index : nullptr, &fd[i], out_format, 0, scale, rois ? &rois[i] : nullptr,
+            rois ? &sides[i] : nullptr);
+        if (t < 0) return static_cast<int>(t);
+        fd[i].task_begin = tasks;
+        tasks += t;
+        pixels += fpixels;
+        blocks += fblocks;
     }
 
     HJD_HIP(hipSetDevice(ctx->device));
@@ -830,16 +782,37 @@ int hjd_plan_destroy(hjd_plan* plan)
     return HJD_OK;
 }
 
+// A launch of this plan, without the caller's buffers: its shape with the
+// default grid, its device and its tables.
+static hjd_internal::DecodeLaunch plan_launch(const hjd_plan* p)
+{
+    hjd_internal::DecodeLaunch l;
+    l.sampling = p->sampling;
+    l.input_format = p->input_format;
+    l.out_format = p->out_format;
+    l.scale = p->scale;
+    l.roi = p->roi != 0;
+    l.variant = p->variant;
+    l.kernel_mode = p->kernel_mode;
+    l.tasks = p->tasks;
+    l.device = p->ctx->device;
+    l.d_qt_nat = p->d_qt;
+    l.d_frames = reinterpret_cast<const hjd_internal::FrameRecord*>(p->d_frames);
+    l.nframes = p->nframes;
+    return l;
+}
+
 int hjd_plan_set_variant(hjd_plan* plan, int variant)
 {
     if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
-    if (variant < 0 || variant > 3) return fail(HJD_E_INVALID, "unknown kernel variant %d", variant);
-    if (variant != 0 && (hjd_internal::out_format_any_alignment(plan->out_format) ||
-                         hjd_internal::out_format_float_bytes(plan->out_format)))
-        return fail(HJD_E_INVALID, "kernel variants are BGRX-only");
-    if (variant != 0 && plan->scale != 1)
-        return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no kernel variants", plan->scale);
-    if (variant != 0 && plan->roi) return fail(HJD_E_INVALID, "a ROI plan has no kernel variants");
+    hjd_internal::DecodeLaunch l = plan_launch(plan);
+    l.variant = variant;
+    // The bits must suit the plan's persistent kernel, whichever kernel its launches take; as
+    // documented (hjd.h), a BGR24 plan takes them like a BGRX one and fails at a persistent launch.
+    l.kernel_mode = HJD_KERNEL_PERSISTENT;
+    if (l.out_format == HJD_OUT_BGR24) l.out_format = HJD_OUT_BGRX;
+    int rc = hjd_internal::shape_check(l);
+    if (rc) return rc;
     plan->variant = variant;
     return HJD_OK;
 }
@@ -876,11 +849,11 @@ int hjd_plan_set_chunk(hjd_plan* plan, int tasks)
 int hjd_plan_set_kernel(hjd_plan* plan, int mode)
 {
     if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
-    if (mode != HJD_KERNEL_AUTO && mode != HJD_KERNEL_PERSISTENT && mode != HJD_KERNEL_LATENCY)
-        return fail(HJD_E_INVALID, "unknown kernel mode %d", mode);
-    if (mode == HJD_KERNEL_LATENCY && plan->scale != 1)
-        return fail(HJD_E_INVALID, "a scaled plan (scale %d) has no latency kernel", plan->scale);
-    if (mode == HJD_KERNEL_LATENCY && plan->roi) return fail(HJD_E_INVALID, "a ROI plan has no latency kernel");
+    hjd_internal::DecodeLaunch l = plan_launch(plan);
+    l.kernel_mode = mode;
+    l.variant = 0;   // the mode alone: a BGR24 plan's variant bits fail at its persistent launches (hjd.h)
+    int rc = hjd_internal::shape_check(l);
+    if (rc) return rc;
     plan->kernel_mode = mode;
     return HJD_OK;
 }
@@ -933,11 +906,7 @@ static int grid_for_chunk(int64_t tasks, int64_t per_wave, bool occupancy_floor)
 }
 
 // A default launch of this plan takes the persistent kernel (not the latency one).
-static bool plan_is_persistent(const hjd_plan* p)
-{
-    return p->kernel_mode == HJD_KERNEL_PERSISTENT || p->scale != 1 || p->roi ||   // scaled / ROI: no latency kernel
-           (p->kernel_mode == HJD_KERNEL_AUTO && p->tasks > latency_max_tasks());
-}
+static bool plan_is_persistent(const hjd_plan* p) { return !takes_latency(plan_launch(p)); }
 
 static int default_grid(const hjd_ctx* ctx, int64_t work_waves)
 {
@@ -957,12 +926,12 @@ int hjd_plan_launch(hjd_plan* plan, const void* d_coefs, void* d_out, void* stre
     // hjd_plan_autotune's / hjd_plan_set_chunk's chunk, for plans that take the
     // persistent kernel anyway (a small AUTO plan keeps the latency kernel)
     if (grid_blocks == 0 && plan->tuned_grid > 0 && plan_is_persistent(plan)) grid_blocks = plan->tuned_grid;
-    return hjd_internal::launch_decode(plan->ctx->device, plan->ctx->num_cu, plan->sampling, plan->input_format,
-                                       plan->variant, d_coefs, plan->d_qt,
-                                       reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
-                                       plan->nframes, plan->tasks, d_out, stream, grid_blocks, plan->out_format,
-                                       plan->scale != 1 || plan->roi ? HJD_KERNEL_PERSISTENT : plan->kernel_mode,
-                                       plan->scale, plan->roi != 0);
+    hjd_internal::DecodeLaunch l = plan_launch(plan);
+    l.d_coefs = d_coefs;
+    l.d_out = d_out;
+    l.stream = stream;
+    l.grid_blocks = grid_blocks;
+    return hjd_internal::launch_decode(l);
 }
 
 // The fused kernel's launch adapted to the device it runs on (VERDICT r3:
@@ -1064,14 +1033,16 @@ int hjd_plan_autotune(hjd_plan* plan, const void* d_coefs, void* d_out, void* st
     int rc = HJD_OK;
     for (int r = 0; r < rounds && rc == HJD_OK; ++r) {
         for (Cand& c : cands) {
-            const int v = keep | c.store;
+            hjd_internal::DecodeLaunch l = plan_launch(plan);
+            l.variant = keep | c.store;
+            l.kernel_mode = HJD_KERNEL_PERSISTENT;
+            l.grid_blocks = c.grid;
+            l.d_coefs = d_coefs;
+            l.d_out = d_out;
+            l.stream = s;
             auto go = [&]() {
                 plan->autotune_launches++;
-                return hjd_internal::launch_decode(plan->ctx->device, plan->ctx->num_cu, plan->sampling,
-                                                   plan->input_format, v, d_coefs, plan->d_qt,
-                                                   reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
-                                                   plan->nframes, plan->tasks, d_out, s, c.grid, plan->out_format,
-                                                   HJD_KERNEL_PERSISTENT, plan->scale, plan->roi != 0);
+                return hjd_internal::launch_decode(l);
             };
             float ms = 0;
             if ((rc = go()) || (rc = hipEventRecord(e0, s) == hipSuccess ? HJD_OK : HJD_E_HIP) || (rc = go()) ||
@@ -1136,24 +1107,46 @@ int hjd_debug_plan_launch_stages(hjd_plan* plan, int stages, const void* d_coefs
                                  int grid_blocks)
 {
     if (!plan) return fail(HJD_E_INVALID, "plan is NULL");
-    if (stages != 4 && stages != 16 && stages != 20 && stages != 64 && stages != 80 && stages != 8 && stages != 24 &&
-        stages != 256)
-        return fail(HJD_E_INVALID, "unknown stage variant %d", stages);
-    if (plan->scale != 1)
-        return fail(HJD_E_INVALID, "stage variants are not built for scaled plans (scale %d)", plan->scale);
-    if (plan->roi) return fail(HJD_E_INVALID, "stage variants are not built for ROI plans");
-    if (plan->input_format != HJD_IN_Q16_ZIGZAG || plan->out_format != HJD_OUT_BGRX ||
-        (plan->sampling != HJD_YUV420 && plan->sampling != HJD_YUV444))
-        return fail(HJD_E_INVALID, "stage variants: 4:2:0 / 4:4:4, int16 zigzag in, BGRX out");
+    hjd_internal::DecodeLaunch l = plan_launch(plan);
+    l.variant = 0;
+    l.stages = stages;
+    l.kernel_mode = HJD_KERNEL_PERSISTENT;
+    int rc = hjd_internal::shape_check(l);
+    if (rc) return rc;
     if (plan->tasks == 0) return HJD_OK;
     if (!d_coefs || !d_out || ((reinterpret_cast<uintptr_t>(d_coefs) | reinterpret_cast<uintptr_t>(d_out)) & 15))
         return fail(HJD_E_INVALID, "NULL or unaligned device buffer");
-    return hjd_internal::launch_decode(plan->ctx->device, plan->ctx->num_cu, plan->sampling, plan->input_format,
-                                       stages << kStageShift, d_coefs, plan->d_qt,
-                                       reinterpret_cast<const hjd_internal::FrameRecord*>(plan->d_frames),
-                                       plan->nframes, plan->tasks, d_out, stream,
-                                       grid_blocks > 0 ? grid_blocks : plan->tuned_grid,
-                                       plan->out_format, HJD_KERNEL_PERSISTENT);
+    l.d_coefs = d_coefs;
+    l.d_out = d_out;
+    l.stream = stream;
+    l.grid_blocks = grid_blocks > 0 ? grid_blocks : plan->tuned_grid;
+    return hjd_internal::launch_decode(l);
+}
+
+// The table entry a shape takes, without a device: d16 stands for the probe's
+// answer.  key: {latency, S, F, V}, the template arguments of the entry found.
+int hjd_debug_kernel_key(int sampling, int input_format, int out_format, int scale, int roi, int variant, int stages,
+                         int kernel_mode, int64_t tasks, int grid_blocks, int d16, int32_t key[4])
+{
+    if (!key) return fail(HJD_E_INVALID, "key is NULL");
+    DecodeShape s = make_shape(sampling, scale, input_format, out_format, roi != 0);
+    s.variant = variant;
+    s.stages = stages;
+    s.kernel_mode = kernel_mode;
+    s.tasks = tasks;
+    s.grid_blocks = grid_blocks;
+    const KernelEntry* k;
+    int rc = select_kernel(s, d16 != 0, -1, &k);
+    if (rc) return rc;
+    std::copy(k->key, k->key + 4, key);
+    return HJD_OK;
+}
+
+// The keys of the table, four ints each (at most `cap` entries are written); returns their count.
+int hjd_debug_kernel_table(int32_t* keys, int cap)
+{
+    for (int i = 0; keys && i < std::min(cap, kKernels); ++i) std::copy(kKernelList[i].key, kKernelList[i].key + 4, keys + 4 * i);
+    return kKernels;
 }
 
 int hjd_idct_blocks(hjd_ctx* ctx, const int32_t* d_in, int32_t* d_out, int64_t nblocks, void* stream)

@@ -168,10 +168,18 @@ int hjd_stream::issue(const Job& job, int rc, const hjd_jpeg_info& info)
     if (e == hipSuccess && work) e = hipEventRecord(t_k0[t], compute);
     int lrc = HJD_OK;
     if (e == hipSuccess && work) {
-        lrc = hjd_internal::launch_decode(device, num_cu, info.sampling, HJD_IN_Q16_ZIGZAG, 0, dev[s] + kHeader,
-                                          reinterpret_cast<const int32_t*>(dev[s] + kQtOffset),
-                                          reinterpret_cast<const FrameRecord*>(dev[s]), 1, tasks, job.d_out,
-                                          compute, 0, job.out_format);
+        hjd_internal::DecodeLaunch l;   // int16 input, HJD_KERNEL_AUTO, the default grid
+        l.sampling = info.sampling;
+        l.out_format = job.out_format;
+        l.tasks = tasks;
+        l.device = device;
+        l.d_coefs = dev[s] + kHeader;
+        l.d_qt_nat = reinterpret_cast<const int32_t*>(dev[s] + kQtOffset);
+        l.d_frames = reinterpret_cast<const FrameRecord*>(dev[s]);
+        l.nframes = 1;
+        l.d_out = job.d_out;
+        l.stream = compute;
+        lrc = hjd_internal::launch_decode(l);
         launches++;
     }
     if (e == hipSuccess && work) e = hipEventRecord(t_k1[t], compute);
