@@ -1,6 +1,6 @@
 // hjd_entropy.hpp -- GPU entropy (Huffman) decoding of baseline JPEG scans:
 // the state machine shared by the gfx950 kernels (hjd_entropy.hip) and the
-// host emulation used by the CPU tests.
+// host emulation used by the CPU tests (hjd_entropy_emulate.cpp).
 //
 // What it replaces: the reference decodes the whole scan on one host thread
 // (src/decoder.cpp:221-365: DC/AC symbol loop :221-260, restart handling

@@ -1,0 +1,110 @@
+// hjd_gdec.hpp -- the GPU entropy decoder object (include/hjd_host.h hjd_gdec_*),
+// private to hjd_gdec.hip, which owns it, and hjd_gstream.hip, whose slots
+// stage into it and issue it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "hjd.h"
+#include "hjd_entropy_prep.hpp"
+#include "hjd_internal.h"
+
+struct hjd_gdec {
+    hjd_ctx* ctx = nullptr;
+    int device = 0, num_cu = 256;
+    hjd::ent::Staging st;               // the host side of the batch; st.h_stage is pinned
+    uint8_t* d_blob = nullptr;
+    uint64_t* d_entries = nullptr;
+    hjd::ent::SubStats* d_stats = nullptr;
+    uint64_t* d_mids = nullptr;
+    hjd::ent::SubStats* d_stats1 = nullptr;
+    uint64_t* d_wentries = nullptr;
+    uint32_t* d_linked = nullptr;
+    hjd::ent::SubStats* d_agg = nullptr;
+    uint32_t* h_status = nullptr;       // pinned; the device's status words are in the batch header (H.status)
+    int16_t* d_coefs = nullptr;
+    uint8_t* d_raw = nullptr;           // raw scan bytes of device-destuffed frames (same offsets as the data area)
+    uint32_t* d_tiles = nullptr;        // destuff scratch [3][max_tiles]
+    bool spec = false;                  // speculative sync (latency decoders: ent_spec/cand/sync_spec kernels)
+    hjd::ent::SpecRec* d_spec = nullptr;   // [max_subs][kMaxBpm]
+    hjd::ent::CandRec* d_cand = nullptr;
+    uint8_t* d_cmap = nullptr;
+    uint8_t* d_cslot = nullptr;
+    uint32_t* d_chainfn = nullptr;
+    uint32_t* d_chain_broken = nullptr;
+    hjd::ent::SubStats* d_agg2 = nullptr;   // [group] (ent_chain_lb_kernel)
+    uint32_t chain_epoch = 0;           // the last launch's look-back tag
+    int64_t chain_fn_rows = 0;          // capacity of d_chainfn in chunk functions
+    uint8_t* d_steps = nullptr;         // [table][1 << kStepBits] (ent_steps_kernel)
+    std::vector<uint8_t> steps_tabs;    // the tables d_steps was last derived from (host copy, batch order)
+    double host_us[3] = {0, 0, 0};      // host time per phase (wait for staging, stage, issue): HJD_GDEC_HOST_TIMES
+    int64_t host_calls = 0;
+    hipEvent_t staged = nullptr, done = nullptr;
+    int64_t last_h2d = 0;               // bytes the last issue moved host -> device
+    int64_t last_host_scan_bytes = 0;   // scan bytes the host CPU read + wrote for the staged frames
+    bool pending = false;
+    bool staged_by_done = false;        // the last issue pulled its staging: `done` also means staged
+    // the batch in flight (hjd_debug_gdec_state, hjd_gdec_sync)
+    uint32_t batch_sub_bits = 0;        // its S (0: caps.sub_bits)
+    bool batch_spec = false;            // it took the speculative sync
+    bool batch_lookback = false;        // ... and ran ent_chain_lb_kernel
+    uint32_t batch_chain_chunks = 0;    // its chain_chunks
+    uint32_t batch_lead = 0;            // its lead-in in bits (0: round-based sync)
+    int nframes_issued = 0;
+    // the lead-in ladder (spec_lead_bits)
+    uint32_t lead_step = 0;             // the ladder step for the next batch
+    uint32_t lead_left = 0;             // clean batches before it steps down
+    uint32_t lead_hold = 0;             // the clean run a step down waits for (kLeadBatches at first)
+    bool lead_stepped_down = false;     // the batch in flight runs one step lower than the last
+    int first_error = HJD_OK;
+    // settings of the next calls
+    int out_format = HJD_OUT_BGRX;      // pixel output format (hjd_gdec_set_output_format)
+    int scale = 1;                      // decode scale of hjd_gdec_decode: 1, 2, 4 or 8 (hjd_gdec_set_scale)
+    hjd_internal::NormRecord norm = hjd_internal::norm_identity();   // float formats (hjd_gdec_set_normalize)
+};
+
+namespace hjd {
+namespace ent {
+
+// D2H sink of one frame (hjd_gstream_submit_host): where its pixels go once decoded.
+struct HostCopy {
+    void* host;          // destination (pinned host memory recommended), or null
+    int32_t host_pitch;
+    int32_t width, height;
+};
+
+// One call of the decoder: everything that belongs to the call and not to
+// the object.  gdec_run reads all of it; gdec_issue (frames already staged in
+// g->st) all but datas, sizes and n.
+struct GdecCall {
+    const uint8_t* const* datas = nullptr;
+    const size_t* sizes = nullptr;
+    int n = 0;
+    void* const* d_outs = nullptr;      // pixels (with pitches), or null: coefficients only
+    const int32_t* pitches = nullptr;
+    const hjd_rect* rois = nullptr;     // hjd_gdec_decode_roi: one rectangle per image
+    int16_t* coefs_out = nullptr;       // null: the decoder's own buffer
+    int64_t* block_offsets = nullptr;
+    hipStream_t stream = nullptr;
+    const HostCopy* host = nullptr;     // per frame, or null
+    // early pull of a latency decoder's lone image (gdec_early_pull)
+    hjd_gdec* early_g = nullptr;        // non-null while the call's host destuff may pull
+    size_t prepulled = 0;               // data-area bytes of frame 0 already pulled
+};
+
+// Upload the staged frames and run the entropy kernels (+ the pixel kernel
+// when c.d_outs is given) on c.stream.
+int gdec_issue(hjd_gdec* g, GdecCall& c);
+
+// Destuff mode of a JPEG and, for the device modes, its place in the raw
+// area (PlanFn); with host_fallback, HJD_DESTUFF=auto picks the host path for
+// a scan that does not fit instead (fits stays true).
+int plan_raw(const Staging& st, const uint8_t* data, size_t size, RawCursor& cur, int& mode, uint64_t& raw_off,
+             bool& fits, size_t data_room, uint64_t reserve, bool host_fallback);
+
+// S of the stream's decoders (hjd_gstream_create).
+int stream_sub_bits(int max_frames);
+
+}  // namespace ent
+}  // namespace hjd

@@ -15,6 +15,14 @@ namespace hjd_internal {
 // return `code`.  Defined in hjd_runtime.hip.
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// JPEG zigzag: natural index of zigzag position k (src/zigzag.h:15-40).
+constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                             12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                             58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
 // Per-sampling geometry shared by the parser, the plans and the kernels.  A
 // pixel-kernel task is always 48 coefficient blocks (hjd::kTaskBlocks).
 struct SamplingGeom {
@@ -23,6 +31,7 @@ struct SamplingGeom {
     int bpm;            // blocks per MCU
     int mcus_per_task;  // 48 / bpm
 };
+constexpr int kSamplingClasses = 6;   // values of SamplingGeom::index
 inline bool sampling_geom(int sampling, SamplingGeom* g)
 {
     switch (sampling) {
@@ -191,6 +200,21 @@ inline NormRecord norm_identity() { return NormRecord{{1.f, 1.f, 1.f}, {0.f, 0.f
 // HJD_OK, or HJD_E_INVALID (NULL or non-finite constants) with the cause in the error string.
 int norm_check(const float* a, const float* b);
 
+// The one statement of a launch's frame table (DecodeLaunch::d_frames):
+// nframes FrameRecords, then with a ROI their RoiRecords at `side`, then for a
+// float format the NormRecord at `norm`; `bytes` in all.
+struct FrameTable {
+    size_t side, norm, bytes;
+};
+inline FrameTable frame_table(int nframes, bool roi, bool norm)
+{
+    FrameTable t;
+    t.side = sizeof(FrameRecord) * static_cast<size_t>(nframes);
+    t.norm = t.side + (roi ? sizeof(RoiRecord) * static_cast<size_t>(nframes) : 0);
+    t.bytes = t.norm + (norm ? sizeof(NormRecord) : 0);
+    return t;
+}
+
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe
 // the whole image; the rest the scan.
@@ -291,7 +315,7 @@ void restore_current_thread(const std::vector<int>& prev);
 namespace hjd_internal {
 
 // The scan-copy step of both host destuff routines (jpeg_host.cpp
-// destuff_scan, hjd_entropy.hip destuff): copy the bytes of [s, end) before
+// destuff_scan, hjd_entropy_prep.cpp destuff): copy the bytes of [s, end) before
 // the first 0xFF to o (advanced) and return where that 0xFF is (or end).
 // AVX2 compares, 64 bytes per test while none is an 0xFF, instead of a memchr
 // + memcpy call pair per run: entropy-coded data has an 0xFF every ~200 bytes,

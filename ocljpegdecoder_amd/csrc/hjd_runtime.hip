@@ -52,11 +52,7 @@ int fail(int code, const char* fmt, ...)
                         __FILE__, __LINE__);                                                 \
     } while (0)
 
-// JPEG zigzag: natural index of zigzag position k (src/zigzag.h:15-40).
-constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                             12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                             58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using hjd_internal::kZigzag;
 
 }  // namespace
 
@@ -744,20 +740,22 @@ int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int 
         for (int t = 0; t < nq; ++t)
             for (int k = 0; k < 64; ++k) qnat[t * 64 + kZigzag[k]] = qtables[t * 64 + k];
 
-    // a ROI plan's RoiDev table follows the nframes records (frames + nframes)
+    // the frame table (hjd_internal::frame_table): a ROI plan's RoiDev table follows the nframes
+    // records, a float plan's NormDev record both; a = 1, b = 0 until hjd_plan_set_normalize
+    static_assert(sizeof(hjd_internal::FrameRecord) == sizeof(FrameDev), "frame record layout");
     static_assert(sizeof(hjd_internal::RoiRecord) == sizeof(hjd::RoiDev), "side record layout");
-    const size_t side_off = static_cast<size_t>(nframes) * sizeof(FrameDev);
-    // a float plan's NormDev record follows both tables; a = 1, b = 0 until hjd_plan_set_normalize
     static_assert(sizeof(hjd_internal::NormRecord) == sizeof(hjd::NormDev), "norm record layout");
     const bool norm = hjd_internal::out_format_float_bytes(out_format) != 0;
-    p->norm_off = norm ? side_off + (rois ? static_cast<size_t>(nframes) * sizeof(hjd::RoiDev) : 0) : 0;
+    const hjd_internal::FrameTable tab = hjd_internal::frame_table(nframes, rois != nullptr, norm);
+    p->norm_off = norm ? tab.norm : 0;
     const hjd_internal::NormRecord ident = hjd_internal::norm_identity();
-    hipError_t e = hipMalloc(&p->d_frames, std::max(fd.size() * sizeof(FrameDev) + sides.size() * sizeof(hjd::RoiDev),
-                                                    p->norm_off) + (norm ? sizeof(hjd::NormDev) : 0));
+    // (an empty plan still holds fd's one record)
+    hipError_t e = hipMalloc(&p->d_frames,
+                             hjd_internal::frame_table(static_cast<int>(fd.size()), rois != nullptr, norm).bytes);
     if (e == hipSuccess) e = hipMalloc(&p->d_qt, qnat.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemcpy(p->d_frames, fd.data(), fd.size() * sizeof(FrameDev), hipMemcpyHostToDevice);
     if (e == hipSuccess && rois && nframes > 0)
-        e = hipMemcpy(reinterpret_cast<char*>(p->d_frames) + side_off, sides.data(),
+        e = hipMemcpy(reinterpret_cast<char*>(p->d_frames) + tab.side, sides.data(),
                       static_cast<size_t>(nframes) * sizeof(hjd::RoiDev), hipMemcpyHostToDevice);
     if (e == hipSuccess && norm)
         e = hipMemcpy(reinterpret_cast<char*>(p->d_frames) + p->norm_off, &ident, sizeof(ident), hipMemcpyHostToDevice);

@@ -41,7 +41,7 @@ constexpr int32_t kFastEob = 0x8000;
 
 struct HuffTable {
     bool defined = false;
-    uint8_t counts[16];      // the DHT spec, kept for the GPU tables (hjd_entropy.hip)
+    uint8_t counts[16];      // the DHT spec, kept for the GPU tables (hjd_entropy_prep.cpp)
     int nsym = 0;
     uint16_t fast[kFast];    // (length << 8) | symbol for codes of <= kFastBits bits; 0 = slow path
     // AC: (value << 16) | (run << 5) | (code + extra bits) when those fit kFastBits, else 0
@@ -1675,6 +1675,39 @@ int hjd_jpeg_decode_batch(const uint8_t* const* datas, const size_t* sizes, int 
     work();
     for (auto& t : pool) t.join();
     return failed ? set_error(HJD_E_INVALID, "%d of %d files failed to decode", failed.load(), n) : HJD_OK;
+}
+
+static void bmp_header_bpp(int32_t width, int32_t height, int bpp, uint8_t header[54])
+{
+    // src/decoder.cpp:372-394 (bmp_create): BITMAPFILEHEADER + BITMAPINFOHEADER,
+    // BI_RGB, negative height = top-down rows; rows padded to 4 bytes.
+    auto put16 = [&](int o, uint32_t v) { header[o] = v & 0xFF; header[o + 1] = (v >> 8) & 0xFF; };
+    auto put32 = [&](int o, uint32_t v) { put16(o, v & 0xFFFF); put16(o + 2, v >> 16); };
+    memset(header, 0, 54);
+    const uint64_t row = (static_cast<uint64_t>(width) * (bpp / 8) + 3) & ~uint64_t(3);
+    const uint64_t size = 54 + row * static_cast<uint64_t>(height);
+    put16(0, 0x4d42);
+    put32(2, static_cast<uint32_t>(size));
+    put32(10, 54);
+    put32(14, 40);
+    put32(18, static_cast<uint32_t>(width));
+    put32(22, static_cast<uint32_t>(-height));
+    put16(26, 1);
+    put16(28, static_cast<uint32_t>(bpp));
+}
+
+int hjd_bmp_header(int32_t width, int32_t height, uint8_t header[54])
+{
+    if (!header || width <= 0 || height <= 0) return set_error(HJD_E_INVALID, "invalid BMP geometry");
+    bmp_header_bpp(width, height, 32, header);   // the reference's 32-bpp BGRX file
+    return HJD_OK;
+}
+
+int hjd_bmp_header_bgr24(int32_t width, int32_t height, uint8_t header[54])
+{
+    if (!header || width <= 0 || height <= 0) return set_error(HJD_E_INVALID, "invalid BMP geometry");
+    bmp_header_bpp(width, height, 24, header);
+    return HJD_OK;
 }
 
 }  // extern "C"

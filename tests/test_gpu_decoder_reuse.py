@@ -4,7 +4,7 @@ A decoder is built once and called thousands of times, and it carries state
 from launch to launch: the look-back words of ent_chain_lb_kernel and their
 24-bit tag, device buffers and caches that are never cleared (d_linked, d_agg,
 d_agg2, d_cslot, d_cand, d_cmap, d_chain_broken, the step tables' cache,
-prepulled, batch_sub_bits, batch_spec) and the lead-in ladder.  Each is right
+batch_sub_bits, batch_spec) and the lead-in ladder.  Each is right
 only if every launch rewrites what it later reads, whatever the launch before
 it was.  Here consecutive calls differ in every way the decoder distinguishes,
 and the carried state is read back through GpuDecoder.debug_state().
@@ -28,10 +28,10 @@ from test_entropy_emulation import _pil
 
 pytestmark = pytest.mark.gpu
 
-kChainChunk = 1024               # subsequences per look-back chunk (hjd_entropy.hip:1121)
-kLeadLadder = (512, 1536, 2560)  # hjd_entropy.hip:2311
-kLeadBatches = 32                # hjd_entropy.hip:2312
-kEpochMax = 0xFFFFFF             # the tag's last value before it wraps to 1 (hjd_entropy.hip:2961, gdec_issue)
+kChainChunk = 1024               # subsequences per look-back chunk (kChainChunk, hjd_entropy_batch.hpp)
+kLeadLadder = (512, 1536, 2560)  # kLeadLadder, hjd_gdec.hip
+kLeadBatches = 32                # kLeadBatches, hjd_gdec.hip
+kEpochMax = 0xFFFFFF             # the tag's last value before it wraps to 1 (gdec_issue, hjd_gdec.hip)
 
 
 @pytest.fixture
@@ -152,7 +152,7 @@ def test_lookback_tags_survive_the_epoch_wrap(hjd, ctx, tuning, frames):
     f * chain_chunks, so which words a launch rewrites changes with its batch.
     When the tag wraps from 2^24 - 1 to 1, a word written at tag 1 one full
     cycle earlier and not rewritten since carries the current tag again: the
-    kernel (hjd_entropy.hip:1425-1430, 1449, 1471) would take that stale exit
+    kernel (ent_chain_lb_kernel, hjd_entropy.hip) would take that stale exit
     slot or map for this launch's and enter a chunk at the wrong slot -- by
     the code wrong coefficients with a clean status, a spurious corrupt status
     or a spurious repair bit (stale slots are real slots, < kChainSlots, so a
@@ -256,7 +256,7 @@ def test_one_decoder_mixed_sequence(hjd, ctx, tuning):
     scan_src = {two_scans: base}   # (the same coefficients with the same tables: the single-scan file's bits)
     bad_src = _pil(640, 480, 100, 0, seed=948, restart_marker_blocks=8)
     bad = _wrong_rst(bad_src)
-    assert 8 * _scan_bytes(dense) > 200 * _ref(dense)[1].nblocks   # kDenseBitsPerBlock (hjd_entropy.hip:2849)
+    assert 8 * _scan_bytes(dense) > 200 * _ref(dense)[1].nblocks   # kDenseBitsPerBlock (hjd_gdec.hip)
     seq = [
         ("coefs", [a[0]]),                 # one large frame, default tables
         ("pixels", [t1, a[1], gray]),      # three frames: tiny with restarts, large, gray
@@ -284,7 +284,7 @@ def test_one_decoder_mixed_sequence(hjd, ctx, tuning):
                 with pytest.raises(hjd._lib.HjdError, match="expected RST"):
                     r.gd.decode_coefs(datas, out)
                 continue
-            # the sync a batch takes, worked out on the CPU (kDenseBitsPerBlock = 200, hjd_entropy.hip:2849)
+            # the sync a batch takes, worked out on the CPU (kDenseBitsPerBlock = 200, hjd_gdec.hip)
             bpb = 8 * sum(_scan_bytes(scan_src.get(d, d)) for d in datas) / sum(_ref(d)[1].nblocks for d in datas)
             assert bpb > 400 if dense in datas else bpb < 190, (k, bpb)
             st = (r.coefs if kind == "coefs" else r.pixels)(datas, f"batch {k} ({kind})")
@@ -302,9 +302,51 @@ def test_one_decoder_mixed_sequence(hjd, ctx, tuning):
     assert min(s[3] for s in seen) == 1 and max(s[3] for s in seen if s[1]) >= 16   # one chunk <-> many
 
 
+def test_failed_roi_call_leaves_nothing_behind(hjd, ctx):
+    """What belongs to one call (its rectangles, its outputs, its early-pull
+    bookkeeping) travels in the call's descriptor (GdecCall), not on the
+    decoder: a ROI call that fails in staging (a) and one refused before
+    staging (b) leave nothing that the next calls could pick up.  (c) a plain
+    decode of whole frames into tensors with a guard row, then (d) a ROI
+    decode, both exact against the oracle, on the one two-frame decoder."""
+    import torch
+    f420 = _pil(48, 32, 90, 2, seed=960)
+    f444 = _pil(40, 24, 90, 0, seed=961)
+    datas = [f420, f444]
+    infos = [_ref(d)[1] for d in datas]
+    assert [(i.width, i.height, i.sampling) for i in infos] == [(48, 32, hjd.YUV420), (40, 24, hjd.YUV444)]
+    sos = f444.index(b"\xff\xda")
+    assert sos + 4 < infos[1].scan_offset
+    cut = f444[:sos + 4]   # inside the SOS header: no pre-check reads it, staging refuses it
+    rois = [(8, 4, 24, 16), (3, 5, 28, 12)]
+
+    def roi_outs():
+        return [torch.full((r[3], r[2]), -1, dtype=torch.int32, device="cuda") for r in rois]
+
+    with hjd.GpuDecoder(ctx, 2, 2 * sum(map(len, datas)), 2 * sum(i.nblocks for i in infos)) as gd:
+        with pytest.raises(hjd._lib.HjdError):                        # (a)
+            gd.decode([f420, cut], roi_outs(), rois=rois)
+        with pytest.raises(hjd._lib.HjdError, match="frame 0: roi") as e:   # (b)
+            gd.decode(datas, roi_outs(), rois=[(40, 0, 16, 8), rois[1]])   # 56 px wide
+        assert e.value.code == -1
+        guarded = [torch.full((i.height + 1, i.width), -1, dtype=torch.int32, device="cuda") for i in infos]
+        gd.decode(datas, [g[:i.height] for g, i in zip(guarded, infos)])   # (c)
+        assert gd.sync() == [0, 0]
+        for k, (d, g, i) in enumerate(zip(datas, guarded, infos)):
+            host = g.cpu().numpy()
+            np.testing.assert_array_equal(host[:i.height].view(np.uint32), _ref_pixels(d), err_msg=f"(c) file {k}")
+            assert (host[i.height] == -1).all(), f"(c) file {k}: guard row written"
+        outs = roi_outs()
+        gd.decode(datas, outs, rois=rois)                             # (d)
+        assert gd.sync() == [0, 0]
+        for k, (d, o, (x, y, w, h)) in enumerate(zip(datas, outs, rois)):
+            np.testing.assert_array_equal(o.cpu().numpy().view(np.uint32), _ref_pixels(d)[y:y + h, x:x + w],
+                                          err_msg=f"(d) file {k}")
+
+
 def test_lead_ladder_walks_down_and_doubles_its_hold(hjd, ctx, tuning):
-    """The lead-in ladder of hjd_gdec_sync (hjd_entropy.hip:3308-3321, "the lead-in of
-    the next batches") on a one-frame decoder at its default S (512):
+    """The lead-in ladder of hjd_gdec_sync ("the lead-in of the next batches",
+    hjd_gdec.hip) on a one-frame decoder at its default S (512):
     kLeadLadder = {512, 1536, 2560}, kLeadBatches = 32.  B (320x240 q90 4:4:4
     seed 0) needs a repair at a lead-in of 512 bits and none at 1536; C (seed 1)
     is clean at both (pinned on the CPU, test_entropy_emulation_spec.py).
@@ -342,7 +384,7 @@ def test_lead_ladder_walks_down_and_doubles_its_hold(hjd, ctx, tuning):
             if k == 10:   # a dense batch does not touch the ladder
                 st = r.coefs([D], "dense")
                 assert (st["batch_spec"], st["batch_lookback"], st["batch_lead_bits"]) == (0, 0, 0), st
-                assert st["batch_sub_bits"] == 8192, st   # kDenseTiers' last (hjd_entropy.hip:2853)
+                assert st["batch_sub_bits"] == 8192, st   # kDenseTiers' last (hjd_gdec.hip)
                 assert ladder(st) == (1, 32 - k, 32, 0), st
         run(C, 1, (0, 0, 32, 1), "C 32", compare=True)
         run(B, 0, (1, 64, 64, 0), "B after the step down", compare=True)

@@ -1,7 +1,8 @@
 #!/bin/bash
-# CPU-only: build the GPU entropy decoder's host emulation (hjd_entropy.hip and
-# what it links against) with host-side AddressSanitizer + UBSan, and fuzz it
-# on damaged sequential JPEGs, one scan or several (tools/fuzz/entropy_emulate_fuzz.cpp).
+# CPU-only: build the GPU entropy decoder's host emulation (hjd_entropy_emulate.cpp
+# and what it links against: every unit of csrc/) with host-side AddressSanitizer +
+# UBSan, and fuzz it on damaged sequential JPEGs, one scan or several
+# (tools/fuzz/entropy_emulate_fuzz.cpp).
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/build/efuzz   # in the tree (git-ignored): a shared temp directory may belong to another user
@@ -11,10 +12,20 @@ FLAGS="-std=c++17 -O1 -g -fno-omit-frame-pointer -I$R/include -I$R/ocljpegdecode
 C=$R/ocljpegdecoder_amd/csrc
 pids=()
 newest_hdr=$(ls -t $C/*.hpp $C/*.h $R/include/*.h | head -1)
-for f in hjd_entropy hjd_runtime idct_compat stream_pipeline numa_affinity hjd_probe; do
-  [ $O/$f.o -nt $C/$f.hip ] && [ $O/$f.o -nt $newest_hdr ] || { /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $SAN -c $C/$f.hip -o $O/$f.o & pids+=($!); }
+# the library's units are whatever csrc/ holds (as tools/build_native.py lists them):
+# *.hip with device code, *.cpp as plain C++; objects of units that are gone are dropped
+for o in $O/*.o; do
+  f=$(basename $o .o)
+  [ -e $C/$f.hip ] || [ -e $C/$f.cpp ] || rm -f $o   # (main.o too: rebuilt below)
 done
-[ $O/jpeg_host.o -nt $C/jpeg_host.cpp ] && [ $O/jpeg_host.o -nt $newest_hdr ] || { /opt/rocm/bin/hipcc -x c++ $FLAGS $SAN -c $C/jpeg_host.cpp -o $O/jpeg_host.o & pids+=($!); }
+for s in $C/*.hip $C/*.cpp; do
+  f=$(basename ${s%.*})
+  [ $O/$f.o -nt $s ] && [ $O/$f.o -nt $newest_hdr ] && continue
+  case $s in
+    *.hip) /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $SAN -c $s -o $O/$f.o & pids+=($!) ;;
+    *.cpp) /opt/rocm/bin/hipcc -x c++ $FLAGS $SAN -c $s -o $O/$f.o & pids+=($!) ;;
+  esac
+done
 for p in ${pids[@]+"${pids[@]}"}; do wait $p; done
 /opt/rocm/bin/hipcc -x c++ $FLAGS $SAN -c $R/tools/fuzz/entropy_emulate_fuzz.cpp -o $O/main.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize $O/*.o -o $O/efuzz -lpthread
