@@ -326,6 +326,66 @@ typedef struct hjd_launch_shape {
 } hjd_launch_shape;
 int hjd_plan_launch_shape(const hjd_plan* plan, hjd_launch_shape* out);
 
+/*
+ * Resize (extension; the reference has none): n planar uint8 RGB images, each
+ * of its own size, resampled to one common out_w x out_h in ONE launch, so
+ * that crops of different sizes become one (N, 3, out_h, out_w) batch.
+ *
+ * Source: three uint8 planes R, G, B of src_w x src_h as HJD_OUT_RGB_PLANAR
+ * writes them: rows src_pitch bytes apart, planes src_pitch * src_h apart;
+ * any pointer and any src_pitch >= src_w.  All four dimensions lie in
+ * 1..16384 (every expression below then fits 32-bit arithmetic).
+ *
+ * Definition (exact, integer): bilinear with half-pixel centres
+ * (align_corners = false), 11-bit weights, no antialiasing.  Per axis (x
+ * shown; y the same with src_h, out_h, i), for output column j:
+ *     n  = max((2j + 1) * src_w - out_w, 0)       den = 2 * out_w
+ *     x0 = n / den (floor)      fx = ((n mod den) * 2048) / den (floor)
+ *     x1 = min(x0 + 1, src_w - 1)
+ * and per channel, with A = src[y0][x0], B = src[y0][x1], C = src[y1][x0],
+ * D = src[y1][x1]:
+ *     u8 = (A (2048-fx)(2048-fy) + B fx (2048-fy) + C (2048-fx) fy + D fx fy
+ *           + 2^21) >> 22
+ * -- one rounding.  With out_w == src_w and out_h == src_h the result is the
+ * source, byte for byte.  flags bit 0 (horizontal flip): output column j
+ * holds the unflipped result's column out_w - 1 - j.  Other bits must be 0.
+ * Plain bilinear aliases beyond a 2x reduction: decode at the scale (1/2,
+ * 1/4, 1/8 box means, hjd_plan_create_scaled) that leaves the crop at most
+ * 2x the target, then resize.
+ *
+ * Output: out_format is HJD_OUT_RGB_PLANAR (the bytes u8),
+ * HJD_OUT_RGB_PLANAR_F16 or _F32 (fma((float)u8, a[c], b[c]) as hjd_out_format
+ * defines it, both roundings of F16 included; hjd_resize_set_normalize, default
+ * a = 1, b = 0); anything else is HJD_E_INVALID.  Item i's plane R starts at
+ * dst, rows out_pitch bytes apart (>= out_w x the element size and a multiple
+ * of it, like dst), planes out_pitch * out_h apart.  An item whose dst and
+ * out_pitch are multiples of 4 (bytes), 8 (F16) or 16 (F32), with out_w % 4 ==
+ * 0, is written with one dword / dwordx2 / dwordx4 store per plane and four
+ * pixels; any other with guarded element stores.  Sources and outputs must
+ * not overlap.
+ */
+typedef struct hjd_resize_item {
+    const void* src;   /* device: plane R of the source */
+    void* dst;         /* device: plane R of this item's output */
+    int32_t src_w, src_h, src_pitch, flags;
+} hjd_resize_item;
+typedef struct hjd_resize hjd_resize;
+/* Validates what hjd_resize_create would take.  HJD_E_INVALID (with a message)
+ * for n outside 1..2^20, a NULL items / src / dst, a dimension outside
+ * 1..16384, src_pitch < src_w, a bad out_pitch or dst alignment, a non-planar
+ * or unknown format and unknown flag bits.  Host only: needs no device. */
+int hjd_resize_check(const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch, int out_format);
+/* Validates and uploads the item table (synchronously). */
+int hjd_resize_create(hjd_ctx* ctx, const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch,
+                      int out_format, hjd_resize** out);
+/* The float formats' constants for the launches that follow (an enqueued
+ * launch keeps its own).  HJD_E_INVALID for non-finite constants and for a
+ * byte-format object. */
+int hjd_resize_set_normalize(hjd_resize* r, const float a[3], const float b[3]);
+/* Enqueue the resize of all n items on `stream` (asynchronous, one kernel). */
+int hjd_resize_launch(hjd_resize* r, void* stream);
+int hjd_resize_destroy(hjd_resize* r);
+
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */
 int hjd_idct_blocks(hjd_ctx* ctx, const int32_t* d_in, int32_t* d_out, int64_t nblocks, void* stream);

@@ -203,6 +203,29 @@ int hjd_gdec_set_scale(hjd_gdec* g, int scale);
  * (HJD_E_INVALID) before anything is enqueued. */
 int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                         void* const* d_outs, const int32_t* pitches, void* stream);
+/* Decode n JPEGs, crop each (rois[i] as hjd_gdec_decode_roi's; rois == NULL:
+ * the whole frames at the decoder's scale), resize every crop to out_w x
+ * out_h (include/hjd.h, hjd_resize_*: bilinear, 11-bit weights, no
+ * antialiasing, dimensions 1..16384) and flip it where flags[i] bit 0 is set
+ * (flags == NULL: none; other bits are HJD_E_INVALID).  Image i lands at
+ * d_out + i * 3 * out_pitch * out_h: with out_pitch == out_w x the element
+ * size, d_out is one contiguous (n, 3, out_h, out_w) batch.  The format is
+ * the decoder's current one and must be planar (HJD_OUT_RGB_PLANAR, _F16 or
+ * _F32: out_pitch and d_out follow hjd_resize_check's rules; any other format
+ * is HJD_E_INVALID); the constants and the scale are the decoder's current
+ * ones too.  A refused call (format, sizes, pitch, a rectangle, a scale the
+ * file's sampling does not serve) enqueues nothing.
+ *
+ * The pixel kernels run as for hjd_gdec_decode_roi with HJD_OUT_RGB_PLANAR,
+ * into a scratch buffer the decoder owns (each crop 16-byte aligned, its
+ * pitch rounded up to 4, so whole strips keep their vector stores); one
+ * resize launch for all n images follows on the same stream.  The scratch
+ * only grows: a call that needs more than the decoder holds waits for the
+ * previous call (a host synchronisation) and reallocates; calls that fit are
+ * asynchronous as hjd_gdec_decode.  hjd_gdec_destroy frees it.  The streams
+ * (hjd_stream, hjd_gstream) do not serve a resized decode. */
+int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                            const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

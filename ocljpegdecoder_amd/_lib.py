@@ -37,6 +37,15 @@ class HjdRect(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("x", "y", "w", "h")]
 
 
+class HjdResizeItem(ctypes.Structure):
+    """struct hjd_resize_item (include/hjd.h): one image of a resize."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in
+                                                                       ("src_w", "src_h", "src_pitch", "flags")]
+
+
+assert ctypes.sizeof(HjdResizeItem) == 32
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -120,6 +129,13 @@ SIGNATURES = {
                                          ctypes.c_int, c_i32p, c_i32p]),
     "hjd_autotune_cache_clear": (ctypes.c_int, []),
     "hjd_plan_launch_shape": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdLaunchShape)]),
+    "hjd_resize_check": (ctypes.c_int, [ctypes.POINTER(HjdResizeItem)] + [ctypes.c_int] * 5),
+    "hjd_resize_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdResizeItem)] + [ctypes.c_int] * 5 +
+                          [ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_resize_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                                ctypes.POINTER(ctypes.c_float)]),
+    "hjd_resize_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_resize_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
     "hjd_debug_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -211,6 +227,9 @@ def _bind_host(lib):
         "hjd_gdec_set_normalize": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
         "hjd_gdec_decode_roi": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int,
                                                ctypes.POINTER(HjdRect), ctypes.POINTER(vp), c_i32p, vp]),
+        "hjd_gdec_decode_resized": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                   ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, vp, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int32, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -398,6 +398,95 @@ class Plan:
             pass
 
 
+RESIZE_FLIP_H = 1   # hjd_resize_item.flags bit 0
+_DTYPE_FORMATS = {"torch.uint8": OUT_RGB_PLANAR, "torch.float16": OUT_RGB_PLANAR_F16,
+                  "torch.float32": OUT_RGB_PLANAR_F32}
+
+
+def resize_scale(src_w: int, src_h: int, out_w: int, out_h: int) -> int:
+    """The decode scale to resize from: the largest s in (8, 4, 2, 1) that
+    leaves a src_w x src_h region (at scale 1) at least out_w x out_h, that is
+    ceil(src_w / s) >= out_w and ceil(src_h / s) >= out_h; 1 if none does (an
+    upscale).  The box means of the scaled decode then do the reduction beyond
+    2x that plain bilinear would alias on.  Pure Python."""
+    for s in (8, 4, 2):
+        if -(-int(src_w) // s) >= out_w and -(-int(src_h) // s) >= out_h:
+            return s
+    return 1
+
+
+class Resize:
+    """hjd_resize: N planar uint8 RGB images of different sizes -> one
+    (N, 3, Ho, Wo) batch in one launch (include/hjd.h: bilinear, half-pixel
+    centres, 11-bit integer weights, no antialiasing; sizes 1..16384)."""
+
+    def __init__(self, ctx: Context, srcs, out, flips=None, normalize=None):
+        """srcs: N device tensors (3, h, w) uint8 (contiguous, or a [..., :w]
+        view of wider rows), or (tensor, pitch) pairs: 3 * h rows of `pitch`
+        bytes from the tensor's data_ptr, whose shape (3, h, w) gives h and w.
+        out: a device tensor (N, 3, Ho, Wo) of uint8, float16 or float32,
+        contiguous or a [..., :Wo] view of wider rows.  flips: N truthy
+        values, image i mirrored horizontally where set.  normalize = (a, b):
+        the float dtypes' constants (set_normalize; default a = 1, b = 0)."""
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.handle = None
+        n = len(srcs)
+        if not (out.is_cuda and out.ndim == 4 and out.shape[1] == 3 and str(out.dtype) in _DTYPE_FORMATS):
+            raise ValueError("out must be a uint8 / float16 / float32 device tensor (N, 3, Ho, Wo)")
+        ho, wo = int(out.shape[2]), int(out.shape[3])
+        row = out.stride(2)   # elements between rows: Wo, or more for a [..., :Wo] view of wider rows
+        if out.stride(3) != 1 or row < wo or out.stride(1) != ho * row or (n > 1 and out.stride(0) != 3 * ho * row):
+            raise ValueError("out must be contiguous, or a [..., :Wo] view of a contiguous (N, 3, Ho, P) tensor")
+        if out.shape[0] != n:
+            raise ValueError(f"out holds {out.shape[0]} images, {n} sources given")
+        if flips is not None and len(flips) != n:
+            raise ValueError("one flip flag per source")
+        self.out_format = _DTYPE_FORMATS[str(out.dtype)]
+        pitch = row * out.element_size()
+        items = (_lib.HjdResizeItem * max(1, n))()
+        self._keep = []
+        for i, s in enumerate(srcs):
+            t, sp = s if isinstance(s, (tuple, list)) else (s, None)
+            if not (t.is_cuda and t.element_size() == 1 and t.ndim == 3 and t.shape[0] == 3):
+                raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
+            if sp is None:   # contiguous, or a [..., :w] view of wider rows
+                sp = t.stride(1)
+                if t.stride(2) != 1 or sp < t.shape[2] or t.stride(0) != t.shape[1] * sp:
+                    raise ValueError(f"source {i} must be contiguous, a [..., :w] view of wider rows, or come with "
+                                     "its pitch")
+            self._keep.append(t)
+            items[i] = _lib.HjdResizeItem(t.data_ptr(), out[i].data_ptr(), int(t.shape[2]), int(t.shape[1]), int(sp),
+                                          RESIZE_FLIP_H if flips is not None and flips[i] else 0)
+        self.out = out
+        h = ctypes.c_void_p()
+        check(self.lib.hjd_resize_create(ctx.handle, items, n, wo, ho, pitch, self.out_format, ctypes.byref(h)),
+              "hjd_resize_create")
+        self.handle = h
+        if normalize is not None:
+            self.set_normalize(*normalize)
+
+    def set_normalize(self, a, b):
+        """hjd_resize_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
+        ca, cb = _norm_arrays((a, b))
+        check(self.lib.hjd_resize_set_normalize(self.handle, ca, cb), "hjd_resize_set_normalize")
+
+    def launch(self, stream=None):
+        """Enqueue the resize kernel (asynchronous)."""
+        check(self.lib.hjd_resize_launch(self.handle, _stream_ptr(stream)), "hjd_resize_launch")
+
+    def close(self):
+        if self.handle:
+            self.lib.hjd_resize_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def worker_cpus(bus: str, gpus: Sequence[str], sysfs_root: Optional[str] = None, only_allowed: bool = False):
     """hjd_debug_worker_cpus: the host CPUs the worker pool of the GPU at PCI
     address `bus` binds to, among the GPUs `gpus` (its NUMA node's CPUs split

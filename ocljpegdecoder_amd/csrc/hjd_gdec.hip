@@ -259,7 +259,7 @@ inline int sampling_class(int sampling)
 // The pixel kernel's tables of the batch assembled in g->st: the frame
 // records grouped by sampling class (one launch each) at H.recs, and the
 // natural-order qtables at H.qt.
-int write_pixel_records(hjd_gdec* g, const GdecCall& c, bool fnorm, PixelClasses& px)
+int write_pixel_records(hjd_gdec* g, const GdecCall& c, int out_format, bool fnorm, PixelClasses& px)
 {
     Staging& st = g->st;
     const int n = static_cast<int>(st.frames.size());
@@ -267,9 +267,9 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, bool fnorm, PixelClasses
     px.roi = rois != nullptr;
     const EntFrame* ef = reinterpret_cast<const EntFrame*>(st.h_stage + st.H.frames);
     int32_t* qtn = reinterpret_cast<int32_t*>(st.h_stage + st.H.qt);
-    const int obytes = hjd_internal::out_format_row_bytes(g->out_format);
-    const uintptr_t amask = hjd_internal::out_format_align_mask(g->out_format);
-    const int pmask = hjd_internal::out_format_pitch_mask(g->out_format);
+    const int obytes = hjd_internal::out_format_row_bytes(out_format);
+    const uintptr_t amask = hjd_internal::out_format_align_mask(out_format);
+    const int pmask = hjd_internal::out_format_pitch_mask(out_format);
     for (int i = 0; i < n; ++i) {
         const Prepared& p = st.frames[i];
         const int out_w = rois ? rois[i].w : hjd_internal::scaled_dim(p.width, g->scale);
@@ -296,7 +296,7 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, bool fnorm, PixelClasses
         const int64_t t = hjd_internal::make_frame_record(
             p.width, p.height, p.sampling, static_cast<int64_t>(ef[i].coef_off),
             static_cast<int64_t>(static_cast<uint8_t*>(c.d_outs[i]) - px.out_base[sidx]), c.pitches[i], qti, &rec,
-            g->out_format, reinterpret_cast<uintptr_t>(px.out_base[sidx]), g->scale, rois ? &rois[i] : nullptr,
+            out_format, reinterpret_cast<uintptr_t>(px.out_base[sidx]), g->scale, rois ? &rois[i] : nullptr,
             rois ? &side : nullptr);
         if (t < 0) return static_cast<int>(t);
         rec.task_begin = px.tasks[sidx];
@@ -309,6 +309,38 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, bool fnorm, PixelClasses
         ++written[sidx];
         for (int q = 0; q < 3; ++q)
             for (int k = 0; k < 64; ++k) qtn[(3 * i + q) * 64 + hjd_internal::kZigzag[k]] = p.qt[q][k];
+    }
+    return HJD_OK;
+}
+
+// Where a resized call's records lie behind the pixel kernel's tables (from H.recs).
+inline size_t resize_records_offset(int n, bool roi)
+{
+    return hjd_internal::align_up(pixel_tables_bytes(n, roi, false), 16);
+}
+
+// The resize kernel's records of a resized call (ResizeStage): image i from
+// its crop in the scratch (c.d_outs[i], c.pitches[i]) to its place in the batch.
+int write_resize_records(hjd_gdec* g, const GdecCall& c)
+{
+    Staging& st = g->st;
+    const int n = static_cast<int>(st.frames.size());
+    const ResizeStage& r = *c.resize;
+    hjd_internal::ResizeRecord* recs = reinterpret_cast<hjd_internal::ResizeRecord*>(
+        st.h_stage + st.H.recs + resize_records_offset(n, c.rois != nullptr));
+    const size_t image = 3 * static_cast<size_t>(r.out_pitch) * static_cast<size_t>(r.out_h);
+    for (int i = 0; i < n; ++i) {
+        const Prepared& p = st.frames[i];
+        hjd_internal::ResizeRecord rec;
+        rec.src = c.d_outs[i];
+        rec.dst = static_cast<uint8_t*>(r.out) + image * static_cast<size_t>(i);
+        rec.w = c.rois ? c.rois[i].w : hjd_internal::scaled_dim(p.width, g->scale);
+        rec.h = c.rois ? c.rois[i].h : hjd_internal::scaled_dim(p.height, g->scale);
+        rec.pitch = c.pitches[i];
+        rec.flags = r.flags ? r.flags[i] : 0;
+        const int rc = hjd_internal::resize_item_check(rec, i, g->out_format);
+        if (rc) return rc;
+        recs[i] = rec;
     }
     return HJD_OK;
 }
@@ -347,16 +379,25 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     }
     g->batch_spec = spec;
     const uint32_t S = g->batch_sub_bits ? g->batch_sub_bits : static_cast<uint32_t>(st.caps.sub_bits);
-    const bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(g->out_format) != 0;
+    // a resized call's pixel kernels write planar bytes (the crops); its resize launch the decoder's format
+    const int pix_format = c.resize ? HJD_OUT_RGB_PLANAR : g->out_format;
+    const bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
+    const size_t recs_bytes = !c.d_outs ? 0
+                              : c.resize ? resize_records_offset(n, c.rois != nullptr) +
+                                               sizeof(hjd_internal::ResizeRecord) * static_cast<size_t>(n)
+                                         : pixel_tables_bytes(n, c.rois != nullptr, fnorm);
     EntBatchDev b;
-    int rc = st.assemble(g->d_blob, coefs, c.block_offsets, S,
-                         c.d_outs ? pixel_tables_bytes(n, c.rois != nullptr, fnorm) : 0,
+    int rc = st.assemble(g->d_blob, coefs, c.block_offsets, S, recs_bytes,
                          c.d_outs ? 192 * 4 * static_cast<size_t>(n) : 0, b);
     if (rc) return rc;
     PixelClasses px;
     if (c.d_outs) {
-        rc = write_pixel_records(g, c, fnorm, px);
+        rc = write_pixel_records(g, c, pix_format, fnorm, px);
         if (rc) return rc;
+        if (c.resize) {
+            rc = write_resize_records(g, c);
+            if (rc) return rc;
+        }
     }
     b.entries = g->d_entries;
     b.stats = g->d_stats;
@@ -515,7 +556,7 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
             if (!px.nrec[sidx]) continue;
             hjd_internal::DecodeLaunch l;   // int16 input, HJD_KERNEL_AUTO, the default grid
             l.sampling = kClassSampling[sidx];
-            l.out_format = g->out_format;
+            l.out_format = pix_format;
             l.scale = g->scale;
             l.roi = px.roi;
             l.tasks = px.tasks[sidx];
@@ -527,6 +568,15 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
             l.d_out = px.out_base[sidx];
             l.stream = s;
             rc = hjd_internal::launch_decode(l);
+            if (rc) return rc;
+        }
+        if (c.resize) {   // the crops -> the batch, behind the pixel kernels; `done` (below) covers it
+            const ResizeStage& r = *c.resize;
+            rc = hjd_internal::launch_resize(
+                g->device,
+                reinterpret_cast<const hjd_internal::ResizeRecord*>(g->d_blob + g->st.H.recs +
+                                                                    resize_records_offset(n, c.rois != nullptr)),
+                n, r.out_w, r.out_h, r.out_pitch, g->out_format, g->norm, s);
             if (rc) return rc;
         }
     }
@@ -656,7 +706,7 @@ int hjd_gdec_destroy(hjd_gdec* g)
     if (g->h_status) (void)hipHostFree(g->h_status);
     void* dev[] = {g->d_blob, g->d_entries, g->d_stats, g->d_mids, g->d_stats1, g->d_wentries, g->d_linked, g->d_agg,
                    g->d_coefs, g->d_raw, g->d_tiles, g->d_spec, g->d_cand, g->d_cmap, g->d_cslot,
-                   g->d_steps, g->d_chainfn, g->d_chain_broken, g->d_agg2};
+                   g->d_steps, g->d_chainfn, g->d_chain_broken, g->d_agg2, g->d_crops};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (g->staged) (void)hipEventDestroy(g->staged);
@@ -709,6 +759,78 @@ int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* 
     c.d_outs = d_outs;
     c.pitches = pitches;
     c.rois = rois;
+    return gdec_run(g, c);
+}
+
+int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                            const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
+{
+    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
+    if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
+    // everything that can refuse the call is checked before anything is staged, allocated or enqueued
+    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
+        return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
+                         hjd_internal::out_format_row_bytes(g->out_format));
+    if (n > g->st.caps.max_frames)
+        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
+    // the crops in the scratch: each 16-byte aligned, its pitch rounded up to 4
+    // (whole strips of the pixel kernel keep their vector stores)
+    std::vector<size_t> offs(static_cast<size_t>(n));
+    std::vector<int32_t> pitches(static_cast<size_t>(n));
+    size_t need = 0;
+    hjd_internal::ScanHeader h;
+    hjd_internal::DecodeShape shape;
+    shape.scale = g->scale;
+    for (int i = 0; i < n; ++i) {
+        if (!datas[i]) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
+        rc = hjd_internal::parse_scan_header(datas[i], sizes[i], &h);
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        int cw, ch;
+        if (rois) {   // the rectangle, and the scale against the file's sampling
+            hjd_internal::RoiGeom rg;
+            rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rois[i], &rg);
+            cw = rois[i].w;
+            ch = rois[i].h;
+        } else {
+            shape.sampling = h.sampling;
+            rc = g->scale != 1 ? hjd_internal::shape_check(shape) : HJD_OK;
+            cw = hjd_internal::scaled_dim(h.width, g->scale);
+            ch = hjd_internal::scaled_dim(h.height, g->scale);
+        }
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        if (cw > hjd_internal::kResizeMaxDim || ch > hjd_internal::kResizeMaxDim)
+            return set_error(HJD_E_INVALID, "frame %d: the crop is %d x %d, the resize takes up to %d", i, cw, ch,
+                             hjd_internal::kResizeMaxDim);
+        if (flags && (flags[i] & ~1))
+            return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: horizontal flip)", i,
+                             static_cast<unsigned>(flags[i] & ~1));
+        pitches[i] = (cw + 3) & ~3;
+        offs[i] = need;
+        need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(ch), 16);
+    }
+    if (need > g->crops_bytes) {   // grow-only; the previous call may still use the old buffer
+        HJD_HIP(hipSetDevice(g->device));
+        if (g->pending) HJD_HIP(hipEventSynchronize(g->done));
+        if (g->d_crops) (void)hipFree(g->d_crops);
+        g->d_crops = nullptr;
+        g->crops_bytes = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&g->d_crops), need) != hipSuccess) {
+            (void)hipGetLastError();
+            g->d_crops = nullptr;
+            return set_error(HJD_E_NOMEM, "the crops of this call need %zu bytes of device memory", need);
+        }
+        g->crops_bytes = need;
+    }
+    std::vector<void*> crops(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
+    ResizeStage stage{d_out, out_w, out_h, out_pitch, flags};
+    GdecCall c = make_call(datas, sizes, n, stream);
+    c.d_outs = crops.data();
+    c.pitches = pitches.data();
+    c.rois = rois;
+    c.resize = &stage;
     return gdec_run(g, c);
 }
 

@@ -26,6 +26,8 @@ struct hjd_gdec {
     int16_t* d_coefs = nullptr;
     uint8_t* d_raw = nullptr;           // raw scan bytes of device-destuffed frames (same offsets as the data area)
     uint32_t* d_tiles = nullptr;        // destuff scratch [3][max_tiles]
+    uint8_t* d_crops = nullptr;         // hjd_gdec_decode_resized: the decoded crops the resize kernel reads;
+    size_t crops_bytes = 0;             // grow-only, (re)allocated by a call that needs more, behind the previous call
     bool spec = false;                  // speculative sync (latency decoders: ent_spec/cand/sync_spec kernels)
     hjd::ent::SpecRec* d_spec = nullptr;   // [max_subs][kMaxBpm]
     hjd::ent::CandRec* d_cand = nullptr;
@@ -74,6 +76,15 @@ struct HostCopy {
     int32_t width, height;
 };
 
+// The second stage of hjd_gdec_decode_resized: the call's d_outs are the crops
+// in the decoder's scratch (HJD_OUT_RGB_PLANAR whatever the decoder's format),
+// and one resize launch takes them to `out` in that format.
+struct ResizeStage {
+    void* out;                 // image i at out + i * 3 * out_pitch * out_h
+    int out_w, out_h, out_pitch;
+    const int32_t* flags;      // per image, or null
+};
+
 // One call of the decoder: everything that belongs to the call and not to
 // the object.  gdec_run reads all of it; gdec_issue (frames already staged in
 // g->st) all but datas, sizes and n.
@@ -88,6 +99,7 @@ struct GdecCall {
     int64_t* block_offsets = nullptr;
     hipStream_t stream = nullptr;
     const HostCopy* host = nullptr;     // per frame, or null
+    const ResizeStage* resize = nullptr;   // hjd_gdec_decode_resized, or null
     // early pull of a latency decoder's lone image (gdec_early_pull)
     hjd_gdec* early_g = nullptr;        // non-null while the call's host destuff may pull
     size_t prepulled = 0;               // data-area bytes of frame 0 already pulled

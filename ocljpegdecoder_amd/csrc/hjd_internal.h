@@ -215,6 +215,25 @@ inline FrameTable frame_table(int nframes, bool roi, bool norm)
     return t;
 }
 
+// The resize kernel (hjd_resize.hip; include/hjd.h hjd_resize_*).  One image's
+// record as the kernel reads it (layout of hjd::ResizeDev and of
+// hjd_resize_item): planar uint8 source w x h at `pitch`, destination plane R.
+struct ResizeRecord {
+    const void* src;
+    void* dst;
+    int32_t w, h, pitch, flags;
+};
+constexpr int kResizeMaxDim = 16384;      // source and output dimensions: 1..16384 (32-bit arithmetic)
+constexpr int kResizeMaxItems = 1 << 20;  // images per launch
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: the output's
+// side of hjd_resize_check (n, format, size, pitch), and one item's.
+int resize_out_check(int n, int out_w, int out_h, int out_pitch, int out_format);
+int resize_item_check(const ResizeRecord& it, int index, int out_format);
+// One resize_kernel launch over n records in device memory (no host
+// synchronisation); the arguments have passed the two checks.
+int launch_resize(int device, const ResizeRecord* d_items, int n, int out_w, int out_h, int out_pitch, int out_format,
+                  const NormRecord& norm, void* stream);
+
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe
 // the whole image; the rest the scan.

@@ -18,6 +18,7 @@
 // 16-byte BGRX stores (two 512-byte row segments per wave instruction).
 #pragma once
 #include "hjd_device.hpp"
+#include "hjd_norm.hpp"
 
 namespace hjd {
 
@@ -264,14 +265,8 @@ template <int kVariant>
 constexpr int kOutBytes = (kVariant & kOutF32) != 0 ? 4 : (kVariant & kOutF16) != 0 ? 2 : (kVariant & kOutPlanar) != 0 ? 1
                           : (kVariant & (kOutBgr24 | kOutRgb24)) != 0 ? 3 : 4;
 
-// The plan-level constants of the float formats, per channel R, G, B: the
-// 32-byte record that follows the frame table (and the RoiDev table of a ROI
-// plan).  Only the float instantiations read it.
-struct NormDev {
-    float a[3], b[3];
-    float reserved[2];   // 0
-};
-static_assert(sizeof(NormDev) == 32, "NormDev layout");
+// (NormDev, the constants' record, and norm_px / half_bits / pack_half2, the
+// formats' arithmetic, are in hjd_norm.hpp: the resize kernel shares them.)
 
 // Once per wave, with scalar loads.  A gfx9 VALU op reads at most one SGPR
 // and each fma takes a[c] from one, so b has to be in a VGPR: kPinB keeps it
@@ -289,36 +284,6 @@ __device__ __forceinline__ NormDev norm_load(const FrameDev* __restrict__ fr, in
         for (int c = 0; c < 3; ++c) asm("" : "+v"(n.b[c]));
     }
     return n;
-}
-
-// Channel c (0 R, 1 G, 2 B) of BGRX word p as the normalised fp32 value: the
-// byte is converted in place (v_cvt_f32_ubyte2/1/0), then one fused
-// multiply-add, correctly rounded (never a multiply followed by an add).
-template <int kC>
-__device__ __forceinline__ float norm_px(uint32_t p, const NormDev& nk)
-{
-    return __builtin_fmaf(static_cast<float>((p >> (16 - 8 * kC)) & 0xffu), nk.a[kC], nk.b[kC]);
-}
-// fp32 -> IEEE half in the low 16 bits, rounded to nearest-even under the
-// kernels' default mode (overflow to inf, subnormals kept).  The instruction
-// is spelled out so that the fp32 value -- the definition's first rounding --
-// exists: left to the compiler, the convert folds into v_fma_mixlo_f16 or
-// pairs up as gfx950's v_cvt_pk_f16_f32, and the latter's results differed
-// from fp32-then-half rounding on MI355X where the fp32 value is a half tie
-// (tests/test_gpu_norm_outputs.py test_half_is_rounded_twice).
-__device__ __forceinline__ uint32_t half_bits(float f)
-{
-    uint32_t w;
-    asm("v_cvt_f16_f32_e32 %0, %1" : "=v"(w) : "v"(f));
-    return w;
-}
-// Two fp32 values as two halves in one dword (low half first): the second
-// convert writes the high half in place (SDWA), so no pack instruction.
-__device__ __forceinline__ uint32_t pack_half2(float lo, float hi)
-{
-    uint32_t w = half_bits(lo);
-    asm("v_cvt_f16_f32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(w) : "v"(hi));
-    return w;
 }
 
 // store4 of the float formats, one channel: kFull, the lane's four pixels as

@@ -1,0 +1,188 @@
+// hjd_resize.hip -- the resize object of include/hjd.h (hjd_resize_*) and the
+// launch of hjd::resize_kernel, which the GPU decoder's resized decode
+// (hjd_gdec.hip) shares.  DESIGN.md s3.9.
+#include "hjd_resize.hpp"
+
+#include <cstring>
+#include <new>
+
+#include "hjd.h"
+#include "hjd_internal.h"
+
+using hjd_internal::set_error;
+
+#define HJD_HIP(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+static_assert(sizeof(hjd_resize_item) == sizeof(hjd::ResizeDev) && offsetof(hjd_resize_item, dst) == 8 &&
+                  offsetof(hjd_resize_item, src_w) == 16 && offsetof(hjd_resize_item, flags) == 28,
+              "hjd_resize_item is the kernel's record");
+static_assert(sizeof(hjd_internal::ResizeRecord) == sizeof(hjd::ResizeDev), "ResizeRecord is the kernel's record");
+static_assert(sizeof(hjd_internal::NormRecord) == sizeof(hjd::NormDev), "NormRecord is the kernel's record");
+
+struct hjd_resize {
+    int device = 0;
+    int n = 0, out_w = 0, out_h = 0, out_pitch = 0, out_format = 0;
+    hjd::ResizeDev* d_items = nullptr;
+    hjd_internal::NormRecord norm = hjd_internal::norm_identity();
+};
+
+namespace {
+
+inline bool dim_ok(int d) { return d >= 1 && d <= hjd_internal::kResizeMaxDim; }
+
+// Groups of 256 threads per image: one quad per thread up to kMaxGroups
+// groups, beyond that the threads loop.
+constexpr int kMaxGroups = 256;
+int resize_groups(int out_w, int out_h)
+{
+    const int64_t quads = static_cast<int64_t>((out_w + 3) / 4) * out_h;
+    const int64_t g = (quads + hjd::kResizeThreads - 1) / hjd::kResizeThreads;
+    return static_cast<int>(g < kMaxGroups ? g : kMaxGroups);
+}
+
+}  // namespace
+
+int hjd_internal::resize_out_check(int n, int out_w, int out_h, int out_pitch, int out_format)
+{
+    if (n < 1 || n > kResizeMaxItems)
+        return set_error(HJD_E_INVALID, "resize: n = %d is outside 1..%d", n, kResizeMaxItems);
+    if (!out_format_planar(out_format))
+        return set_error(HJD_E_INVALID,
+                         "resize: output format %d is not HJD_OUT_RGB_PLANAR, HJD_OUT_RGB_PLANAR_F16 or _F32", out_format);
+    if (!dim_ok(out_w) || !dim_ok(out_h))
+        return set_error(HJD_E_INVALID, "resize: output size %d x %d is outside 1..%d", out_w, out_h, kResizeMaxDim);
+    const int elem = out_format_row_bytes(out_format);
+    if (out_pitch < elem * out_w || (out_pitch & out_format_pitch_mask(out_format)))
+        return set_error(HJD_E_INVALID, "resize: out_pitch %d must be >= %d (%d bytes x out_w) and a multiple of %d",
+                         out_pitch, elem * out_w, elem, elem);
+    return HJD_OK;
+}
+
+int hjd_internal::resize_item_check(const ResizeRecord& it, int index, int out_format)
+{
+    if (!it.src || !it.dst) return set_error(HJD_E_INVALID, "resize item %d: src or dst is NULL", index);
+    if (reinterpret_cast<uintptr_t>(it.dst) & out_format_align_mask(out_format))
+        return set_error(HJD_E_INVALID, "resize item %d: dst must be a multiple of the element size (%d bytes)", index,
+                         out_format_row_bytes(out_format));
+    if (!dim_ok(it.w) || !dim_ok(it.h))
+        return set_error(HJD_E_INVALID, "resize item %d: source size %d x %d is outside 1..%d", index, it.w, it.h,
+                         kResizeMaxDim);
+    if (it.pitch < it.w)
+        return set_error(HJD_E_INVALID, "resize item %d: src_pitch %d is below src_w %d", index, it.pitch, it.w);
+    if (it.flags & ~hjd::kResizeFlipH)
+        return set_error(HJD_E_INVALID, "resize item %d: unknown flag bits 0x%x (bit 0: horizontal flip)", index,
+                         static_cast<unsigned>(it.flags & ~hjd::kResizeFlipH));
+    return HJD_OK;
+}
+
+int hjd_internal::launch_resize(int device, const ResizeRecord* d_items, int n, int out_w, int out_h, int out_pitch,
+                                int out_format, const NormRecord& norm, void* stream)
+{
+    HJD_HIP(hipSetDevice(device));
+    hjd::NormDev nk;
+    memcpy(&nk, &norm, sizeof(nk));
+    const int groups = resize_groups(out_w, out_h);
+    const dim3 grid(static_cast<uint32_t>(n) * static_cast<uint32_t>(groups)), block(hjd::kResizeThreads);
+    const hjd::ResizeDev* items = reinterpret_cast<const hjd::ResizeDev*>(d_items);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (out_format) {
+    case HJD_OUT_RGB_PLANAR:
+        hipLaunchKernelGGL(hjd::resize_kernel<0>, grid, block, 0, s, items, groups, out_w, out_h, out_pitch, nk);
+        break;
+    case HJD_OUT_RGB_PLANAR_F16:
+        hipLaunchKernelGGL(hjd::resize_kernel<hjd::kResizeOutF16>, grid, block, 0, s, items, groups, out_w, out_h,
+                           out_pitch, nk);
+        break;
+    case HJD_OUT_RGB_PLANAR_F32:
+        hipLaunchKernelGGL(hjd::resize_kernel<hjd::kResizeOutF32>, grid, block, 0, s, items, groups, out_w, out_h,
+                           out_pitch, nk);
+        break;
+    default:
+        return set_error(HJD_E_INVALID, "resize: output format %d has no kernel", out_format);   // (no fallback)
+    }
+    HJD_HIP(hipGetLastError());
+    return HJD_OK;
+}
+
+extern "C" {
+
+int hjd_resize_check(const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch, int out_format)
+{
+    if (!items) return set_error(HJD_E_INVALID, "resize: items is NULL");
+    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, out_format);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+        hjd_internal::ResizeRecord r;
+        memcpy(&r, &items[i], sizeof(r));
+        rc = hjd_internal::resize_item_check(r, i, out_format);
+        if (rc) return rc;
+    }
+    return HJD_OK;
+}
+
+int hjd_resize_create(hjd_ctx* ctx, const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch,
+                      int out_format, hjd_resize** out)
+{
+    if (!ctx || !out) return set_error(HJD_E_INVALID, "resize: ctx or out is NULL");
+    *out = nullptr;
+    int rc = hjd_resize_check(items, n, out_w, out_h, out_pitch, out_format);
+    if (rc) return rc;
+    hjd_resize* r = new (std::nothrow) hjd_resize;
+    if (!r) return set_error(HJD_E_NOMEM, "resize allocation");
+    r->device = hjd_ctx_device(ctx);
+    r->n = n;
+    r->out_w = out_w;
+    r->out_h = out_h;
+    r->out_pitch = out_pitch;
+    r->out_format = out_format;
+    const size_t bytes = sizeof(hjd::ResizeDev) * static_cast<size_t>(n);
+    hipError_t e = hipSetDevice(r->device);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_items), bytes);
+    if (e == hipSuccess) e = hipMemcpy(r->d_items, items, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hjd_resize_destroy(r);
+        return set_error(e == hipErrorOutOfMemory ? HJD_E_NOMEM : HJD_E_HIP, "resize table upload: %s",
+                         hipGetErrorString(e));
+    }
+    *out = r;
+    return HJD_OK;
+}
+
+int hjd_resize_set_normalize(hjd_resize* r, const float a[3], const float b[3])
+{
+    const int rc = hjd_internal::norm_check(a, b);
+    if (rc) return rc;
+    if (!r) return set_error(HJD_E_INVALID, "resize is NULL");
+    if (!hjd_internal::out_format_float_bytes(r->out_format))
+        return set_error(HJD_E_INVALID, "hjd_resize_set_normalize: output format %d is not HJD_OUT_RGB_PLANAR_F16 / _F32",
+                         r->out_format);
+    for (int c = 0; c < 3; ++c) {   // a launch argument: an enqueued launch keeps its own
+        r->norm.a[c] = a[c];
+        r->norm.b[c] = b[c];
+    }
+    return HJD_OK;
+}
+
+int hjd_resize_launch(hjd_resize* r, void* stream)
+{
+    if (!r) return set_error(HJD_E_INVALID, "resize is NULL");
+    return hjd_internal::launch_resize(r->device, reinterpret_cast<const hjd_internal::ResizeRecord*>(r->d_items), r->n,
+                                       r->out_w, r->out_h, r->out_pitch, r->out_format, r->norm, stream);
+}
+
+int hjd_resize_destroy(hjd_resize* r)
+{
+    if (!r) return HJD_OK;
+    if (r->d_items) {
+        (void)hipSetDevice(r->device);
+        (void)hipFree(r->d_items);   // (waits for the launches that read the table)
+    }
+    delete r;
+    return HJD_OK;
+}
+
+}  // extern "C"

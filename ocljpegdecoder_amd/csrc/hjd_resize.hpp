@@ -1,0 +1,158 @@
+// hjd_resize.hpp -- the resize kernel for gfx950 (include/hjd.h hjd_resize_*;
+// DESIGN.md s3.9): n planar uint8 RGB images, each of its own size, resampled
+// (bilinear, half-pixel centres, 11-bit integer weights, one rounding) to one
+// common out_w x out_h, flipped where asked, and written as planar uint8 or
+// normalised half / float planes.
+//
+// Work decomposition: every image has the same output, so every image gets the
+// same number of 256-thread groups (gridDim.x = n * groups) and the image of
+// a group is blockIdx.x / groups -- group-uniform, its record read with scalar
+// loads.  A lane produces quads: 4 horizontally adjacent output pixels of one
+// row, all three channels; the quads of an image are dealt to its groups'
+// threads round-robin, so consecutive lanes write consecutive 4-pixel pieces
+// of a row.  The 48 taps of a quad are read straight from the source planes
+// (byte loads, any pointer and pitch): the crops are small and were written by
+// the kernel before this one, so they sit in L2.  No LDS, no barrier.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hjd_norm.hpp"
+
+namespace hjd {
+
+constexpr int kResizeThreads = 256;
+constexpr int kResizeFlipH = 1;        // hjd_resize_item.flags bit 0
+constexpr int kResizeOutF16 = 1;       // resize_kernel<kFormat>: 0 bytes, else one of these
+constexpr int kResizeOutF32 = 2;
+constexpr int kResizeWeightBits = 11;
+
+// Device record of one image: the layout of hjd_resize_item.
+struct ResizeDev {
+    const uint8_t* src;   // plane R; G and B follow at pitch * h
+    uint8_t* dst;         // plane R of the output; G and B follow at out_pitch * out_h
+    int32_t w, h, pitch, flags;
+};
+static_assert(sizeof(ResizeDev) == 32, "ResizeDev layout");
+
+// Source sample position of output index j on one axis (size -> out_size):
+// the first tap p0 and the weight f (0..2047) of the second tap min(p0 + 1,
+// size - 1).  Every product stays below 2^31 for sizes up to 16384.
+__device__ __forceinline__ void resize_tap(uint32_t j, uint32_t size, uint32_t out_size, uint32_t& p0, uint32_t& f)
+{
+    const int32_t s = static_cast<int32_t>((2 * j + 1) * size) - static_cast<int32_t>(out_size);
+    const uint32_t n = static_cast<uint32_t>(s > 0 ? s : 0), den = 2 * out_size;
+    p0 = n / den;
+    f = ((n - p0 * den) << kResizeWeightBits) / den;
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeDev* __restrict__ items, int groups,
+                                                                 int out_w, int out_h, int out_pitch, NormDev nk)
+{
+    constexpr int kElem = kFormat == kResizeOutF32 ? 4 : kFormat == kResizeOutF16 ? 2 : 1;
+    typedef __attribute__((address_space(1))) uint8_t gbyte;
+    typedef __attribute__((address_space(1))) const uint8_t gcbyte;
+    const uint32_t img = blockIdx.x / static_cast<uint32_t>(groups);
+    const uint32_t grp = blockIdx.x - img * static_cast<uint32_t>(groups);
+    const ResizeDev it = items[img];   // group-uniform: scalar loads
+    const uint32_t w = static_cast<uint32_t>(it.w), h = static_cast<uint32_t>(it.h);
+    const uint32_t wo = static_cast<uint32_t>(out_w), ho = static_cast<uint32_t>(out_h);
+    const int64_t splane = static_cast<int64_t>(it.pitch) * it.h;
+    const int64_t dplane = static_cast<int64_t>(out_pitch) * out_h;
+    const bool flip = (it.flags & kResizeFlipH) != 0;
+    // whole quads as one dword / dwordx2 / dwordx4 per plane (group-uniform)
+    const bool vec = ((reinterpret_cast<uintptr_t>(it.dst) | static_cast<uintptr_t>(out_pitch)) & (4 * kElem - 1)) == 0 &&
+                     (wo & 3) == 0;
+    const uint32_t qw = (wo + 3) >> 2, quads = qw * ho;
+    for (uint32_t q = grp * kResizeThreads + threadIdx.x; q < quads; q += static_cast<uint32_t>(groups) * kResizeThreads) {
+        const uint32_t i = q / qw, j0 = 4 * (q - i * qw);
+        uint32_t y0, fy;
+        resize_tap(i, h, ho, y0, fy);
+        const uint32_t y1 = min(y0 + 1, h - 1);
+        // (global, not flat, addresses: the record's pointers are device memory)
+        const gcbyte* r0 = (const gcbyte*)it.src + static_cast<int64_t>(y0) * it.pitch;
+        const gcbyte* r1 = (const gcbyte*)it.src + static_cast<int64_t>(y1) * it.pitch;
+        uint32_t px[4];   // 0x00RRGGBB, as the pixel kernels' BGRX words
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // (a column past out_w on the guarded path: clamped, computed, not stored)
+            const uint32_t j = min(j0 + k, wo - 1);
+            uint32_t x0, fx;
+            resize_tap(flip ? wo - 1 - j : j, w, wo, x0, fx);
+            const uint32_t x1 = min(x0 + 1, w - 1);
+            uint32_t p = 0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const gcbyte* a = r0 + c * splane;
+                const gcbyte* b = r1 + c * splane;
+                const uint32_t top = a[x0] * (2048u - fx) + a[x1] * fx;
+                const uint32_t bot = b[x0] * (2048u - fx) + b[x1] * fx;
+                p = (p << 8) | ((top * (2048u - fy) + bot * fy + (1u << 21)) >> 22);
+            }
+            px[k] = p;
+        }
+        gbyte* d = (gbyte*)it.dst + static_cast<int64_t>(i) * out_pitch + static_cast<int64_t>(j0) * kElem;
+        if constexpr (kFormat == 0) {
+            if (vec) {
+                typedef __attribute__((address_space(1))) uint32_t gword;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int sh = 16 - 8 * c;
+                    const uint32_t v = ((px[0] >> sh) & 0xffu) | (((px[1] >> sh) & 0xffu) << 8) |
+                                       (((px[2] >> sh) & 0xffu) << 16) | (((px[3] >> sh) & 0xffu) << 24);
+                    __builtin_nontemporal_store(v, (gword*)(d + c * dplane));
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (j0 + k < wo) {
+                        d[k] = static_cast<uint8_t>(px[k] >> 16);
+                        d[dplane + k] = static_cast<uint8_t>(px[k] >> 8);
+                        d[2 * dplane + k] = static_cast<uint8_t>(px[k]);
+                    }
+            }
+        } else {
+            float f[3][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                f[0][k] = norm_px<0>(px[k], nk);
+                f[1][k] = norm_px<1>(px[k], nk);
+                f[2][k] = norm_px<2>(px[k], nk);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                gbyte* dc = d + c * dplane;
+                if constexpr (kFormat == kResizeOutF16) {
+                    if (vec) {
+                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                        typedef __attribute__((address_space(1))) u32x2 gvec2;
+                        const u32x2 v = {pack_half2(f[c][0], f[c][1]), pack_half2(f[c][2], f[c][3])};
+                        __builtin_nontemporal_store(v, (gvec2*)dc);
+                    } else {
+                        typedef __attribute__((address_space(1))) uint16_t ghalf;
+                        ghalf* e = (ghalf*)dc;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (j0 + k < wo) e[k] = static_cast<uint16_t>(half_bits(f[c][k]));
+                    }
+                } else {
+                    if (vec) {
+                        typedef float f32x4 __attribute__((ext_vector_type(4)));
+                        typedef __attribute__((address_space(1))) f32x4 gvec4;
+                        const f32x4 v = {f[c][0], f[c][1], f[c][2], f[c][3]};
+                        __builtin_nontemporal_store(v, (gvec4*)dc);
+                    } else {
+                        typedef __attribute__((address_space(1))) float gfloat;
+                        gfloat* e = (gfloat*)dc;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (j0 + k < wo) e[k] = f[c][k];
+                    }
+                }
+            }
+        }
+    }
+}
+
+}  // namespace hjd

@@ -355,6 +355,36 @@ class GpuDecoder:
                                                _stream_handle(stream)), "hjd_gdec_decode_roi")
         self._n = n
 
+    def decode_resized(self, datas: Sequence[bytes], out, stream=None, rois=None, flips=None):
+        """hjd_gdec_decode_resized: decode, crop (rois, one (x, y, w, h) per
+        image on the grid of the decoder's scale, of any sizes; None: whole
+        frames), resize every crop to out's (Ho, Wo) and flip where flips[i]
+        is set, into `out`, a contiguous device tensor (N, 3, Ho, Wo) whose
+        dtype is the decoder's current planar format's.  The crops pass
+        through a scratch the decoder owns: a call that needs a larger one
+        than any before waits for the previous call and reallocates."""
+        _keep, arr_d, arr_s = _byte_arrays(datas)
+        n = len(datas)
+        if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
+            raise ValueError(f"out must be a contiguous device tensor ({n}, 3, Ho, Wo)")
+        elem = {3: 1, 5: 2, 6: 4}.get(self.out_format)   # the planar formats (any other: the library refuses)
+        if elem is not None and out.element_size() != elem:
+            raise ValueError(f"out's dtype {out.dtype} is not the decoder's output format ({self.out_format})")
+        rects = fl = None
+        if rois is not None:
+            if len(rois) != n:
+                raise ValueError("one ROI per JPEG")
+            rects = (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
+        if flips is not None:
+            if len(flips) != n:
+                raise ValueError("one flip flag per JPEG")
+            fl = (ctypes.c_int32 * n)(*[1 if f else 0 for f in flips])
+        ho, wo = int(out.shape[2]), int(out.shape[3])
+        check(self.lib.hjd_gdec_decode_resized(self.handle, arr_d, arr_s, n, rects, fl, out.data_ptr(), wo, ho,
+                                               wo * out.element_size(), _stream_handle(stream)),
+              "hjd_gdec_decode_resized")
+        self._n = n
+
     def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1,
                    rois=None, dtype=_UINT8, mean=None, std=None):
         """Decode to RGB tensors: layout "chw" gives (3, H, W) per image
@@ -375,26 +405,11 @@ class GpuDecoder:
         `out` every ROI's (h, w) must equal out's while the files' own sizes
         may differ.  Asynchronous like
         decode(): call sync() before reading.  The decoder's output format
-        and constants are restored afterwards."""
+        and constants are restored afterwards.  decode_rgb_resized() resizes
+        images of different sizes into one batch."""
         import torch
-        from .backend import (OUT_RGB24, OUT_RGB_PLANAR, OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32, norm_constants,
-                              scaled_size)
-        if layout not in ("chw", "hwc"):
-            raise ValueError('layout must be "chw" or "hwc"')
-        chw = layout == "chw"
-        if dtype is None:
-            dtype = torch.uint8
-        if dtype not in (torch.uint8, torch.float16, torch.float32):
-            raise ValueError("dtype must be torch.uint8, torch.float16 or torch.float32")
-        if dtype == torch.uint8:
-            if mean is not None or std is not None:
-                raise ValueError("mean and std need dtype torch.float16 or torch.float32")
-            fmt, norm = (OUT_RGB_PLANAR if chw else OUT_RGB24), None
-        else:
-            if not chw:
-                raise ValueError('the float dtypes are planar: layout must be "chw"')
-            fmt = OUT_RGB_PLANAR_F16 if dtype == torch.float16 else OUT_RGB_PLANAR_F32
-            norm = norm_constants(mean, std)
+        from .backend import scaled_size
+        chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
         infos = []
         for d in datas:   # headers only; any input decode() takes (bytes, arrays, pinned tensors)
             addr, size, _k = _ptr_size(d)
@@ -421,19 +436,73 @@ class GpuDecoder:
                     raise ValueError(f"image {k} is {w}x{h}" + (f" at scale {scale}" if scale != 1 else "") +
                                      f", out is {ow}x{oh}")
             outs = [out[k] for k in range(len(infos))]
+        return self._with_settings(scale, fmt, norm, lambda: self.decode(datas, outs, stream, rois=rois),
+                                   outs if out is None else out)
+
+    def _with_settings(self, scale, fmt, norm, call, result):
+        """Run `call` at this scale, output format and constants (norm, or
+        None: untouched), restore the decoder's own and return `result`."""
         prev, prev_scale, prev_norm = self.out_format, self.scale, self.normalize
         self.set_scale(scale)
         self.set_output_format(fmt)
         try:
             if norm is not None:
                 self.set_normalize(*norm)
-            self.decode(datas, outs, stream, rois=rois)
+            call()
         finally:
             self.set_output_format(prev)
             self.set_scale(prev_scale)
             if norm is not None:
                 self.set_normalize(*prev_norm)
-        return outs if out is None else out
+        return result
+
+    @staticmethod
+    def _rgb_format(layout, dtype, mean, std):
+        """(chw, dtype, output format, constants or None) of decode_rgb's arguments."""
+        import torch
+        from .backend import OUT_RGB24, OUT_RGB_PLANAR, OUT_RGB_PLANAR_F16, OUT_RGB_PLANAR_F32, norm_constants
+        if layout not in ("chw", "hwc"):
+            raise ValueError('layout must be "chw" or "hwc"')
+        chw = layout == "chw"
+        if dtype is None:
+            dtype = torch.uint8
+        if dtype not in (torch.uint8, torch.float16, torch.float32):
+            raise ValueError("dtype must be torch.uint8, torch.float16 or torch.float32")
+        if dtype == torch.uint8:
+            if mean is not None or std is not None:
+                raise ValueError("mean and std need dtype torch.float16 or torch.float32")
+            return chw, dtype, (OUT_RGB_PLANAR if chw else OUT_RGB24), None
+        if not chw:
+            raise ValueError('the float dtypes are planar: layout must be "chw"')
+        return chw, dtype, (OUT_RGB_PLANAR_F16 if dtype == torch.float16 else OUT_RGB_PLANAR_F32), \
+            norm_constants(mean, std)
+
+    def decode_rgb_resized(self, datas: Sequence[bytes], size, flips=None, layout: str = "chw", out=None, stream=None,
+                           scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None):
+        """decode_rgb with size = (h, w): every image -- its ROI, of any size,
+        or its whole (scaled) frame -- is resized to h x w on the GPU
+        (decode_resized: bilinear, no antialiasing; resize_scale() gives the
+        `scale` that keeps the reduction within 2x) and mirrored horizontally
+        where flips[i] is set, and ONE (N, 3, h, w) tensor of the dtype comes
+        back: `out` if given (a contiguous device tensor of exactly that shape
+        and dtype), else a new one.  dtype, mean, std, scale and rois as
+        decode_rgb; layout "chw" only ("hwc" is a ValueError: the batch is
+        planar).  Asynchronous; the decoder's format, scale and constants are
+        restored afterwards."""
+        import torch
+        chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
+        if not chw:
+            raise ValueError('a resized batch is planar: layout must be "chw"')
+        size = (int(size[0]), int(size[1]))
+        if min(size) < 1:
+            raise ValueError(f"size must be (h, w) with h, w >= 1, got {size}")
+        shape = (len(datas), 3) + size
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.ctx.device))
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == shape):
+            raise ValueError(f"out must be a contiguous {dtype} device tensor {shape}")
+        return self._with_settings(scale, fmt, norm,
+                                   lambda: self.decode_resized(datas, out, stream, rois=rois, flips=flips), out)
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
