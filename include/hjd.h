@@ -386,6 +386,57 @@ int hjd_resize_set_normalize(hjd_resize* r, const float a[3], const float b[3]);
 int hjd_resize_launch(hjd_resize* r, void* stream);
 int hjd_resize_destroy(hjd_resize* r);
 
+/*
+ * The antialiased filter (HJD_RESIZE_TRIANGLE_AA): what Resize(antialias=True)
+ * of an image library computes, as an exact integer definition.  Sources,
+ * flags, output formats, pitches and store forms are those above; only the
+ * resampling differs.
+ *
+ * Definition: the triangle (bilinear) filter widened to the reduction,
+ * separable -- a horizontal pass over every source row, its result rounded to
+ * uint8, then a vertical pass, rounded again (as Pillow's and torch's uint8
+ * paths).  One axis, source size w, output size Wo, output index j (y the
+ * same with src_h, out_h, i):
+ *     S   = max(w, Wo)
+ *     d_k = (2k + 1) Wo - (2j + 1) w            for source index k, 0 <= k < w
+ *     t_k = 2S - |d_k|                          the taps are exactly the k with t_k > 0
+ *     T   = sum of t_k over the taps
+ *     u8  = floor((sum of t_k p_k + floor(T / 2)) / T)
+ * -- the triangle centred at (2j + 1) w / (2 Wo) with support max(w / Wo, 1),
+ * its weights exact rationals renormalised over the taps inside the image:
+ * interpolate(mode = "bilinear", antialias = true, align_corners = false)
+ * without its float rounding.  For Wo >= w it is exact two-tap bilinear
+ * (T = 2 Wo where neither tap falls outside the image), for Wo == w the
+ * identity; the centre tap always lies inside the image, so T > 0.  flags
+ * bit 0: output column j holds the unflipped result's column out_w - 1 - j
+ * (applied in the horizontal pass).  The float formats are
+ * fma((float)u8, a[c], b[c]) of the final bytes.
+ *
+ * 32-bit bound: (2j + 1) w + 2S < 2^31 for dimensions up to 16384, and
+ * T <= 2 S^2 / Wo + 2S, so the accumulator 255 T + T / 2 stays below 2^31
+ * whenever S^2 <= 2^21 Wo.  That is the filter's one extra rule, per axis,
+ * compared in 64 bits: src_w^2 <= 2^21 out_w and src_h^2 <= 2^21 out_h, else
+ * HJD_E_INVALID with a message naming the axis (a 16384-wide source needs
+ * out_w >= 128; everything up to 1448 wide may go to 1 pixel).
+ *
+ * Two launches on the same stream through a uint8 intermediate in device
+ * memory (per item three planes of src_h rows x out_w bytes, the pitch out_w
+ * rounded up to 4, each item 16-byte aligned).  An hjd_resize object of this
+ * filter allocates its intermediate at create (HJD_E_NOMEM if that fails;
+ * nothing is leaked) and hjd_resize_destroy frees it; set_normalize, launch
+ * and destroy work on it unchanged.  All launches of one such object share
+ * that intermediate: the caller orders them (the same stream, or events).
+ *
+ * hjd_resize_check_filter / hjd_resize_create_filter with filter ==
+ * HJD_RESIZE_BILINEAR are exactly hjd_resize_check / hjd_resize_create; any
+ * filter other than the two is HJD_E_INVALID.
+ */
+enum { HJD_RESIZE_BILINEAR = 0, HJD_RESIZE_TRIANGLE_AA = 1 };
+int hjd_resize_check_filter(const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch, int out_format,
+                            int filter);
+int hjd_resize_create_filter(hjd_ctx* ctx, const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch,
+                             int out_format, int filter, hjd_resize** out);
+
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */
 int hjd_idct_blocks(hjd_ctx* ctx, const int32_t* d_in, int32_t* d_out, int64_t nblocks, void* stream);
@@ -471,6 +522,12 @@ int hjd_debug_set_tuning(const char* name, const char* value);
 int hjd_debug_kernel_key(int sampling, int input_format, int out_format, int scale, int roi, int variant, int stages,
                          int kernel_mode, int64_t tasks, int grid_blocks, int d16, int32_t key[4]);
 int hjd_debug_kernel_table(int32_t* keys, int cap);
+
+/* Timing only: enqueue ONE of the two launches of an HJD_RESIZE_TRIANGLE_AA
+ * object -- pass 0 the horizontal kernel (sources -> intermediate), pass 1 the
+ * vertical one (intermediate -> outputs, reading whatever the intermediate
+ * holds).  HJD_E_INVALID for another pass or a bilinear object. */
+int hjd_debug_resize_launch_pass(hjd_resize* r, int pass, void* stream);
 
 #ifdef __cplusplus
 }

@@ -226,6 +226,18 @@ int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* 
  * (hjd_stream, hjd_gstream) do not serve a resized decode. */
 int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                             const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream);
+/* hjd_gdec_decode_resized with the resize's filter (include/hjd.h):
+ * HJD_RESIZE_BILINEAR is exactly the call above, HJD_RESIZE_TRIANGLE_AA the
+ * antialiased triangle filter, any other value HJD_E_INVALID.  The
+ * antialiased filter adds its ratio rule per image (crop_w^2 <= 2^21 out_w,
+ * crop_h^2 <= 2^21 out_h), refused like everything else before anything is
+ * staged, allocated or enqueued, and follows the pixel kernels with two
+ * launches; their intermediate (hjd.h) lies behind the crops in the same
+ * grow-only scratch, under the same rule: a call that must grow it waits for
+ * the previous call and reallocates, calls that fit stay asynchronous. */
+int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                   const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
+                                   int32_t out_pitch, int filter, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

@@ -47,6 +47,8 @@ from .backend import (  # noqa: E402
     norm_constants,
     Resize,
     RESIZE_FLIP_H,
+    RESIZE_BILINEAR,
+    RESIZE_TRIANGLE_AA,
     resize_scale,
     roi_geometry,
     scaled_size,
@@ -64,6 +66,6 @@ __all__ = [
     "parse", "pinned_bytes",
     "Context", "FrameSpec", "Plan", "autotune_cache_clear", "decode_frame", "device_count", "frame_blocks", "mcu_geometry", "worker_cpus", "cpu_share", "debug_tuning",
     "device_worker_cpus", "stream_worker_threads", "scaled_size", "roi_geometry", "norm_constants", "frame_check",
-    "OUT_RGB_PLANAR_F16", "OUT_RGB_PLANAR_F32", "Resize", "RESIZE_FLIP_H", "resize_scale",
+    "OUT_RGB_PLANAR_F16", "OUT_RGB_PLANAR_F32", "Resize", "RESIZE_FLIP_H", "RESIZE_BILINEAR", "RESIZE_TRIANGLE_AA", "resize_scale",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -132,9 +132,13 @@ SIGNATURES = {
     "hjd_resize_check": (ctypes.c_int, [ctypes.POINTER(HjdResizeItem)] + [ctypes.c_int] * 5),
     "hjd_resize_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdResizeItem)] + [ctypes.c_int] * 5 +
                           [ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_resize_check_filter": (ctypes.c_int, [ctypes.POINTER(HjdResizeItem)] + [ctypes.c_int] * 6),
+    "hjd_resize_create_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdResizeItem)] + [ctypes.c_int] * 6 +
+                                 [ctypes.POINTER(ctypes.c_void_p)]),
     "hjd_resize_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
                                                 ctypes.POINTER(ctypes.c_float)]),
     "hjd_resize_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_debug_resize_launch_pass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "hjd_resize_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
@@ -230,6 +234,10 @@ def _bind_host(lib):
         "hjd_gdec_decode_resized": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
                                                    ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, vp, ctypes.c_int,
                                                    ctypes.c_int, ctypes.c_int32, vp]),
+        "hjd_gdec_decode_resized_filter": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                          ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, vp,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int,
+                                                          vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -399,6 +399,7 @@ class Plan:
 
 
 RESIZE_FLIP_H = 1   # hjd_resize_item.flags bit 0
+RESIZE_BILINEAR, RESIZE_TRIANGLE_AA = 0, 1   # the resize's filter (include/hjd.h)
 _DTYPE_FORMATS = {"torch.uint8": OUT_RGB_PLANAR, "torch.float16": OUT_RGB_PLANAR_F16,
                   "torch.float32": OUT_RGB_PLANAR_F32}
 
@@ -418,16 +419,22 @@ def resize_scale(src_w: int, src_h: int, out_w: int, out_h: int) -> int:
 class Resize:
     """hjd_resize: N planar uint8 RGB images of different sizes -> one
     (N, 3, Ho, Wo) batch in one launch (include/hjd.h: bilinear, half-pixel
-    centres, 11-bit integer weights, no antialiasing; sizes 1..16384)."""
+    centres, 11-bit integer weights, no antialiasing; sizes 1..16384).
+    antialias=True takes the exact triangle filter instead
+    (RESIZE_TRIANGLE_AA: what interpolate(antialias=True) computes, two
+    launches through an intermediate the object owns, so the launches of one
+    object must be ordered, e.g. on one stream; a source dimension d going to
+    o needs d * d <= 2**21 * o)."""
 
-    def __init__(self, ctx: Context, srcs, out, flips=None, normalize=None):
+    def __init__(self, ctx: Context, srcs, out, flips=None, normalize=None, antialias=False):
         """srcs: N device tensors (3, h, w) uint8 (contiguous, or a [..., :w]
         view of wider rows), or (tensor, pitch) pairs: 3 * h rows of `pitch`
         bytes from the tensor's data_ptr, whose shape (3, h, w) gives h and w.
         out: a device tensor (N, 3, Ho, Wo) of uint8, float16 or float32,
         contiguous or a [..., :Wo] view of wider rows.  flips: N truthy
         values, image i mirrored horizontally where set.  normalize = (a, b):
-        the float dtypes' constants (set_normalize; default a = 1, b = 0)."""
+        the float dtypes' constants (set_normalize; default a = 1, b = 0).
+        antialias: the filter, RESIZE_TRIANGLE_AA if true."""
         self.ctx = ctx
         self.lib = ctx.lib
         self.handle = None
@@ -460,8 +467,9 @@ class Resize:
                                           RESIZE_FLIP_H if flips is not None and flips[i] else 0)
         self.out = out
         h = ctypes.c_void_p()
-        check(self.lib.hjd_resize_create(ctx.handle, items, n, wo, ho, pitch, self.out_format, ctypes.byref(h)),
-              "hjd_resize_create")
+        self.filter = RESIZE_TRIANGLE_AA if antialias else RESIZE_BILINEAR
+        check(self.lib.hjd_resize_create_filter(ctx.handle, items, n, wo, ho, pitch, self.out_format, self.filter,
+                                                ctypes.byref(h)), "hjd_resize_create_filter")
         self.handle = h
         if normalize is not None:
             self.set_normalize(*normalize)
@@ -474,6 +482,12 @@ class Resize:
     def launch(self, stream=None):
         """Enqueue the resize kernel (asynchronous)."""
         check(self.lib.hjd_resize_launch(self.handle, _stream_ptr(stream)), "hjd_resize_launch")
+
+    def launch_pass(self, which: int, stream=None):
+        """Timing only (hjd_debug_resize_launch_pass): one launch of an
+        antialias=True object, 0 the horizontal kernel, 1 the vertical one."""
+        check(self.lib.hjd_debug_resize_launch_pass(self.handle, int(which), _stream_ptr(stream)),
+              "hjd_debug_resize_launch_pass")
 
     def close(self):
         if self.handle:

@@ -319,8 +319,16 @@ inline size_t resize_records_offset(int n, bool roi)
     return hjd_internal::align_up(pixel_tables_bytes(n, roi, false), 16);
 }
 
+// Resize records of a resized call: n, or with the antialiased filter 2 n
+// (the horizontal launch's, then the vertical launch's).
+inline size_t resize_records_bytes(int n, const ResizeStage& r)
+{
+    return sizeof(hjd_internal::ResizeRecord) * static_cast<size_t>(n) * (r.mids ? 2 : 1);
+}
+
 // The resize kernel's records of a resized call (ResizeStage): image i from
-// its crop in the scratch (c.d_outs[i], c.pitches[i]) to its place in the batch.
+// its crop in the scratch (c.d_outs[i], c.pitches[i]) to its place in the
+// batch -- with the antialiased filter by way of its intermediate r.mids[i].
 int write_resize_records(hjd_gdec* g, const GdecCall& c)
 {
     Staging& st = g->st;
@@ -341,6 +349,16 @@ int write_resize_records(hjd_gdec* g, const GdecCall& c)
         const int rc = hjd_internal::resize_item_check(rec, i, g->out_format);
         if (rc) return rc;
         recs[i] = rec;
+        if (r.mids) {
+            hjd_internal::ResizeRecord& v = recs[n + i];
+            v.src = r.mids[i];
+            v.dst = rec.dst;
+            v.w = r.out_w;
+            v.h = rec.h;
+            v.pitch = hjd_internal::resize_aa_pitch(r.out_w);
+            v.flags = 0;   // (the flip is the horizontal pass's)
+            recs[i].dst = r.mids[i];
+        }
     }
     return HJD_OK;
 }
@@ -384,7 +402,7 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     const bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
     const size_t recs_bytes = !c.d_outs ? 0
                               : c.resize ? resize_records_offset(n, c.rois != nullptr) +
-                                               sizeof(hjd_internal::ResizeRecord) * static_cast<size_t>(n)
+                                               resize_records_bytes(n, *c.resize)
                                          : pixel_tables_bytes(n, c.rois != nullptr, fnorm);
     EntBatchDev b;
     int rc = st.assemble(g->d_blob, coefs, c.block_offsets, S, recs_bytes,
@@ -572,11 +590,19 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
         }
         if (c.resize) {   // the crops -> the batch, behind the pixel kernels; `done` (below) covers it
             const ResizeStage& r = *c.resize;
-            rc = hjd_internal::launch_resize(
-                g->device,
-                reinterpret_cast<const hjd_internal::ResizeRecord*>(g->d_blob + g->st.H.recs +
-                                                                    resize_records_offset(n, c.rois != nullptr)),
-                n, r.out_w, r.out_h, r.out_pitch, g->out_format, g->norm, s);
+            const hjd_internal::ResizeRecord* recs = reinterpret_cast<const hjd_internal::ResizeRecord*>(
+                g->d_blob + g->st.H.recs + resize_records_offset(n, c.rois != nullptr));
+            if (r.mids) {
+                int max_h = 1;
+                for (int i = 0; i < n; ++i)
+                    max_h = std::max(max_h, c.rois ? c.rois[i].h
+                                                   : hjd_internal::scaled_dim(g->st.frames[i].height, g->scale));
+                rc = hjd_internal::launch_resize_aa(g->device, recs, recs + n, n, max_h, r.out_w, r.out_h, r.out_pitch,
+                                                    g->out_format, g->norm, s);
+            } else {
+                rc = hjd_internal::launch_resize(g->device, recs, n, r.out_w, r.out_h, r.out_pitch, g->out_format,
+                                                 g->norm, s);
+            }
             if (rc) return rc;
         }
     }
@@ -765,10 +791,21 @@ int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* 
 int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                             const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
 {
+    return hjd_gdec_decode_resized_filter(g, datas, sizes, n, rois, flags, d_out, out_w, out_h, out_pitch,
+                                          HJD_RESIZE_BILINEAR, stream);
+}
+
+int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                   const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
+                                   int32_t out_pitch, int filter, void* stream)
+{
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
     // everything that can refuse the call is checked before anything is staged, allocated or enqueued
-    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
+    int rc = hjd_internal::resize_filter_check(filter);
+    if (rc) return rc;
+    const bool aa = filter == HJD_RESIZE_TRIANGLE_AA;
+    rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
         return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
@@ -777,9 +814,10 @@ int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size
         return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
     // the crops in the scratch: each 16-byte aligned, its pitch rounded up to 4
     // (whole strips of the pixel kernel keep their vector stores)
-    std::vector<size_t> offs(static_cast<size_t>(n));
+    // (the antialiased filter's intermediates follow the crops, each 16-byte aligned too)
+    std::vector<size_t> offs(static_cast<size_t>(n)), mid_offs(aa ? static_cast<size_t>(n) : 0);
     std::vector<int32_t> pitches(static_cast<size_t>(n));
-    size_t need = 0;
+    size_t need = 0, mid_need = 0;
     hjd_internal::ScanHeader h;
     hjd_internal::DecodeShape shape;
     shape.scale = g->scale;
@@ -806,10 +844,18 @@ int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size
         if (flags && (flags[i] & ~1))
             return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: horizontal flip)", i,
                              static_cast<unsigned>(flags[i] & ~1));
+        if (aa) {
+            rc = hjd_internal::resize_aa_ratio_check(cw, ch, out_w, out_h, i);
+            if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+            mid_offs[i] = mid_need;
+            mid_need += hjd_internal::resize_aa_item_bytes(out_w, ch);
+        }
         pitches[i] = (cw + 3) & ~3;
         offs[i] = need;
         need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(ch), 16);
     }
+    const size_t mid_base = need;
+    need += mid_need;
     if (need > g->crops_bytes) {   // grow-only; the previous call may still use the old buffer
         HJD_HIP(hipSetDevice(g->device));
         if (g->pending) HJD_HIP(hipEventSynchronize(g->done));
@@ -819,13 +865,16 @@ int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size
         if (hipMalloc(reinterpret_cast<void**>(&g->d_crops), need) != hipSuccess) {
             (void)hipGetLastError();
             g->d_crops = nullptr;
-            return set_error(HJD_E_NOMEM, "the crops of this call need %zu bytes of device memory", need);
+            return set_error(HJD_E_NOMEM, "the crops%s of this call need %zu bytes of device memory",
+                             aa ? " and the resize's intermediate" : "", need);
         }
         g->crops_bytes = need;
     }
     std::vector<void*> crops(static_cast<size_t>(n));
+    std::vector<void*> mids(mid_offs.size());
     for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
-    ResizeStage stage{d_out, out_w, out_h, out_pitch, flags};
+    for (size_t i = 0; i < mids.size(); ++i) mids[i] = g->d_crops + mid_base + mid_offs[i];
+    ResizeStage stage{d_out, out_w, out_h, out_pitch, flags, aa ? mids.data() : nullptr};
     GdecCall c = make_call(datas, sizes, n, stream);
     c.d_outs = crops.data();
     c.pitches = pitches.data();

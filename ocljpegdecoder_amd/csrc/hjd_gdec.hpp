@@ -26,7 +26,8 @@ struct hjd_gdec {
     int16_t* d_coefs = nullptr;
     uint8_t* d_raw = nullptr;           // raw scan bytes of device-destuffed frames (same offsets as the data area)
     uint32_t* d_tiles = nullptr;        // destuff scratch [3][max_tiles]
-    uint8_t* d_crops = nullptr;         // hjd_gdec_decode_resized: the decoded crops the resize kernel reads;
+    uint8_t* d_crops = nullptr;         // hjd_gdec_decode_resized: the decoded crops the resize kernel reads (and,
+                                        // behind them, the antialiased filter's intermediate);
     size_t crops_bytes = 0;             // grow-only, (re)allocated by a call that needs more, behind the previous call
     bool spec = false;                  // speculative sync (latency decoders: ent_spec/cand/sync_spec kernels)
     hjd::ent::SpecRec* d_spec = nullptr;   // [max_subs][kMaxBpm]
@@ -83,6 +84,9 @@ struct ResizeStage {
     void* out;                 // image i at out + i * 3 * out_pitch * out_h
     int out_w, out_h, out_pitch;
     const int32_t* flags;      // per image, or null
+    // HJD_RESIZE_TRIANGLE_AA: image i's intermediate (hjd_resize_aa.hpp) at mids[i]
+    // in the scratch, and two launches; null: the bilinear kernel
+    void* const* mids;
 };
 
 // One call of the decoder: everything that belongs to the call and not to

@@ -234,6 +234,28 @@ int resize_item_check(const ResizeRecord& it, int index, int out_format);
 int launch_resize(int device, const ResizeRecord* d_items, int n, int out_w, int out_h, int out_pitch, int out_format,
                   const NormRecord& norm, void* stream);
 
+// The antialiased filter (HJD_RESIZE_TRIANGLE_AA; hjd_resize_aa.hpp): two
+// launches through a uint8 intermediate, per item three planes of src_h rows at
+// resize_aa_pitch(out_w), the item's resize_aa_item_bytes a multiple of 16.
+inline int resize_aa_pitch(int out_w) { return (out_w + 3) & ~3; }
+inline size_t resize_aa_item_bytes(int out_w, int src_h)
+{
+    return align_up(3 * static_cast<size_t>(resize_aa_pitch(out_w)) * static_cast<size_t>(src_h), 16);
+}
+// HJD_OK, or HJD_E_INVALID: `filter` is neither HJD_RESIZE_BILINEAR nor HJD_RESIZE_TRIANGLE_AA.
+int resize_filter_check(int filter);
+// The filter's one rule of its own, per axis: src^2 <= 2^21 * out (its 32-bit
+// accumulator).  HJD_OK, or HJD_E_INVALID with a message naming the axis.
+int resize_aa_ratio_check(int src_w, int src_h, int out_w, int out_h, int index);
+// Both launches over n record pairs in device memory: d_h[i] = {the source,
+// dst = item i's intermediate}, d_v[i] = {src = that intermediate, the output,
+// w = out_w, h = src_h, pitch = resize_aa_pitch(out_w)}.  max_src_h: the
+// largest src_h, which sizes the horizontal launch.  passes: bit 0 the
+// horizontal launch, bit 1 the vertical one (hjd_debug_resize_launch_pass
+// takes one).  No host synchronisation.
+int launch_resize_aa(int device, const ResizeRecord* d_h, const ResizeRecord* d_v, int n, int max_src_h, int out_w,
+                     int out_h, int out_pitch, int out_format, const NormRecord& norm, void* stream, int passes = 3);
+
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe
 // the whole image; the rest the scan.

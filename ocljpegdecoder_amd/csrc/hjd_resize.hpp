@@ -46,6 +46,76 @@ __device__ __forceinline__ void resize_tap(uint32_t j, uint32_t size, uint32_t o
     f = ((n - p0 * den) << kResizeWeightBits) / den;
 }
 
+// Store one quad: px[k] = 0x00RRGGBB of output columns j0 .. j0 + 3 of one row,
+// d the address of plane R's element j0.  vec: one dword / dwordx2 / dwordx4
+// per plane; else element stores of the columns below wo.  Non-temporal.
+template <int kFormat>
+__device__ __forceinline__ void resize_store_quad(const uint32_t (&px)[4],
+                                                  __attribute__((address_space(1))) uint8_t* d, int64_t dplane, bool vec,
+                                                  uint32_t j0, uint32_t wo, const NormDev& nk)
+{
+    typedef __attribute__((address_space(1))) uint8_t gbyte;
+    if constexpr (kFormat == 0) {
+        if (vec) {
+            typedef __attribute__((address_space(1))) uint32_t gword;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int sh = 16 - 8 * c;
+                const uint32_t v = ((px[0] >> sh) & 0xffu) | (((px[1] >> sh) & 0xffu) << 8) |
+                                   (((px[2] >> sh) & 0xffu) << 16) | (((px[3] >> sh) & 0xffu) << 24);
+                __builtin_nontemporal_store(v, (gword*)(d + c * dplane));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (j0 + k < wo) {
+                    d[k] = static_cast<uint8_t>(px[k] >> 16);
+                    d[dplane + k] = static_cast<uint8_t>(px[k] >> 8);
+                    d[2 * dplane + k] = static_cast<uint8_t>(px[k]);
+                }
+        }
+    } else {
+        float f[3][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            f[0][k] = norm_px<0>(px[k], nk);
+            f[1][k] = norm_px<1>(px[k], nk);
+            f[2][k] = norm_px<2>(px[k], nk);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            gbyte* dc = d + c * dplane;
+            if constexpr (kFormat == kResizeOutF16) {
+                if (vec) {
+                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                    typedef __attribute__((address_space(1))) u32x2 gvec2;
+                    const u32x2 v = {pack_half2(f[c][0], f[c][1]), pack_half2(f[c][2], f[c][3])};
+                    __builtin_nontemporal_store(v, (gvec2*)dc);
+                } else {
+                    typedef __attribute__((address_space(1))) uint16_t ghalf;
+                    ghalf* e = (ghalf*)dc;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (j0 + k < wo) e[k] = static_cast<uint16_t>(half_bits(f[c][k]));
+                }
+            } else {
+                if (vec) {
+                    typedef float f32x4 __attribute__((ext_vector_type(4)));
+                    typedef __attribute__((address_space(1))) f32x4 gvec4;
+                    const f32x4 v = {f[c][0], f[c][1], f[c][2], f[c][3]};
+                    __builtin_nontemporal_store(v, (gvec4*)dc);
+                } else {
+                    typedef __attribute__((address_space(1))) float gfloat;
+                    gfloat* e = (gfloat*)dc;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (j0 + k < wo) e[k] = f[c][k];
+                }
+            }
+        }
+    }
+}
+
 template <int kFormat>
 __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeDev* __restrict__ items, int groups,
                                                                  int out_w, int out_h, int out_pitch, NormDev nk)
@@ -93,65 +163,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeDev*
             px[k] = p;
         }
         gbyte* d = (gbyte*)it.dst + static_cast<int64_t>(i) * out_pitch + static_cast<int64_t>(j0) * kElem;
-        if constexpr (kFormat == 0) {
-            if (vec) {
-                typedef __attribute__((address_space(1))) uint32_t gword;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int sh = 16 - 8 * c;
-                    const uint32_t v = ((px[0] >> sh) & 0xffu) | (((px[1] >> sh) & 0xffu) << 8) |
-                                       (((px[2] >> sh) & 0xffu) << 16) | (((px[3] >> sh) & 0xffu) << 24);
-                    __builtin_nontemporal_store(v, (gword*)(d + c * dplane));
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (j0 + k < wo) {
-                        d[k] = static_cast<uint8_t>(px[k] >> 16);
-                        d[dplane + k] = static_cast<uint8_t>(px[k] >> 8);
-                        d[2 * dplane + k] = static_cast<uint8_t>(px[k]);
-                    }
-            }
-        } else {
-            float f[3][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                f[0][k] = norm_px<0>(px[k], nk);
-                f[1][k] = norm_px<1>(px[k], nk);
-                f[2][k] = norm_px<2>(px[k], nk);
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                gbyte* dc = d + c * dplane;
-                if constexpr (kFormat == kResizeOutF16) {
-                    if (vec) {
-                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                        typedef __attribute__((address_space(1))) u32x2 gvec2;
-                        const u32x2 v = {pack_half2(f[c][0], f[c][1]), pack_half2(f[c][2], f[c][3])};
-                        __builtin_nontemporal_store(v, (gvec2*)dc);
-                    } else {
-                        typedef __attribute__((address_space(1))) uint16_t ghalf;
-                        ghalf* e = (ghalf*)dc;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (j0 + k < wo) e[k] = static_cast<uint16_t>(half_bits(f[c][k]));
-                    }
-                } else {
-                    if (vec) {
-                        typedef float f32x4 __attribute__((ext_vector_type(4)));
-                        typedef __attribute__((address_space(1))) f32x4 gvec4;
-                        const f32x4 v = {f[c][0], f[c][1], f[c][2], f[c][3]};
-                        __builtin_nontemporal_store(v, (gvec4*)dc);
-                    } else {
-                        typedef __attribute__((address_space(1))) float gfloat;
-                        gfloat* e = (gfloat*)dc;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (j0 + k < wo) e[k] = f[c][k];
-                    }
-                }
-            }
-        }
+        resize_store_quad<kFormat>(px, d, dplane, vec, j0, wo, nk);
     }
 }
 

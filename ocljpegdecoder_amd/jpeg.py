@@ -355,14 +355,17 @@ class GpuDecoder:
                                                _stream_handle(stream)), "hjd_gdec_decode_roi")
         self._n = n
 
-    def decode_resized(self, datas: Sequence[bytes], out, stream=None, rois=None, flips=None):
-        """hjd_gdec_decode_resized: decode, crop (rois, one (x, y, w, h) per
+    def decode_resized(self, datas: Sequence[bytes], out, stream=None, rois=None, flips=None, antialias=False):
+        """hjd_gdec_decode_resized_filter: decode, crop (rois, one (x, y, w, h) per
         image on the grid of the decoder's scale, of any sizes; None: whole
         frames), resize every crop to out's (Ho, Wo) and flip where flips[i]
         is set, into `out`, a contiguous device tensor (N, 3, Ho, Wo) whose
         dtype is the decoder's current planar format's.  The crops pass
         through a scratch the decoder owns: a call that needs a larger one
-        than any before waits for the previous call and reallocates."""
+        than any before waits for the previous call and reallocates.
+        antialias: the exact triangle filter (RESIZE_TRIANGLE_AA) instead of
+        plain bilinear; a crop dimension d going to o then needs
+        d * d <= 2**21 * o."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
@@ -380,9 +383,10 @@ class GpuDecoder:
                 raise ValueError("one flip flag per JPEG")
             fl = (ctypes.c_int32 * n)(*[1 if f else 0 for f in flips])
         ho, wo = int(out.shape[2]), int(out.shape[3])
-        check(self.lib.hjd_gdec_decode_resized(self.handle, arr_d, arr_s, n, rects, fl, out.data_ptr(), wo, ho,
-                                               wo * out.element_size(), _stream_handle(stream)),
-              "hjd_gdec_decode_resized")
+        check(self.lib.hjd_gdec_decode_resized_filter(self.handle, arr_d, arr_s, n, rects, fl, out.data_ptr(), wo, ho,
+                                                      wo * out.element_size(), 1 if antialias else 0,
+                                                      _stream_handle(stream)),
+              "hjd_gdec_decode_resized_filter")
         self._n = n
 
     def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1,
@@ -478,11 +482,13 @@ class GpuDecoder:
             norm_constants(mean, std)
 
     def decode_rgb_resized(self, datas: Sequence[bytes], size, flips=None, layout: str = "chw", out=None, stream=None,
-                           scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None):
+                           scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None, antialias=False):
         """decode_rgb with size = (h, w): every image -- its ROI, of any size,
         or its whole (scaled) frame -- is resized to h x w on the GPU
-        (decode_resized: bilinear, no antialiasing; resize_scale() gives the
-        `scale` that keeps the reduction within 2x) and mirrored horizontally
+        (decode_resized: bilinear, no antialiasing, where resize_scale() gives
+        the `scale` that keeps the reduction within 2x; with antialias=True
+        the exact triangle filter of interpolate(antialias=True), for any
+        reduction) and mirrored horizontally
         where flips[i] is set, and ONE (N, 3, h, w) tensor of the dtype comes
         back: `out` if given (a contiguous device tensor of exactly that shape
         and dtype), else a new one.  dtype, mean, std, scale and rois as
@@ -502,7 +508,8 @@ class GpuDecoder:
         elif not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == shape):
             raise ValueError(f"out must be a contiguous {dtype} device tensor {shape}")
         return self._with_settings(scale, fmt, norm,
-                                   lambda: self.decode_resized(datas, out, stream, rois=rois, flips=flips), out)
+                                   lambda: self.decode_resized(datas, out, stream, rois=rois, flips=flips,
+                                                               antialias=antialias), out)
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
