@@ -437,6 +437,83 @@ int hjd_resize_check_filter(const hjd_resize_item* items, int n, int out_w, int 
 int hjd_resize_create_filter(hjd_ctx* ctx, const hjd_resize_item* items, int n, int out_w, int out_h, int out_pitch,
                              int out_format, int filter, hjd_resize** out);
 
+/*
+ * Orientation (extension; the reference has none): n planar uint8 RGB images,
+ * each of its own size, permuted by their EXIF Orientation value in ONE
+ * launch.  What ImageOps.exif_transpose of an image library computes.
+ *
+ * Definition.  S is the stored image, h rows by w columns; D the displayed
+ * (oriented) image, for orientation o:
+ *
+ *     o   D[i][j] =            size of D (rows x columns)
+ *     1   S[i][j]              h x w
+ *     2   S[i][w-1-j]          h x w
+ *     3   S[h-1-i][w-1-j]      h x w
+ *     4   S[h-1-i][j]          h x w
+ *     5   S[j][i]              w x h
+ *     6   S[h-1-j][i]          w x h
+ *     7   S[h-1-j][w-1-i]      w x h
+ *     8   S[j][w-1-i]          w x h
+ *
+ * per plane: a pure permutation of bytes, exact.  Under a decode scale S is
+ * the scaled decode (ceil(W / s) x ceil(H / s)) and D its permutation.
+ *
+ * Source: as the resize's -- three uint8 planes R, G, B of src_w x src_h as
+ * HJD_OUT_RGB_PLANAR writes them, rows src_pitch bytes apart, planes
+ * src_pitch * src_h apart; any pointer and any src_pitch >= src_w; both
+ * dimensions in 1..16384.  Orientation 1 is legal: a copy.
+ *
+ * Output: out_format is HJD_OUT_RGB_PLANAR (the bytes), HJD_OUT_RGB_PLANAR_F16
+ * or _F32 (fma((float)u8, a[c], b[c]) as hjd_out_format defines it, both
+ * roundings of F16 included; hjd_orient_set_normalize, default a = 1, b = 0);
+ * anything else is HJD_E_INVALID.  Every item carries its own dst_pitch: plane
+ * R of D starts at dst, rows dst_pitch bytes apart, planes dst_pitch * (D's
+ * rows) apart; dst and dst_pitch are multiples of the element size and
+ * dst_pitch >= D's columns x the element size.  reserved must be 0.  Whole
+ * dwords move on the side (source, output) whose base and pitch are multiples
+ * of 4 bytes (the output's: of 4 elements), in every 128 x 128 tile none of
+ * whose dwords straddles the image's edge; every other tile takes guarded byte
+ * loads / element stores.  Nothing outside D's own elements is written.
+ * Sources may overlap each other; an output may overlap neither a source nor
+ * another output (hjd_orient_check refuses it).
+ *
+ * hjd_orient_roi: the rectangle on S that holds the pixels of `display`, a
+ * rectangle on D, for a stored frame of width x height (already scaled):
+ * orient(S restricted to *stored, o) == orient(S, o) restricted to *display.
+ * With (x, y, w, h) = *display, W = width, H = height:
+ *     1 (x, y, w, h)            2 (W-x-w, y, w, h)
+ *     3 (W-x-w, H-y-h, w, h)    4 (x, H-y-h, w, h)
+ *     5 (y, x, h, w)            6 (y, H-x-w, h, w)
+ *     7 (W-y-h, H-x-w, h, w)    8 (W-y-h, x, h, w)
+ * HJD_E_INVALID for a NULL, width or height < 1, an orientation outside 1..8
+ * and a rectangle that is empty or not inside D.  Host only.
+ */
+typedef struct hjd_orient_item {
+    const void* src;   /* device: plane R of the stored image */
+    void* dst;         /* device: plane R of the oriented image */
+    int32_t src_w, src_h, src_pitch, orientation;
+    int32_t dst_pitch; /* bytes between the oriented image's rows */
+    int32_t reserved;  /* 0 */
+} hjd_orient_item;
+typedef struct hjd_orient hjd_orient;
+int hjd_orient_roi(int width, int height, int orientation, const hjd_rect* display, hjd_rect* stored);
+/* Validates what hjd_orient_create would take.  HJD_E_INVALID (with a message)
+ * for n outside 1..2^20, a NULL items / src / dst, a dimension outside
+ * 1..16384, src_pitch < src_w, an orientation outside 1..8, a bad dst_pitch or
+ * dst alignment, a non-zero reserved, a non-planar or unknown format, more
+ * than 2^31 - 1 tiles of 128 x 128 in all, and an output that overlaps a source
+ * or another output.  Host only: needs no device. */
+int hjd_orient_check(const hjd_orient_item* items, int n, int out_format);
+/* Validates and uploads the item table (synchronously). */
+int hjd_orient_create(hjd_ctx* ctx, const hjd_orient_item* items, int n, int out_format, hjd_orient** out);
+/* The float formats' constants for the launches that follow (an enqueued
+ * launch keeps its own).  HJD_E_INVALID for non-finite constants and for a
+ * byte-format object. */
+int hjd_orient_set_normalize(hjd_orient* r, const float a[3], const float b[3]);
+/* Enqueue the orientation of all n items on `stream` (asynchronous, one kernel). */
+int hjd_orient_launch(hjd_orient* r, void* stream);
+int hjd_orient_destroy(hjd_orient* r);
+
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */
 int hjd_idct_blocks(hjd_ctx* ctx, const int32_t* d_in, int32_t* d_out, int64_t nblocks, void* stream);

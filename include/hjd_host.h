@@ -56,6 +56,20 @@ typedef struct hjd_jpeg_info {
  * unsupported files (hjd_last_error() says why). */
 int hjd_jpeg_parse(const uint8_t* data, size_t size, hjd_jpeg_info* info);
 
+/* The EXIF Orientation of a file (include/hjd.h hjd_orient_item defines what
+ * the values 1..8 mean): the marker segments before the first SOS are walked,
+ * the first APP1 whose payload starts with "Exif\0\0" is taken, its TIFF
+ * header read ("II" or "MM", magic 42, the offset of IFD0) and IFD0's 12-byte
+ * entries searched for tag 0x0112 of type SHORT and count 1, in the header's
+ * byte order.  A value in 1..8 is returned in *orientation.  Everything else
+ * gives 1 and HJD_OK, never an error -- no APP1, none with Exif, a bad byte
+ * order or magic, an offset, entry count or entry past the segment, another
+ * type or count, a value outside 1..8 -- so a broken EXIF block never makes an
+ * image undecodable; every read is checked against the segment.  Only a file
+ * that is not a JPEG up to there (SOI missing, a truncated segment or bad
+ * segment length, no SOS) returns the parser's HJD_E_INVALID. */
+int hjd_jpeg_orientation(const uint8_t* data, size_t size, int32_t* orientation);
+
 /* Parse + Huffman-decode one file into coefs (capacity in blocks). */
 int hjd_jpeg_decode_coefs(const uint8_t* data, size_t size, hjd_jpeg_info* info, int16_t* coefs,
                           int64_t capacity_blocks);
@@ -238,6 +252,37 @@ int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size
 int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
                                    const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
                                    int32_t out_pitch, int filter, void* stream);
+/* hjd_gdec_decode / hjd_gdec_decode_roi with an EXIF orientation per frame
+ * (include/hjd.h hjd_orient_item defines the values 1..8 and the oriented
+ * image D; hjd_jpeg_orientation reads a file's): d_outs[i] receives D of frame
+ * i in the decoder's format, which must be HJD_OUT_RGB_PLANAR, _F16 or _F32
+ * (any other is HJD_E_INVALID), rows pitches[i] apart (>= D's columns x the
+ * element size).  rois may be NULL; if given, rois[i] is a rectangle on D
+ * (display coordinates) and d_outs[i] receives that part of D: the stored
+ * rectangle that holds it (hjd_orient_roi) is what is decoded.  Under a scale
+ * D is the permutation of the scaled decode.
+ *
+ * A call whose orientations are all 1 is exactly hjd_gdec_decode /
+ * hjd_gdec_decode_roi: no scratch, no extra launch.  In any other call every
+ * frame, those of orientation 1 included, is decoded as planar bytes into the
+ * decoder's grow-only scratch (as hjd_gdec_decode_resized's crops, under the
+ * same growth rule) and one orient launch for all n frames follows on the same
+ * stream and writes the outputs.  Everything that can refuse the call -- an
+ * orientation outside 1..8, the format, a rectangle outside D, a scale the
+ * file's sampling does not serve, an output pointer or pitch -- is checked
+ * before anything is staged, allocated or enqueued. */
+int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                             const int32_t* orientations, void* const* d_outs, const int32_t* pitches, void* stream);
+/* hjd_gdec_decode_resized_filter of the oriented images: the result is
+ * resize(orient(decode)) for either filter; rois are rectangles on D, flags
+ * flip D, and the antialiased filter's ratio rule applies to D's crop.  Built
+ * as that composition: the stored crops are decoded into the scratch, one
+ * orient launch writes the oriented crops (planar bytes) into a second region
+ * of it, and the resize launches read those, unchanged.  All orientations 1:
+ * exactly hjd_gdec_decode_resized_filter. */
+int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                     const hjd_rect* rois, const int32_t* orientations, const int32_t* flags, void* d_out,
+                                     int out_w, int out_h, int32_t out_pitch, int filter, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

@@ -45,6 +45,9 @@ from .backend import (  # noqa: E402
     frame_check,
     mcu_geometry,
     norm_constants,
+    Orient,
+    oriented_roi,
+    oriented_size,
     Resize,
     RESIZE_FLIP_H,
     RESIZE_BILINEAR,
@@ -57,8 +60,8 @@ from .backend import (  # noqa: E402
 )
 
 from .jpeg import (GpuDecoder, GpuJpegStream, JpegInfo, JpegStream, bmp_bytes, bmp_header,  # noqa: E402
-                   decode_coefs, decode_coefs_batch, decode_coefs_into, decode_jpeg, emulate_entropy, parse,
-                   pinned_bytes)
+                   decode_coefs, decode_coefs_batch, decode_coefs_into, decode_jpeg, emulate_entropy,
+                   exif_orientation, parse, pinned_bytes)
 
 __all__ = [
     "GpuDecoder", "GpuJpegStream", "JpegInfo", "JpegStream", "bmp_bytes", "bmp_header", "decode_coefs",
@@ -67,5 +70,6 @@ __all__ = [
     "Context", "FrameSpec", "Plan", "autotune_cache_clear", "decode_frame", "device_count", "frame_blocks", "mcu_geometry", "worker_cpus", "cpu_share", "debug_tuning",
     "device_worker_cpus", "stream_worker_threads", "scaled_size", "roi_geometry", "norm_constants", "frame_check",
     "OUT_RGB_PLANAR_F16", "OUT_RGB_PLANAR_F32", "Resize", "RESIZE_FLIP_H", "RESIZE_BILINEAR", "RESIZE_TRIANGLE_AA", "resize_scale",
+    "Orient", "oriented_roi", "oriented_size", "exif_orientation",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -46,6 +46,16 @@ class HjdResizeItem(ctypes.Structure):
 assert ctypes.sizeof(HjdResizeItem) == 32
 
 
+class HjdOrientItem(ctypes.Structure):
+    """struct hjd_orient_item (include/hjd.h): one image of an orientation launch."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in
+                                                                       ("src_w", "src_h", "src_pitch", "orientation",
+                                                                        "dst_pitch", "reserved")]
+
+
+assert ctypes.sizeof(HjdOrientItem) == 40
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -140,6 +150,14 @@ SIGNATURES = {
     "hjd_resize_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hjd_debug_resize_launch_pass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "hjd_resize_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_orient_roi": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(HjdRect), ctypes.POINTER(HjdRect)]),
+    "hjd_orient_check": (ctypes.c_int, [ctypes.POINTER(HjdOrientItem), ctypes.c_int, ctypes.c_int]),
+    "hjd_orient_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdOrientItem), ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_orient_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                                ctypes.POINTER(ctypes.c_float)]),
+    "hjd_orient_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_orient_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
     "hjd_debug_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -238,6 +256,14 @@ def _bind_host(lib):
                                                           ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, vp,
                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int,
                                                           vp]),
+        "hjd_jpeg_orientation": (ctypes.c_int, [u8p, ctypes.c_size_t, c_i32p]),
+        "hjd_gdec_decode_oriented": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                    ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, ctypes.POINTER(vp),
+                                                    c_i32p, vp]),
+        "hjd_gdec_decode_resized_oriented": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                            ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, c_i32p, vp,
+                                                            ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int,
+                                                            vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

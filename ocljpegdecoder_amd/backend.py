@@ -501,6 +501,105 @@ class Resize:
             pass
 
 
+def oriented_size(width: int, height: int, orientation: int):
+    """(W, H) of the displayed image of a width x height stored one under EXIF
+    orientation 1..8 (include/hjd.h): swapped for 5..8.  Pure Python."""
+    o = int(orientation)
+    if not 1 <= o <= 8:
+        raise ValueError(f"orientation {orientation} is outside 1..8")
+    return (int(height), int(width)) if o >= 5 else (int(width), int(height))
+
+
+def oriented_roi(width: int, height: int, orientation: int, roi):
+    """hjd_orient_roi: the (x, y, w, h) rectangle on the stored width x height
+    frame (already scaled) that holds the pixels of `roi`, a rectangle on the
+    displayed image.  HjdError for a rectangle outside it."""
+    lib = _lib.load()
+    d, s = _lib.HjdRect(*[int(v) for v in roi]), _lib.HjdRect()
+    check(lib.hjd_orient_roi(int(width), int(height), int(orientation), ctypes.byref(d), ctypes.byref(s)),
+          "hjd_orient_roi")
+    return (s.x, s.y, s.w, s.h)
+
+
+class Orient:
+    """hjd_orient: N planar uint8 RGB images of different sizes, each permuted
+    by its EXIF orientation (1..8; include/hjd.h has the table) into its own
+    output, in one launch.  A pure permutation of bytes; the float dtypes are
+    fma(float(u8), a, b) of the permuted bytes."""
+
+    def __init__(self, ctx: Context, srcs, outs, orientations, normalize=None):
+        """srcs: N device tensors (3, h, w) uint8 (contiguous, or a [..., :w]
+        view of wider rows), or (tensor, pitch) pairs as Resize takes them.
+        outs: N device tensors of one dtype (uint8, float16 or float32), out i
+        shaped (3, H, W) with (W, H) = oriented_size(w, h, orientations[i]),
+        contiguous or a [..., :W] view of wider rows, or (tensor, pitch)
+        pairs: 3 * H rows of `pitch` bytes from the tensor's data_ptr.
+        normalize = (a, b): the float dtypes' constants."""
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.handle = None
+        n = len(srcs)
+        if len(outs) != n or len(orientations) != n:
+            raise ValueError("one output and one orientation per source")
+        items = (_lib.HjdOrientItem * max(1, n))()
+        self._keep = []
+        fmt = None
+        for i, (s, d) in enumerate(zip(srcs, outs)):
+            t, sp = self._planes(s, i, "source")
+            if t.element_size() != 1:
+                raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
+            u, dp = self._planes(d, i, "output")
+            if str(u.dtype) not in _DTYPE_FORMATS or (fmt is not None and _DTYPE_FORMATS[str(u.dtype)] != fmt):
+                raise ValueError("outputs must be uint8 / float16 / float32 device tensors of one dtype")
+            fmt = _DTYPE_FORMATS[str(u.dtype)]
+            w, h = int(t.shape[2]), int(t.shape[1])
+            if 1 <= int(orientations[i]) <= 8 and (int(u.shape[2]), int(u.shape[1])) != oriented_size(
+                    w, h, orientations[i]):
+                raise ValueError(f"output {i} is {u.shape[2]}x{u.shape[1]}, the oriented image "
+                                 f"{'x'.join(map(str, oriented_size(w, h, orientations[i])))}")
+            self._keep += [t, u]
+            items[i] = _lib.HjdOrientItem(t.data_ptr(), u.data_ptr(), w, h, int(sp), int(orientations[i]), int(dp), 0)
+        self.out_format = fmt if fmt is not None else OUT_RGB_PLANAR
+        h = ctypes.c_void_p()
+        check(self.lib.hjd_orient_create(ctx.handle, items, n, self.out_format, ctypes.byref(h)), "hjd_orient_create")
+        self.handle = h
+        if normalize is not None:
+            self.set_normalize(*normalize)
+
+    @staticmethod
+    def _planes(s, i, what):
+        """(tensor, pitch in bytes) of a (3, h, w) tensor or a (tensor, pitch) pair."""
+        t, p = s if isinstance(s, (tuple, list)) else (s, None)
+        if not (t.is_cuda and t.ndim == 3 and t.shape[0] == 3):
+            raise ValueError(f"{what} {i} must be a (3, h, w) device tensor")
+        if p is None:   # contiguous, or a [..., :w] view of wider rows
+            row = t.stride(1)
+            if t.stride(2) != 1 or row < t.shape[2] or t.stride(0) != t.shape[1] * row:
+                raise ValueError(f"{what} {i} must be contiguous, a [..., :w] view of wider rows, or come with its pitch")
+            p = row * t.element_size()
+        return t, p
+
+    def set_normalize(self, a, b):
+        """hjd_orient_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
+        ca, cb = _norm_arrays((a, b))
+        check(self.lib.hjd_orient_set_normalize(self.handle, ca, cb), "hjd_orient_set_normalize")
+
+    def launch(self, stream=None):
+        """Enqueue the orientation kernel (asynchronous)."""
+        check(self.lib.hjd_orient_launch(self.handle, _stream_ptr(stream)), "hjd_orient_launch")
+
+    def close(self):
+        if self.handle:
+            self.lib.hjd_orient_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def worker_cpus(bus: str, gpus: Sequence[str], sysfs_root: Optional[str] = None, only_allowed: bool = False):
     """hjd_debug_worker_cpus: the host CPUs the worker pool of the GPU at PCI
     address `bus` binds to, among the GPUs `gpus` (its NUMA node's CPUs split

@@ -313,10 +313,54 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, int out_format, bool fno
     return HJD_OK;
 }
 
-// Where a resized call's records lie behind the pixel kernel's tables (from H.recs).
-inline size_t resize_records_offset(int n, bool roi)
+// Where an oriented call's records lie behind the pixel kernel's tables (from H.recs).
+inline size_t orient_records_offset(int n, bool roi)
 {
     return hjd_internal::align_up(pixel_tables_bytes(n, roi, false), 16);
+}
+
+// Where a resized call's records lie (from H.recs): behind the pixel kernel's
+// tables and, in an oriented call, the orient records.
+inline size_t resize_records_offset(int n, bool roi, bool orient)
+{
+    return orient_records_offset(n, roi) +
+           (orient ? hjd_internal::align_up(sizeof(hjd_internal::OrientRecord) * static_cast<size_t>(n), 16) : 0);
+}
+
+// The stored crop of image i as the pixel kernels write it: its size.
+inline void crop_size(const hjd_gdec* g, const GdecCall& c, int i, int& w, int& h)
+{
+    const Prepared& p = g->st.frames[i];
+    w = c.rois ? c.rois[i].w : hjd_internal::scaled_dim(p.width, g->scale);
+    h = c.rois ? c.rois[i].h : hjd_internal::scaled_dim(p.height, g->scale);
+}
+
+// The orient kernel's records of an oriented call (OrientStage): image i from
+// its stored crop in the scratch (c.d_outs[i], c.pitches[i]) to o.outs[i].
+// Returns the launch's tiles in *tiles.
+int write_orient_records(hjd_gdec* g, const GdecCall& c, int64_t* tiles)
+{
+    Staging& st = g->st;
+    const int n = static_cast<int>(st.frames.size());
+    const OrientStage& o = *c.orient;
+    hjd_internal::OrientRecord* recs = reinterpret_cast<hjd_internal::OrientRecord*>(
+        st.h_stage + st.H.recs + orient_records_offset(n, c.rois != nullptr));
+    *tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        hjd_internal::OrientRecord rec;
+        rec.src = c.d_outs[i];
+        rec.dst = o.outs[i];
+        crop_size(g, c, i, rec.w, rec.h);
+        rec.pitch = c.pitches[i];
+        rec.orientation = o.orientations[i];
+        rec.dst_pitch = o.out_pitches[i];
+        rec.tile_begin = static_cast<uint32_t>(*tiles);
+        const int rc = hjd_internal::orient_item_check(rec, i, o.out_format);
+        if (rc) return rc;
+        *tiles += hjd_internal::orient_tiles(rec.w, rec.h);
+        recs[i] = rec;
+    }
+    return HJD_OK;
 }
 
 // Resize records of a resized call: n, or with the antialiased filter 2 n
@@ -335,16 +379,19 @@ int write_resize_records(hjd_gdec* g, const GdecCall& c)
     const int n = static_cast<int>(st.frames.size());
     const ResizeStage& r = *c.resize;
     hjd_internal::ResizeRecord* recs = reinterpret_cast<hjd_internal::ResizeRecord*>(
-        st.h_stage + st.H.recs + resize_records_offset(n, c.rois != nullptr));
+        st.h_stage + st.H.recs + resize_records_offset(n, c.rois != nullptr, c.orient != nullptr));
     const size_t image = 3 * static_cast<size_t>(r.out_pitch) * static_cast<size_t>(r.out_h);
     for (int i = 0; i < n; ++i) {
-        const Prepared& p = st.frames[i];
         hjd_internal::ResizeRecord rec;
         rec.src = c.d_outs[i];
         rec.dst = static_cast<uint8_t*>(r.out) + image * static_cast<size_t>(i);
-        rec.w = c.rois ? c.rois[i].w : hjd_internal::scaled_dim(p.width, g->scale);
-        rec.h = c.rois ? c.rois[i].h : hjd_internal::scaled_dim(p.height, g->scale);
+        crop_size(g, c, i, rec.w, rec.h);
         rec.pitch = c.pitches[i];
+        if (c.orient) {   // the resize reads the oriented crop
+            rec.src = c.orient->outs[i];
+            rec.pitch = c.orient->out_pitches[i];
+            if (hjd_internal::orientation_transposes(c.orient->orientations[i])) std::swap(rec.w, rec.h);
+        }
         rec.flags = r.flags ? r.flags[i] : 0;
         const int rc = hjd_internal::resize_item_check(rec, i, g->out_format);
         if (rc) return rc;
@@ -398,20 +445,27 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     g->batch_spec = spec;
     const uint32_t S = g->batch_sub_bits ? g->batch_sub_bits : static_cast<uint32_t>(st.caps.sub_bits);
     // a resized call's pixel kernels write planar bytes (the crops); its resize launch the decoder's format
-    const int pix_format = c.resize ? HJD_OUT_RGB_PLANAR : g->out_format;
+    // (an oriented call's too: its orient launch writes the decoder's format, or the resize's source)
+    const int pix_format = c.resize || c.orient ? HJD_OUT_RGB_PLANAR : g->out_format;
     const bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
     const size_t recs_bytes = !c.d_outs ? 0
-                              : c.resize ? resize_records_offset(n, c.rois != nullptr) +
+                              : c.resize ? resize_records_offset(n, c.rois != nullptr, c.orient != nullptr) +
                                                resize_records_bytes(n, *c.resize)
+                              : c.orient ? resize_records_offset(n, c.rois != nullptr, true)
                                          : pixel_tables_bytes(n, c.rois != nullptr, fnorm);
     EntBatchDev b;
     int rc = st.assemble(g->d_blob, coefs, c.block_offsets, S, recs_bytes,
                          c.d_outs ? 192 * 4 * static_cast<size_t>(n) : 0, b);
     if (rc) return rc;
     PixelClasses px;
+    int64_t orient_tiles = 0;
     if (c.d_outs) {
         rc = write_pixel_records(g, c, pix_format, fnorm, px);
         if (rc) return rc;
+        if (c.orient) {
+            rc = write_orient_records(g, c, &orient_tiles);
+            if (rc) return rc;
+        }
         if (c.resize) {
             rc = write_resize_records(g, c);
             if (rc) return rc;
@@ -588,15 +642,24 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
             rc = hjd_internal::launch_decode(l);
             if (rc) return rc;
         }
+        if (c.orient) {   // the stored crops -> the oriented images, behind the pixel kernels
+            const hjd_internal::OrientRecord* recs = reinterpret_cast<const hjd_internal::OrientRecord*>(
+                g->d_blob + g->st.H.recs + orient_records_offset(n, c.rois != nullptr));
+            rc = hjd_internal::launch_orient(g->device, recs, n, orient_tiles, c.orient->out_format, g->norm, s);
+            if (rc) return rc;
+        }
         if (c.resize) {   // the crops -> the batch, behind the pixel kernels; `done` (below) covers it
             const ResizeStage& r = *c.resize;
             const hjd_internal::ResizeRecord* recs = reinterpret_cast<const hjd_internal::ResizeRecord*>(
-                g->d_blob + g->st.H.recs + resize_records_offset(n, c.rois != nullptr));
+                g->d_blob + g->st.H.recs + resize_records_offset(n, c.rois != nullptr, c.orient != nullptr));
             if (r.mids) {
                 int max_h = 1;
-                for (int i = 0; i < n; ++i)
-                    max_h = std::max(max_h, c.rois ? c.rois[i].h
-                                                   : hjd_internal::scaled_dim(g->st.frames[i].height, g->scale));
+                for (int i = 0; i < n; ++i) {
+                    int cw, ch;
+                    crop_size(g, c, i, cw, ch);
+                    if (c.orient && hjd_internal::orientation_transposes(c.orient->orientations[i])) ch = cw;
+                    max_h = std::max(max_h, ch);
+                }
                 rc = hjd_internal::launch_resize_aa(g->device, recs, recs + n, n, max_h, r.out_w, r.out_h, r.out_pitch,
                                                     g->out_format, g->norm, s);
             } else {
@@ -795,9 +858,131 @@ int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size
                                           HJD_RESIZE_BILINEAR, stream);
 }
 
-int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
-                                   const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
-                                   int32_t out_pitch, int filter, void* stream)
+// Grow the decoder's scratch to `need` bytes (grow-only; the previous call may
+// still use the old buffer, so growing waits for it).
+static int grow_scratch(hjd_gdec* g, size_t need, const char* what)
+{
+    if (need <= g->crops_bytes) return HJD_OK;
+    HJD_HIP(hipSetDevice(g->device));
+    if (g->pending) HJD_HIP(hipEventSynchronize(g->done));
+    if (g->d_crops) (void)hipFree(g->d_crops);
+    g->d_crops = nullptr;
+    g->crops_bytes = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&g->d_crops), need) != hipSuccess) {
+        (void)hipGetLastError();
+        g->d_crops = nullptr;
+        return set_error(HJD_E_NOMEM, "the %s of this call need %zu bytes of device memory", what, need);
+    }
+    g->crops_bytes = need;
+    return HJD_OK;
+}
+
+// HJD_OK if every orientation lies in 1..8; *any says whether one is not 1.
+static int orientations_check(const int32_t* orientations, int n, bool* any)
+{
+    *any = false;
+    for (int i = 0; i < n; ++i) {
+        if (!hjd_internal::orientation_ok(orientations[i]))
+            return set_error(HJD_E_INVALID, "frame %d: orientation %d is outside 1..8", i, orientations[i]);
+        *any = *any || orientations[i] != 1;
+    }
+    return HJD_OK;
+}
+
+// The stored crop of frame i of an oriented call, everything about it checked:
+// the file's header, the display rectangle (rois, or null: the whole frame)
+// mapped to the stored one (*stored; roi_geom checks it against the sampling
+// and the scale), the crop's size.
+static int oriented_crop(const hjd_gdec* g, const uint8_t* data, size_t size, int i, int orientation,
+                         const hjd_rect* rois, hjd_rect* stored, int* cw, int* ch)
+{
+    if (!data) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
+    hjd_internal::ScanHeader h;
+    int rc = hjd_internal::parse_scan_header(data, size, &h);
+    if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+    const int sw = hjd_internal::scaled_dim(h.width, g->scale), sh = hjd_internal::scaled_dim(h.height, g->scale);
+    if (rois) {
+        rc = hjd_internal::orient_roi(sw, sh, orientation, rois[i], stored);
+        if (!rc) {
+            hjd_internal::RoiGeom rg;
+            rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, stored, &rg);
+        }
+        *cw = stored->w;
+        *ch = stored->h;
+    } else {
+        hjd_internal::DecodeShape shape;
+        shape.scale = g->scale;
+        shape.sampling = h.sampling;
+        rc = g->scale != 1 ? hjd_internal::shape_check(shape) : HJD_OK;
+        *cw = sw;
+        *ch = sh;
+    }
+    if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+    if (*cw > hjd_internal::kResizeMaxDim || *ch > hjd_internal::kResizeMaxDim)
+        return set_error(HJD_E_INVALID, "frame %d: the crop is %d x %d, the orientation and the resize take up to %d", i,
+                         *cw, *ch, hjd_internal::kResizeMaxDim);
+    return HJD_OK;
+}
+
+int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                             const int32_t* orientations, void* const* d_outs, const int32_t* pitches, void* stream)
+{
+    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
+    if (!d_outs) return set_error(HJD_E_INVALID, "d_outs is NULL");
+    if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
+    if (!pitches) return set_error(HJD_E_INVALID, "pitches is NULL");
+    // everything that can refuse the call is checked before anything is staged, allocated or enqueued
+    int rc = hjd_internal::orient_out_check(n, g->out_format);
+    if (rc) return rc;
+    bool any = false;
+    rc = orientations_check(orientations, n, &any);
+    if (rc) return rc;
+    if (!any)   // nothing to orient: today's call, no scratch and no extra launch
+        return rois ? hjd_gdec_decode_roi(g, datas, sizes, n, rois, d_outs, pitches, stream)
+                    : hjd_gdec_decode(g, datas, sizes, n, d_outs, pitches, stream);
+    if (n > g->st.caps.max_frames)
+        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
+    // the stored crops in the scratch: each 16-byte aligned, its pitch rounded up to 4
+    std::vector<size_t> offs(static_cast<size_t>(n));
+    std::vector<int32_t> crop_pitches(static_cast<size_t>(n));
+    std::vector<hjd_rect> stored(rois ? static_cast<size_t>(n) : 0);
+    size_t need = 0;
+    int64_t tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        int cw, ch;
+        rc = oriented_crop(g, datas[i], sizes[i], i, orientations[i], rois, rois ? &stored[i] : nullptr, &cw, &ch);
+        if (rc) return rc;
+        // the record's checks on the caller's side of it (its source, a place in the scratch, comes below)
+        hjd_internal::OrientRecord rec{g, d_outs[i], cw, ch, (cw + 3) & ~3, orientations[i], pitches[i], 0};
+        rc = hjd_internal::orient_item_check(rec, i, g->out_format);
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        tiles += hjd_internal::orient_tiles(cw, ch);
+        crop_pitches[i] = rec.pitch;
+        offs[i] = need;
+        need = hjd_internal::align_up(need + 3 * static_cast<size_t>(rec.pitch) * static_cast<size_t>(ch), 16);
+    }
+    if (tiles > hjd_internal::kOrientMaxTiles)
+        return set_error(HJD_E_INVALID, "the crops have %lld tiles of 128 x 128 in all (at most %lld per call)",
+                         static_cast<long long>(tiles), static_cast<long long>(hjd_internal::kOrientMaxTiles));
+    rc = grow_scratch(g, need, "stored crops");
+    if (rc) return rc;
+    std::vector<void*> crops(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
+    OrientStage ostage{orientations, d_outs, pitches, g->out_format};
+    GdecCall c = make_call(datas, sizes, n, stream);
+    c.d_outs = crops.data();
+    c.pitches = crop_pitches.data();
+    c.rois = rois ? stored.data() : nullptr;
+    c.orient = &ostage;
+    return gdec_run(g, c);
+}
+
+// hjd_gdec_decode_resized_filter (orientations null) and
+// hjd_gdec_decode_resized_oriented: decode to the scratch, with orientations
+// orient to a second scratch region, then the resize launches.
+static int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                          const int32_t* orientations, const int32_t* flags, void* d_out, int out_w, int out_h,
+                          int32_t out_pitch, int filter, void* stream)
 {
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
@@ -812,75 +997,109 @@ int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, con
                          hjd_internal::out_format_row_bytes(g->out_format));
     if (n > g->st.caps.max_frames)
         return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
+    if (orientations) {
+        bool any = false;
+        rc = orientations_check(orientations, n, &any);
+        if (rc) return rc;
+        if (!any) orientations = nullptr;   // nothing to orient: the plain resized call
+    }
     // the crops in the scratch: each 16-byte aligned, its pitch rounded up to 4
     // (whole strips of the pixel kernel keep their vector stores)
-    // (the antialiased filter's intermediates follow the crops, each 16-byte aligned too)
-    std::vector<size_t> offs(static_cast<size_t>(n)), mid_offs(aa ? static_cast<size_t>(n) : 0);
-    std::vector<int32_t> pitches(static_cast<size_t>(n));
-    size_t need = 0, mid_need = 0;
+    // (an oriented call's oriented crops follow them under the same rule, and
+    // the antialiased filter's intermediates follow those, each 16-byte aligned too)
+    const size_t un = static_cast<size_t>(n);
+    std::vector<size_t> offs(un), mid_offs(aa ? un : 0), or_offs(orientations ? un : 0);
+    std::vector<int32_t> pitches(un), or_pitches(or_offs.size());
+    std::vector<hjd_rect> stored(orientations && rois ? un : 0);
+    size_t need = 0, mid_need = 0, or_need = 0;
+    int64_t tiles = 0;
     hjd_internal::ScanHeader h;
     hjd_internal::DecodeShape shape;
     shape.scale = g->scale;
     for (int i = 0; i < n; ++i) {
-        if (!datas[i]) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
-        rc = hjd_internal::parse_scan_header(datas[i], sizes[i], &h);
-        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-        int cw, ch;
-        if (rois) {   // the rectangle, and the scale against the file's sampling
-            hjd_internal::RoiGeom rg;
-            rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rois[i], &rg);
-            cw = rois[i].w;
-            ch = rois[i].h;
+        int cw, ch;   // the stored crop
+        if (orientations) {
+            rc = oriented_crop(g, datas[i], sizes[i], i, orientations[i], rois, rois ? &stored[i] : nullptr, &cw, &ch);
+            if (rc) return rc;
         } else {
-            shape.sampling = h.sampling;
-            rc = g->scale != 1 ? hjd_internal::shape_check(shape) : HJD_OK;
-            cw = hjd_internal::scaled_dim(h.width, g->scale);
-            ch = hjd_internal::scaled_dim(h.height, g->scale);
+            if (!datas[i]) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
+            rc = hjd_internal::parse_scan_header(datas[i], sizes[i], &h);
+            if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+            if (rois) {   // the rectangle, and the scale against the file's sampling
+                hjd_internal::RoiGeom rg;
+                rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rois[i], &rg);
+                cw = rois[i].w;
+                ch = rois[i].h;
+            } else {
+                shape.sampling = h.sampling;
+                rc = g->scale != 1 ? hjd_internal::shape_check(shape) : HJD_OK;
+                cw = hjd_internal::scaled_dim(h.width, g->scale);
+                ch = hjd_internal::scaled_dim(h.height, g->scale);
+            }
+            if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+            if (cw > hjd_internal::kResizeMaxDim || ch > hjd_internal::kResizeMaxDim)
+                return set_error(HJD_E_INVALID, "frame %d: the crop is %d x %d, the resize takes up to %d", i, cw, ch,
+                                 hjd_internal::kResizeMaxDim);
         }
-        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-        if (cw > hjd_internal::kResizeMaxDim || ch > hjd_internal::kResizeMaxDim)
-            return set_error(HJD_E_INVALID, "frame %d: the crop is %d x %d, the resize takes up to %d", i, cw, ch,
-                             hjd_internal::kResizeMaxDim);
         if (flags && (flags[i] & ~1))
             return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: horizontal flip)", i,
                              static_cast<unsigned>(flags[i] & ~1));
+        // what the resize reads: the crop, or its oriented image
+        const bool tr = orientations && hjd_internal::orientation_transposes(orientations[i]);
+        const int rw = tr ? ch : cw, rh = tr ? cw : ch;
         if (aa) {
-            rc = hjd_internal::resize_aa_ratio_check(cw, ch, out_w, out_h, i);
+            rc = hjd_internal::resize_aa_ratio_check(rw, rh, out_w, out_h, i);
             if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
             mid_offs[i] = mid_need;
-            mid_need += hjd_internal::resize_aa_item_bytes(out_w, ch);
+            mid_need += hjd_internal::resize_aa_item_bytes(out_w, rh);
         }
         pitches[i] = (cw + 3) & ~3;
         offs[i] = need;
         need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(ch), 16);
+        if (orientations) {
+            or_pitches[i] = (rw + 3) & ~3;
+            or_offs[i] = or_need;
+            or_need = hjd_internal::align_up(or_need + 3 * static_cast<size_t>(or_pitches[i]) * static_cast<size_t>(rh), 16);
+            tiles += hjd_internal::orient_tiles(cw, ch);
+        }
     }
+    if (tiles > hjd_internal::kOrientMaxTiles)
+        return set_error(HJD_E_INVALID, "the crops have %lld tiles of 128 x 128 in all (at most %lld per call)",
+                         static_cast<long long>(tiles), static_cast<long long>(hjd_internal::kOrientMaxTiles));
+    const size_t or_base = need;
+    need += or_need;
     const size_t mid_base = need;
     need += mid_need;
-    if (need > g->crops_bytes) {   // grow-only; the previous call may still use the old buffer
-        HJD_HIP(hipSetDevice(g->device));
-        if (g->pending) HJD_HIP(hipEventSynchronize(g->done));
-        if (g->d_crops) (void)hipFree(g->d_crops);
-        g->d_crops = nullptr;
-        g->crops_bytes = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g->d_crops), need) != hipSuccess) {
-            (void)hipGetLastError();
-            g->d_crops = nullptr;
-            return set_error(HJD_E_NOMEM, "the crops%s of this call need %zu bytes of device memory",
-                             aa ? " and the resize's intermediate" : "", need);
-        }
-        g->crops_bytes = need;
-    }
-    std::vector<void*> crops(static_cast<size_t>(n));
-    std::vector<void*> mids(mid_offs.size());
+    rc = grow_scratch(g, need, aa ? "crops and the resize's intermediate" : "crops");
+    if (rc) return rc;
+    std::vector<void*> crops(un), mids(mid_offs.size()), oriented(or_offs.size());
     for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
     for (size_t i = 0; i < mids.size(); ++i) mids[i] = g->d_crops + mid_base + mid_offs[i];
+    for (size_t i = 0; i < oriented.size(); ++i) oriented[i] = g->d_crops + or_base + or_offs[i];
     ResizeStage stage{d_out, out_w, out_h, out_pitch, flags, aa ? mids.data() : nullptr};
+    OrientStage ostage{orientations, oriented.data(), or_pitches.data(), HJD_OUT_RGB_PLANAR};
     GdecCall c = make_call(datas, sizes, n, stream);
     c.d_outs = crops.data();
     c.pitches = pitches.data();
-    c.rois = rois;
+    c.rois = orientations && rois ? stored.data() : rois;
     c.resize = &stage;
+    c.orient = orientations ? &ostage : nullptr;
     return gdec_run(g, c);
+}
+
+int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                   const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
+                                   int32_t out_pitch, int filter, void* stream)
+{
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, d_out, out_w, out_h, out_pitch, filter, stream);
+}
+
+int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                     const hjd_rect* rois, const int32_t* orientations, const int32_t* flags, void* d_out,
+                                     int out_w, int out_h, int32_t out_pitch, int filter, void* stream)
+{
+    if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, d_out, out_w, out_h, out_pitch, filter, stream);
 }
 
 int hjd_gdec_decode_coefs(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, int16_t* d_coefs,

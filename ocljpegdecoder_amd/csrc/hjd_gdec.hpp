@@ -26,8 +26,9 @@ struct hjd_gdec {
     int16_t* d_coefs = nullptr;
     uint8_t* d_raw = nullptr;           // raw scan bytes of device-destuffed frames (same offsets as the data area)
     uint32_t* d_tiles = nullptr;        // destuff scratch [3][max_tiles]
-    uint8_t* d_crops = nullptr;         // hjd_gdec_decode_resized: the decoded crops the resize kernel reads (and,
-                                        // behind them, the antialiased filter's intermediate);
+    uint8_t* d_crops = nullptr;         // hjd_gdec_decode_resized / _oriented: the decoded crops the resize or orient
+                                        // kernel reads (and, behind them, a resized oriented call's oriented crops
+                                        // and the antialiased filter's intermediate);
     size_t crops_bytes = 0;             // grow-only, (re)allocated by a call that needs more, behind the previous call
     bool spec = false;                  // speculative sync (latency decoders: ent_spec/cand/sync_spec kernels)
     hjd::ent::SpecRec* d_spec = nullptr;   // [max_subs][kMaxBpm]
@@ -89,6 +90,19 @@ struct ResizeStage {
     void* const* mids;
 };
 
+// The orientation stage of hjd_gdec_decode_oriented / _resized_oriented: the
+// call's d_outs are the stored crops in the decoder's scratch
+// (HJD_OUT_RGB_PLANAR), its rois already the stored rectangles
+// (hjd_orient_roi), and one orient launch behind the pixel kernels takes crop
+// i to outs[i] in out_format: the caller's buffer in the decoder's format, or
+// (a resized call) planar bytes in a second scratch region the resize reads.
+struct OrientStage {
+    const int32_t* orientations;   // per image, 1..8
+    void* const* outs;
+    const int32_t* out_pitches;
+    int out_format;
+};
+
 // One call of the decoder: everything that belongs to the call and not to
 // the object.  gdec_run reads all of it; gdec_issue (frames already staged in
 // g->st) all but datas, sizes and n.
@@ -104,6 +118,7 @@ struct GdecCall {
     hipStream_t stream = nullptr;
     const HostCopy* host = nullptr;     // per frame, or null
     const ResizeStage* resize = nullptr;   // hjd_gdec_decode_resized, or null
+    const OrientStage* orient = nullptr;   // hjd_gdec_decode_oriented / _resized_oriented, or null
     // early pull of a latency decoder's lone image (gdec_early_pull)
     hjd_gdec* early_g = nullptr;        // non-null while the call's host destuff may pull
     size_t prepulled = 0;               // data-area bytes of frame 0 already pulled

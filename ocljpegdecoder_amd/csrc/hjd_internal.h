@@ -256,6 +256,32 @@ int resize_aa_ratio_check(int src_w, int src_h, int out_w, int out_h, int index)
 int launch_resize_aa(int device, const ResizeRecord* d_h, const ResizeRecord* d_v, int n, int max_src_h, int out_w,
                      int out_h, int out_pitch, int out_format, const NormRecord& norm, void* stream, int passes = 3);
 
+// The orientation kernel (hjd_orient.hip; include/hjd.h hjd_orient_*).  One
+// image's record as the kernel reads it (layout of hjd::OrientDev and of
+// hjd_orient_item, whose reserved word is tile_begin here).
+struct OrientRecord {
+    const void* src;
+    void* dst;
+    int32_t w, h, pitch, orientation, dst_pitch;
+    uint32_t tile_begin;
+};
+constexpr int64_t kOrientMaxTiles = INT32_MAX;   // tiles per launch (the grid)
+inline bool orientation_ok(int o) { return o >= 1 && o <= 8; }
+inline bool orientation_transposes(int o) { return o >= 5; }
+// Tiles (workgroups) of one w x h image: 128 x 128 bytes of one plane each.
+inline int64_t orient_tiles(int w, int h) { return 3 * static_cast<int64_t>((w + 127) / 128) * ((h + 127) / 128); }
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: n and the
+// format, and one item's side of hjd_orient_check (tile_begin is not looked at).
+int orient_out_check(int n, int out_format);
+int orient_item_check(const OrientRecord& it, int index, int out_format);
+// The stored rectangle of a display rectangle (hjd_orient_roi without the NULL checks).
+int orient_roi(int width, int height, int orientation, const ::hjd_rect& display, ::hjd_rect* stored);
+// One orient_kernel launch over n records in device memory, `tiles` their
+// tile total (no host synchronisation); the records have passed the checks
+// and carry their tile_begin prefix.
+int launch_orient(int device, const OrientRecord* d_items, int n, int64_t tiles, int out_format, const NormRecord& norm,
+                  void* stream);
+
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe
 // the whole image; the rest the scan.

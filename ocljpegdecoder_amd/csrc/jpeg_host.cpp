@@ -1629,6 +1629,63 @@ int hjd_jpeg_parse(const uint8_t* data, size_t size, hjd_jpeg_info* info)
     return HJD_OK;
 }
 
+// The Orientation value (1..8) of the TIFF block t[0..tl) of an Exif APP1, or 1
+// for anything else.  Every read is checked against tl.
+static int32_t exif_orientation(const uint8_t* t, size_t tl)
+{
+    if (tl < 8) return 1;
+    bool le;
+    if (t[0] == 'I' && t[1] == 'I') le = true;
+    else if (t[0] == 'M' && t[1] == 'M') le = false;
+    else return 1;
+    auto u16 = [&](size_t p) -> uint32_t {
+        return le ? static_cast<uint32_t>(t[p] | (t[p + 1] << 8)) : static_cast<uint32_t>((t[p] << 8) | t[p + 1]);
+    };
+    auto u32 = [&](size_t p) -> uint32_t { return le ? (u16(p) | (u16(p + 2) << 16)) : ((u16(p) << 16) | u16(p + 2)); };
+    if (u16(2) != 42) return 1;
+    const size_t ifd = u32(4);
+    if (ifd > tl - 2) return 1;                      // the entry count lies past the segment
+    const size_t count = u16(ifd);
+    if (12 * count > tl - 2 - ifd) return 1;         // so does one of the entries
+    for (size_t k = 0; k < count; ++k) {
+        const size_t e = ifd + 2 + 12 * k;
+        if (u16(e) != 0x0112) continue;
+        if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;   // SHORT, count 1
+        const uint32_t v = u16(e + 8);
+        return v >= 1 && v <= 8 ? static_cast<int32_t>(v) : 1;
+    }
+    return 1;
+}
+
+int hjd_jpeg_orientation(const uint8_t* data, size_t size, int32_t* orientation)
+{
+    if (!data || !orientation) return set_error(HJD_E_INVALID, "NULL argument");
+    *orientation = 1;
+    const uint8_t* d = data;
+    const size_t n = size;
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return set_error(HJD_E_INVALID, "SOI missing");
+    size_t p = 2;
+    for (;;) {   // the marker segments before the first SOS, walked as parse_segments walks them
+        while (p < n && d[p] != 0xFF) ++p;
+        while (p < n && d[p] == 0xFF) ++p;
+        if (p >= n) return set_error(HJD_E_INVALID, "no SOS marker");
+        const uint8_t m = d[p++];
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (m == 0xD9) return HJD_OK;
+        if (p + 2 > n) return set_error(HJD_E_INVALID, "truncated marker segment");
+        const size_t len = static_cast<size_t>(be16(d + p));
+        if (len < 2 || p + len > n) return set_error(HJD_E_INVALID, "bad segment length");
+        if (m == 0xDA) return HJD_OK;
+        const uint8_t* s = d + p + 2;
+        const size_t sl = len - 2;
+        if (m == 0xE1 && sl >= 6 && memcmp(s, "Exif\0\0", 6) == 0) {   // the first Exif APP1 decides
+            *orientation = exif_orientation(s + 6, sl - 6);
+            return HJD_OK;
+        }
+        p += len;
+    }
+}
+
 int hjd_debug_host_reader(int mode)
 {
     if (mode < 0) return g_host_reader.load();

@@ -80,6 +80,17 @@ def parse(data: bytes) -> JpegInfo:
     return JpegInfo.from_c(info)
 
 
+def exif_orientation(data) -> int:
+    """hjd_jpeg_orientation: the file's EXIF Orientation, 1..8 (include/hjd.h
+    says what each does); 1 where the file has none or its EXIF block is
+    broken.  HjdError only for bytes that are no JPEG."""
+    lib = _lib.load()
+    addr, size, _keep = _ptr_size(data)
+    o = ctypes.c_int32(1)
+    check(lib.hjd_jpeg_orientation(ctypes.cast(addr, _u8p), size, ctypes.byref(o)), "hjd_jpeg_orientation")
+    return int(o.value)
+
+
 def decode_coefs(data: bytes):
     """Host Huffman decode -> (int16 [nblocks][64] zigzag coefficients, JpegInfo)."""
     lib = _lib.load()
@@ -328,13 +339,32 @@ class GpuDecoder:
         check(self.lib.hjd_gdec_set_scale(self.handle, int(scale)), "hjd_gdec_set_scale")
         self.scale = int(scale)
 
-    def decode(self, datas: Sequence[bytes], outs, stream=None, rois=None):
+    @staticmethod
+    def _orientations(datas, apply_exif_orientation, orientations):
+        """The per-image orientations of a call, or None where it asks for
+        none: the explicit list if given, else (apply_exif_orientation) the
+        files' own tags."""
+        if orientations is not None:
+            if len(orientations) != len(datas):
+                raise ValueError("one orientation per JPEG")
+            return [int(o) for o in orientations]
+        if apply_exif_orientation:
+            return [exif_orientation(d) for d in datas]
+        return None
+
+    def decode(self, datas: Sequence[bytes], outs, stream=None, rois=None, apply_exif_orientation: bool = False,
+               orientations: Optional[Sequence[int]] = None):
         """outs: contiguous device tensors, one row per image row: (H, W) int32
         (or (H, pitch/4)) for BGRX, (H, pitch) uint8 for BGR24, (H, W, 3)
         uint8 for RGB24, (3, H, W) uint8 for planar RGB, (3, H, W) float16 /
         float32 for the float planes.  rois: one (x, y, w, h)
         per image on the grid of the decoder's scale (hjd_gdec_decode_roi);
-        outs are then sized (h, w)."""
+        outs are then sized (h, w).  apply_exif_orientation: every image
+        comes out as displayed, permuted by its file's EXIF orientation
+        (exif_orientation()); orientations: one value 1..8 per image instead,
+        which wins over the files' tags (hjd_gdec_decode_oriented: the planar
+        formats only; outs are sized for the oriented image, oriented_size(),
+        and rois are rectangles on it).  With neither, nothing changes."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         if len(outs) != n:
@@ -344,7 +374,16 @@ class GpuDecoder:
                 raise ValueError("outputs must be contiguous device tensors")
         ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
         pitches = (ctypes.c_int32 * n)(*[_out_pitch(o, self.out_format) for o in outs])
-        if rois is None:
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        if orients is not None:
+            rects = None
+            if rois is not None:
+                if len(rois) != n:
+                    raise ValueError("one ROI per JPEG")
+                rects = (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
+            check(self.lib.hjd_gdec_decode_oriented(self.handle, arr_d, arr_s, n, rects, (ctypes.c_int32 * n)(*orients),
+                                                    ptrs, pitches, _stream_handle(stream)), "hjd_gdec_decode_oriented")
+        elif rois is None:
             check(self.lib.hjd_gdec_decode(self.handle, arr_d, arr_s, n, ptrs, pitches, _stream_handle(stream)),
                   "hjd_gdec_decode")
         else:
@@ -355,7 +394,9 @@ class GpuDecoder:
                                                _stream_handle(stream)), "hjd_gdec_decode_roi")
         self._n = n
 
-    def decode_resized(self, datas: Sequence[bytes], out, stream=None, rois=None, flips=None, antialias=False):
+    def decode_resized(self, datas: Sequence[bytes], out, stream=None, rois=None, flips=None,
+                       apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                       antialias=False):
         """hjd_gdec_decode_resized_filter: decode, crop (rois, one (x, y, w, h) per
         image on the grid of the decoder's scale, of any sizes; None: whole
         frames), resize every crop to out's (Ho, Wo) and flip where flips[i]
@@ -365,7 +406,9 @@ class GpuDecoder:
         than any before waits for the previous call and reallocates.
         antialias: the exact triangle filter (RESIZE_TRIANGLE_AA) instead of
         plain bilinear; a crop dimension d going to o then needs
-        d * d <= 2**21 * o."""
+        d * d <= 2**21 * o.  apply_exif_orientation / orientations as
+        decode(): the result is the resize of the oriented image
+        (hjd_gdec_decode_resized_oriented), rois and flips applying to it."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
@@ -383,10 +426,18 @@ class GpuDecoder:
                 raise ValueError("one flip flag per JPEG")
             fl = (ctypes.c_int32 * n)(*[1 if f else 0 for f in flips])
         ho, wo = int(out.shape[2]), int(out.shape[3])
-        check(self.lib.hjd_gdec_decode_resized_filter(self.handle, arr_d, arr_s, n, rects, fl, out.data_ptr(), wo, ho,
-                                                      wo * out.element_size(), 1 if antialias else 0,
-                                                      _stream_handle(stream)),
-              "hjd_gdec_decode_resized_filter")
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        if orients is not None:
+            check(self.lib.hjd_gdec_decode_resized_oriented(self.handle, arr_d, arr_s, n, rects,
+                                                            (ctypes.c_int32 * n)(*orients), fl, out.data_ptr(), wo, ho,
+                                                            wo * out.element_size(), 1 if antialias else 0,
+                                                            _stream_handle(stream)),
+                  "hjd_gdec_decode_resized_oriented")
+        else:
+            check(self.lib.hjd_gdec_decode_resized_filter(self.handle, arr_d, arr_s, n, rects, fl, out.data_ptr(), wo,
+                                                          ho, wo * out.element_size(), 1 if antialias else 0,
+                                                          _stream_handle(stream)),
+                  "hjd_gdec_decode_resized_filter")
         self._n = n
 
     def decode_rgb(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1,
@@ -410,9 +461,33 @@ class GpuDecoder:
         may differ.  Asynchronous like
         decode(): call sync() before reading.  The decoder's output format
         and constants are restored afterwards.  decode_rgb_resized() resizes
-        images of different sizes into one batch."""
+        images of different sizes into one batch, decode_rgb_oriented()
+        applies the files' EXIF orientation."""
+        return self._decode_rgb(datas, layout, out, stream, scale, rois, dtype, mean, std, None)
+
+    def decode_rgb_oriented(self, datas: Sequence[bytes], layout: str = "chw", out=None, stream=None, scale: int = 1,
+                            rois=None, dtype=_UINT8, mean=None, std=None, apply_exif_orientation: bool = True,
+                            orientations: Optional[Sequence[int]] = None):
+        """decode_rgb with every image as displayed: permuted on the GPU
+        (hjd_gdec_decode_oriented) by its file's EXIF orientation
+        (apply_exif_orientation, the default here), or by orientations, one
+        value 1..8 per image, which wins over the files' tags (rot90-style
+        augmentation).  H, W, the rois and the equal-size rule of `out` refer
+        to the oriented image (oriented_size()).  layout "chw" only ("hwc"
+        with either is a ValueError: oriented output is planar).  With
+        apply_exif_orientation=False and no orientations it is decode_rgb.
+        (decode_rgb itself keeps its parameter list; decode(),
+        decode_resized() and decode_rgb_resized() take the two arguments
+        directly.)"""
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        if orients is not None and layout == "hwc":
+            raise ValueError('oriented output is planar: layout must be "chw"')
+        return self._decode_rgb(datas, layout, out, stream, scale, rois, dtype, mean, std, orients)
+
+    def _decode_rgb(self, datas, layout, out, stream, scale, rois, dtype, mean, std, orients):
+        """decode_rgb / decode_rgb_oriented (orients: None, or one orientation per image)."""
         import torch
-        from .backend import scaled_size
+        from .backend import oriented_size, scaled_size
         chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
         infos = []
         for d in datas:   # headers only; any input decode() takes (bytes, arrays, pinned tensors)
@@ -421,6 +496,11 @@ class GpuDecoder:
             check(self.lib.hjd_jpeg_parse(ctypes.cast(addr, _u8p), size, ctypes.byref(c)), "hjd_jpeg_parse")
             infos.append(JpegInfo.from_c(c))
         sizes = [scaled_size(i.width, i.height, scale) for i in infos]   # (W', H')
+        if orients is not None:   # as displayed
+            for k, o in enumerate(orients):
+                if not 1 <= o <= 8:
+                    raise ValueError(f"image {k}: orientation {o} is outside 1..8")
+            sizes = [oriented_size(w, h, o) for (w, h), o in zip(sizes, orients)]
         if rois is not None:
             if len(rois) != len(infos):
                 raise ValueError("one ROI per JPEG")
@@ -440,7 +520,8 @@ class GpuDecoder:
                     raise ValueError(f"image {k} is {w}x{h}" + (f" at scale {scale}" if scale != 1 else "") +
                                      f", out is {ow}x{oh}")
             outs = [out[k] for k in range(len(infos))]
-        return self._with_settings(scale, fmt, norm, lambda: self.decode(datas, outs, stream, rois=rois),
+        return self._with_settings(scale, fmt, norm,
+                                   lambda: self.decode(datas, outs, stream, rois=rois, orientations=orients),
                                    outs if out is None else out)
 
     def _with_settings(self, scale, fmt, norm, call, result):
@@ -482,7 +563,9 @@ class GpuDecoder:
             norm_constants(mean, std)
 
     def decode_rgb_resized(self, datas: Sequence[bytes], size, flips=None, layout: str = "chw", out=None, stream=None,
-                           scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None, antialias=False):
+                           scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None,
+                           apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                           antialias=False):
         """decode_rgb with size = (h, w): every image -- its ROI, of any size,
         or its whole (scaled) frame -- is resized to h x w on the GPU
         (decode_resized: bilinear, no antialiasing, where resize_scale() gives
@@ -493,12 +576,15 @@ class GpuDecoder:
         back: `out` if given (a contiguous device tensor of exactly that shape
         and dtype), else a new one.  dtype, mean, std, scale and rois as
         decode_rgb; layout "chw" only ("hwc" is a ValueError: the batch is
-        planar).  Asynchronous; the decoder's format, scale and constants are
+        planar).  apply_exif_orientation / orientations as decode_rgb: the
+        oriented image is what is cropped (rois), resized and flipped.
+        Asynchronous; the decoder's format, scale and constants are
         restored afterwards."""
         import torch
         chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
         if not chw:
             raise ValueError('a resized batch is planar: layout must be "chw"')
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
         size = (int(size[0]), int(size[1]))
         if min(size) < 1:
             raise ValueError(f"size must be (h, w) with h, w >= 1, got {size}")
@@ -509,7 +595,7 @@ class GpuDecoder:
             raise ValueError(f"out must be a contiguous {dtype} device tensor {shape}")
         return self._with_settings(scale, fmt, norm,
                                    lambda: self.decode_resized(datas, out, stream, rois=rois, flips=flips,
-                                                               antialias=antialias), out)
+                                                               antialias=antialias, orientations=orients), out)
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
