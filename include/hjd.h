@@ -514,6 +514,119 @@ int hjd_orient_set_normalize(hjd_orient* r, const float a[3], const float b[3]);
 int hjd_orient_launch(hjd_orient* r, void* stream);
 int hjd_orient_destroy(hjd_orient* r);
 
+/*
+ * Affine warp (extension; the reference has none): n planar uint8 RGB images,
+ * each of its own size, sampled through each image's own affine map to one
+ * common out_w x out_h in ONE launch: rotation, shear, arbitrary zoom, flips
+ * and translation -- the geometry of RandomAffine / RandomRotation -- into one
+ * (N, 3, out_h, out_w) batch.  It subsumes the crop, the resize without
+ * antialiasing, both flips and the eight orientations.
+ *
+ * Source and output: as the resize's.  Three uint8 planes R, G, B of src_w x
+ * src_h, rows src_pitch bytes apart, planes src_pitch * src_h apart; any
+ * pointer and any src_pitch >= src_w; dimensions in 1..16384.  A common out_w x
+ * out_h and out_pitch for all n items; out_format HJD_OUT_RGB_PLANAR (the bytes
+ * u8), HJD_OUT_RGB_PLANAR_F16 or _F32 (fma((float)u8, a[c], b[c]),
+ * hjd_warp_set_normalize, default a = 1, b = 0); dst and out_pitch multiples of
+ * the element size; the same rule decides between one vector store per plane
+ * and four pixels and guarded element stores.  Sources and outputs must not
+ * overlap.
+ *
+ * Definition (exact, integer).  m[6] is the INVERSE map, output to source, in
+ * Q16 (units of 1/65536 source pixel).  For output column j and row i, in
+ * 64-bit arithmetic:
+ *     X  = m[0] * j + m[1] * i + m[2]        Y  = m[3] * j + m[4] * i + m[5]
+ *     x0 = X >> 16 (floor)                   y0 = Y >> 16 (floor)
+ *     fx = (X & 0xffff) >> 5                 fy = (Y & 0xffff) >> 5
+ * X and Y are positions in source pixel INDICES: the centre of source pixel k
+ * lies at k * 65536, so the caller folds the half-pixel offsets of a
+ * centre-based map into m[2] and m[5].  fx, fy are the resize's 11-bit
+ * weights.  With the taps A = (x0, y0), B = (x0 + 1, y0), C = (x0, y0 + 1),
+ * D = (x0 + 1, y0 + 1), per channel:
+ *     u8 = (A (2048-fx)(2048-fy) + B fx (2048-fy) + C (2048-fx) fy + D fx fy
+ *           + 2^21) >> 22
+ * -- the resize's expression, one rounding.
+ *
+ * Taps outside the image.  A tap whose column is outside 0 .. src_w - 1 or
+ * whose row is outside 0 .. src_h - 1 is the channel's byte of `fill`
+ * (0x00RRGGBB): grid_sample(padding_mode = "zeros") at fill 0, an image
+ * library's masked fill otherwise.  With flags bit 0 (HJD_WARP_REPLICATE) the
+ * tap's coordinates are clamped into the image instead (padding_mode =
+ * "border").  A tap outside the image is never read from memory.  Other flag
+ * bits and `reserved` must be 0, fill <= 0xFFFFFF.
+ *
+ * What it leaves out.  There is no antialiasing: beyond a 2x reduction, decode
+ * at a scale first, as the resize says.  Q16 quantises a real matrix: with
+ * every entry rounded to nearest, the position of output pixel (j, i) is off
+ * by at most (j + i + 1) * 2^-17 source pixel per axis.  In terms of the
+ * integer matrix the result is exact.
+ *
+ * Laws.  {65536, 0, tx << 16, 0, 65536, ty << 16} is the crop at (tx, ty), byte
+ * for byte; {-65536, 0, (w - 1) << 16, 0, 65536, 0} the horizontal flip;
+ * {0, 65536, 0, -65536, 0, (h - 1) << 16} with an h x w output orientation 6;
+ * every orientation 1..8 is such an integer matrix (hjd_warp_orient of the
+ * identity); an output wholly outside the image is all `fill`.
+ *
+ * hjd_warp_roi: the smallest rectangle of a width x height frame that holds
+ * every tap an out_w x out_h output reads through m, after the tap range is
+ * clamped into the frame.  X and Y are affine, so their extrema Xmin, Xmax,
+ * Ymin, Ymax lie at the four output corners, and
+ *     x_lo = clamp(Xmin >> 16, 0, width - 1)
+ *     x_hi = clamp((Xmax >> 16) + 1, 0, width - 1)        (y the same)
+ *     *out = (x_lo, y_lo, x_hi - x_lo + 1, y_hi - y_lo + 1)
+ * The rectangle is never empty.  A tap inside the frame is inside it; a tap
+ * outside the frame is outside it on a side where the rectangle touches the
+ * frame's edge.  So, in both border modes, warping the frame's crop to *out
+ * with m[2] - (x_lo << 16) and m[5] - (y_lo << 16) equals warping the frame.
+ * HJD_E_INVALID for a NULL, width or height < 1 and an output dimension
+ * outside 1..16384.  Host only.
+ *
+ * hjd_warp_orient: m addresses the DISPLAYED image of a stored_w x stored_h
+ * image under `orientation` (the table above); out addresses the stored one.
+ * With (x, y) a displayed position, the stored position (xs, ys) is
+ *     1 (x, y)            2 (w - 1 - x, y)    3 (w - 1 - x, h - 1 - y)
+ *     4 (x, h - 1 - y)    5 (y, x)            6 (y, h - 1 - x)
+ *     7 (w - 1 - y, h - 1 - x)                8 (w - 1 - y, x)
+ * so out's rows are rows of m, negated and offset by (w - 1) << 16 or
+ * (h - 1) << 16: exact in integers.  HJD_E_INVALID if a composed entry leaves
+ * int32, for an orientation outside 1..8, a NULL and a stored size < 1.  Because
+ * fx and fy are truncated (a negated X rounds its weight the other way), the
+ * oriented warp is DEFINED as the warp of the stored image by the composed
+ * matrix.  It equals warp(orient(image)) exactly wherever X and Y are whole
+ * pixels (integer-translation matrices); elsewhere each lies within
+ * 0.5 + 2 * 255 / 2048 of the real-valued bilinear sample at the same position
+ * (the weight truncation moves a position by less than 1/2048 pixel per axis,
+ * bilinear is 255-Lipschitz per axis, the rounding adds 0.5).  Host only.
+ */
+enum { HJD_WARP_REPLICATE = 1 };
+typedef struct hjd_warp_item {
+    const void* src;   /* device: plane R of the source */
+    void* dst;         /* device: plane R of this item's output */
+    int32_t src_w, src_h, src_pitch, flags;   /* bit 0: HJD_WARP_REPLICATE; other bits 0 */
+    int32_t m[6];      /* inverse map, Q16 (1/65536 source pixel) */
+    uint32_t fill;     /* 0x00RRGGBB, <= 0xFFFFFF */
+    int32_t reserved;  /* 0 */
+} hjd_warp_item;       /* 64 bytes */
+typedef struct hjd_warp hjd_warp;
+int hjd_warp_roi(int width, int height, const int32_t m[6], int out_w, int out_h, hjd_rect* out);
+int hjd_warp_orient(const int32_t m[6], int stored_w, int stored_h, int orientation, int32_t out[6]);
+/* Validates what hjd_warp_create would take.  HJD_E_INVALID (with a message)
+ * for n outside 1..2^20, a NULL items / src / dst, a dimension outside
+ * 1..16384, src_pitch < src_w, unknown flag bits, fill > 0xFFFFFF, a non-zero
+ * reserved, a bad out_pitch or dst alignment and a non-planar or unknown
+ * format.  Host only: needs no device. */
+int hjd_warp_check(const hjd_warp_item* items, int n, int out_w, int out_h, int out_pitch, int out_format);
+/* Validates and uploads the item table (synchronously). */
+int hjd_warp_create(hjd_ctx* ctx, const hjd_warp_item* items, int n, int out_w, int out_h, int out_pitch,
+                    int out_format, hjd_warp** out);
+/* The float formats' constants for the launches that follow (an enqueued
+ * launch keeps its own).  HJD_E_INVALID for non-finite constants and for a
+ * byte-format object. */
+int hjd_warp_set_normalize(hjd_warp* w, const float a[3], const float b[3]);
+/* Enqueue the warp of all n items on `stream` (asynchronous, one kernel). */
+int hjd_warp_launch(hjd_warp* w, void* stream);
+int hjd_warp_destroy(hjd_warp* w);
+
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */
 int hjd_idct_blocks(hjd_ctx* ctx, const int32_t* d_in, int32_t* d_out, int64_t nblocks, void* stream);
@@ -605,6 +718,12 @@ int hjd_debug_kernel_table(int32_t* keys, int cap);
  * vertical one (intermediate -> outputs, reading whatever the intermediate
  * holds).  HJD_E_INVALID for another pass or a bilinear object. */
 int hjd_debug_resize_launch_pass(hjd_resize* r, int pass, void* stream);
+
+/* Timing only: hjd_warp_launch with the way the output is dealt to the waves
+ * given -- 0: a wave takes 64 consecutive quads of a row (the resize's way),
+ * 1: a wave takes a tile of 8 quads x 8 rows.  The results are the same bytes.
+ * HJD_E_INVALID for another value. */
+int hjd_debug_warp_launch_form(hjd_warp* w, int tiled, void* stream);
 
 #ifdef __cplusplus
 }

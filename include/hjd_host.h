@@ -283,6 +283,33 @@ int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const siz
 int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
                                      const hjd_rect* rois, const int32_t* orientations, const int32_t* flags, void* d_out,
                                      int out_w, int out_h, int32_t out_pitch, int filter, void* stream);
+/* Decode and warp (include/hjd.h hjd_warp_item defines the warp): frame i is
+ * sampled through m[i], its inverse map in Q16, into image i of the batch at
+ * d_out + i * 3 * out_pitch * out_h, under hjd_gdec_decode_resized's rules for
+ * d_out, out_pitch, the format (the decoder's current one, planar), the
+ * constants and the scale.  m[i] addresses the grid of the decoder's scale
+ * (source pixel indices of the scaled decode), and of the DISPLAYED image where
+ * orientations are given (orientations[i] in 1..8, NULL: all 1): the
+ * orientation is folded into the matrix on the host (hjd_warp_orient), so an
+ * oriented call costs no launch and no second scratch, and is defined as
+ * hjd_warp_orient defines it.  flags[i] is hjd_warp_item's (bit 0
+ * HJD_WARP_REPLICATE; NULL: all 0), fills[i] its fill (NULL: all 0).
+ *
+ * Only the part of a frame the warp reads is decoded: per frame the header is
+ * parsed, the orientation composed, hjd_warp_roi taken on the scaled stored
+ * frame and that rectangle decoded as hjd_gdec_decode_roi decodes one, as
+ * planar bytes into the decoder's grow-only scratch (as
+ * hjd_gdec_decode_resized's crops: 16-byte aligned, pitch rounded up to 4, the
+ * same growth rule); the matrix's translation is shifted to the crop and ONE
+ * warp launch for all n frames follows on the same stream.  Everything that
+ * can refuse the call -- the format, sizes, pitch, an orientation, flag bits,
+ * a fill above 0xFFFFFF, a composed or shifted entry that leaves int32
+ * (HJD_E_INVALID naming the frame), a crop above 16384, a scale the file's
+ * sampling does not serve -- is checked before anything is staged, allocated
+ * or enqueued.  The streams do not serve a warped decode. */
+int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
+                           const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
+                           int out_w, int out_h, int32_t out_pitch, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

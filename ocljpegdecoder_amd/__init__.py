@@ -56,6 +56,11 @@ from .backend import (  # noqa: E402
     roi_geometry,
     scaled_size,
     stream_worker_threads,
+    Warp,
+    WARP_REPLICATE,
+    warp_orient,
+    warp_roi,
+    warp_xform,
     worker_cpus,
 )
 
@@ -71,5 +76,6 @@ __all__ = [
     "device_worker_cpus", "stream_worker_threads", "scaled_size", "roi_geometry", "norm_constants", "frame_check",
     "OUT_RGB_PLANAR_F16", "OUT_RGB_PLANAR_F32", "Resize", "RESIZE_FLIP_H", "RESIZE_BILINEAR", "RESIZE_TRIANGLE_AA", "resize_scale",
     "Orient", "oriented_roi", "oriented_size", "exif_orientation",
+    "Warp", "WARP_REPLICATE", "warp_roi", "warp_orient", "warp_xform",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -56,6 +56,16 @@ class HjdOrientItem(ctypes.Structure):
 assert ctypes.sizeof(HjdOrientItem) == 40
 
 
+class HjdWarpItem(ctypes.Structure):
+    """struct hjd_warp_item (include/hjd.h): one image of a warp."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("src_w", "src_h", "src_pitch", "flags")] + \
+               [("m", ctypes.c_int32 * 6), ("fill", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(HjdWarpItem) == 64
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -158,6 +168,17 @@ SIGNATURES = {
                                                 ctypes.POINTER(ctypes.c_float)]),
     "hjd_orient_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hjd_orient_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_warp_roi": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(HjdRect)]),
+    "hjd_warp_orient": (ctypes.c_int, [c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p]),
+    "hjd_warp_check": (ctypes.c_int, [ctypes.POINTER(HjdWarpItem)] + [ctypes.c_int] * 5),
+    "hjd_warp_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdWarpItem)] + [ctypes.c_int] * 5 +
+                        [ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_warp_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float)]),
+    "hjd_warp_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_debug_warp_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "hjd_warp_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
     "hjd_debug_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -264,6 +285,9 @@ def _bind_host(lib):
                                                             ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, c_i32p, vp,
                                                             ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int,
                                                             vp]),
+        "hjd_gdec_decode_warped": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                  ctypes.c_int, ctypes.POINTER(ctypes.c_int32 * 6), c_i32p, c_i32p,
+                                                  c_u32p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -600,6 +600,175 @@ class Orient:
             pass
 
 
+WARP_REPLICATE = 1   # hjd_warp_item.flags bit 0
+
+
+def _xform(xform):
+    """Six Python ints of a warp's matrix; ValueError unless six int32 values."""
+    m = [int(v) for v in xform]
+    if len(m) != 6 or any(v != f for v, f in zip(m, xform)):
+        raise ValueError("a warp's matrix is six integers (Q16)")
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in m):
+        raise ValueError(f"a matrix entry leaves int32: {m}")
+    return m
+
+
+def warp_xform(src_w: int, src_h: int, out_w: int, out_h: int, angle: float = 0.0, zoom: float = 1.0,
+               shear=(0.0, 0.0), center=None, hflip: bool = False):
+    """The six Q16 integers (hjd_warp_item.m, the inverse map output -> source)
+    of an affine augmentation.  Pure Python, float64.
+
+    On pixel-centre coordinates (the centre of pixel k at k + 0.5) the output
+    position p = (j + 0.5, i + 0.5) reads the source position
+
+        s = ctr + zoom * A * (p - (out_w / 2, out_h / 2))
+
+    with ctr = center, by default (src_w / 2, src_h / 2): the output's centre
+    shows the source's.  zoom is source pixels per output pixel (2: the output
+    covers twice its own size of the source).  A is the inverse of an image
+    library's rotate-and-shear matrix: with r = -radians(angle) and
+    (sx, sy) = radians(shear),
+
+        a = cos(r - sy) / cos(sy)       b = -cos(r - sy) * tan(sx) / cos(sy) - sin(r)
+        c = sin(r - sy) / cos(sy)       d = -sin(r - sy) * tan(sx) / cos(sy) + cos(r)
+        A = [[d, -b], [-c, a]]          (no shear: [[cos t, -sin t], [sin t, cos t]], t = radians(angle))
+
+    so a positive angle turns the picture counter-clockwise on the screen
+    (angle = 90 on a square is orientation 8).  hflip mirrors the output:
+    column j shows what column out_w - 1 - j would (A's first column negated).
+    In source pixel indices (the centre of pixel k at k), X = s.x - 0.5:
+
+        m0 = A00   m1 = A01   m2 = ctr.x - 0.5 + A00 * (0.5 - out_w / 2) + A01 * (0.5 - out_h / 2)
+        m3 = A10   m4 = A11   m5 = ctr.y - 0.5 + A10 * (0.5 - out_w / 2) + A11 * (0.5 - out_h / 2)
+
+    times zoom where A appears, each times 65536 and rounded to nearest: the
+    position of output pixel (j, i) is then off by at most (j + i + 1) * 2**-17
+    pixel.  ValueError if an entry leaves int32."""
+    import math
+    r = -math.radians(float(angle))
+    sx, sy = (math.radians(float(v)) for v in shear)
+    a = math.cos(r - sy) / math.cos(sy)
+    b = -math.cos(r - sy) * math.tan(sx) / math.cos(sy) - math.sin(r)
+    c = math.sin(r - sy) / math.cos(sy)
+    d = -math.sin(r - sy) * math.tan(sx) / math.cos(sy) + math.cos(r)
+    z = float(zoom)
+    a00, a01, a10, a11 = z * d, z * -b, z * -c, z * a
+    if hflip:
+        a00, a10 = -a00, -a10
+    cx, cy = (src_w / 2.0, src_h / 2.0) if center is None else (float(center[0]), float(center[1]))
+    ox, oy = 0.5 - out_w / 2.0, 0.5 - out_h / 2.0
+    real = (a00, a01, cx - 0.5 + a00 * ox + a01 * oy, a10, a11, cy - 0.5 + a10 * ox + a11 * oy)
+    m = [int(math.floor(v * 65536.0 + 0.5)) for v in real]
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in m):
+        raise ValueError(f"a matrix entry leaves int32 (Q16): {m}")
+    return m
+
+
+def warp_roi(width: int, height: int, xform, out_w: int, out_h: int):
+    """hjd_warp_roi: the smallest (x, y, w, h) of a width x height frame that
+    holds every tap an out_w x out_h output reads through xform, the tap range
+    clamped into the frame (never empty).  Warping that crop with
+    xform[2] - (x << 16) and xform[5] - (y << 16) equals warping the frame."""
+    lib = _lib.load()
+    m, r = (ctypes.c_int32 * 6)(*_xform(xform)), _lib.HjdRect()
+    check(lib.hjd_warp_roi(int(width), int(height), m, int(out_w), int(out_h), ctypes.byref(r)), "hjd_warp_roi")
+    return (r.x, r.y, r.w, r.h)
+
+
+def warp_orient(xform, stored_w: int, stored_h: int, orientation: int):
+    """hjd_warp_orient: xform addresses the displayed image of a stored_w x
+    stored_h image under EXIF orientation 1..8; the six ints returned address
+    the stored image.  Exact; HjdError if an entry leaves int32."""
+    lib = _lib.load()
+    m, out = (ctypes.c_int32 * 6)(*_xform(xform)), (ctypes.c_int32 * 6)()
+    check(lib.hjd_warp_orient(m, int(stored_w), int(stored_h), int(orientation), out), "hjd_warp_orient")
+    return list(out)
+
+
+class Warp:
+    """hjd_warp: N planar uint8 RGB images of different sizes, each sampled
+    through its own affine map (six Q16 integers, warp_xform() makes them)
+    into one (N, 3, Ho, Wo) batch in one launch (include/hjd.h: bilinear,
+    11-bit integer weights, one rounding, no antialiasing).  Taps outside an
+    image are its fill colour, or with replicate its nearest pixel."""
+
+    def __init__(self, ctx: Context, srcs, out, xforms, fills=None, replicate=False, normalize=None):
+        """srcs and out as Resize takes them.  xforms: N sequences of six
+        ints.  fills: N colours 0xRRGGBB (default 0); replicate: one truthy
+        value for all images or N of them (WARP_REPLICATE).  normalize =
+        (a, b): the float dtypes' constants."""
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.handle = None
+        n = len(srcs)
+        if not (out.is_cuda and out.ndim == 4 and out.shape[1] == 3 and str(out.dtype) in _DTYPE_FORMATS):
+            raise ValueError("out must be a uint8 / float16 / float32 device tensor (N, 3, Ho, Wo)")
+        ho, wo = int(out.shape[2]), int(out.shape[3])
+        row = out.stride(2)   # elements between rows: Wo, or more for a [..., :Wo] view of wider rows
+        if out.stride(3) != 1 or row < wo or out.stride(1) != ho * row or (n > 1 and out.stride(0) != 3 * ho * row):
+            raise ValueError("out must be contiguous, or a [..., :Wo] view of a contiguous (N, 3, Ho, P) tensor")
+        if out.shape[0] != n:
+            raise ValueError(f"out holds {out.shape[0]} images, {n} sources given")
+        if len(xforms) != n:
+            raise ValueError("one matrix per source")
+        if fills is not None and len(fills) != n:
+            raise ValueError("one fill colour per source")
+        flags = _warp_flags(replicate, n)
+        self.out_format = _DTYPE_FORMATS[str(out.dtype)]
+        items = (_lib.HjdWarpItem * max(1, n))()
+        self._keep = []
+        for i, s in enumerate(srcs):
+            t, sp = Orient._planes(s, i, "source")
+            if t.element_size() != 1:
+                raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
+            self._keep.append(t)
+            items[i] = _lib.HjdWarpItem(t.data_ptr(), out[i].data_ptr(), int(t.shape[2]), int(t.shape[1]), int(sp),
+                                        flags[i], (ctypes.c_int32 * 6)(*_xform(xforms[i])),
+                                        int(fills[i]) if fills is not None else 0, 0)
+        self.out = out
+        h = ctypes.c_void_p()
+        check(self.lib.hjd_warp_create(ctx.handle, items, n, wo, ho, row * out.element_size(), self.out_format,
+                                       ctypes.byref(h)), "hjd_warp_create")
+        self.handle = h
+        if normalize is not None:
+            self.set_normalize(*normalize)
+
+    def set_normalize(self, a, b):
+        """hjd_warp_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
+        ca, cb = _norm_arrays((a, b))
+        check(self.lib.hjd_warp_set_normalize(self.handle, ca, cb), "hjd_warp_set_normalize")
+
+    def launch(self, stream=None):
+        """Enqueue the warp kernel (asynchronous)."""
+        check(self.lib.hjd_warp_launch(self.handle, _stream_ptr(stream)), "hjd_warp_launch")
+
+    def launch_form(self, tiled: bool, stream=None):
+        """Timing only (hjd_debug_warp_launch_form): the same launch with the
+        output dealt to the waves row-major (False) or in 8 x 8-quad tiles (True)."""
+        check(self.lib.hjd_debug_warp_launch_form(self.handle, 1 if tiled else 0, _stream_ptr(stream)),
+              "hjd_debug_warp_launch_form")
+
+    def close(self):
+        if self.handle:
+            self.lib.hjd_warp_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _warp_flags(replicate, n):
+    """Per-image hjd_warp_item.flags of a `replicate` argument: one value for all, or n of them."""
+    if isinstance(replicate, (list, tuple)):
+        if len(replicate) != n:
+            raise ValueError("one replicate flag per image")
+        return [WARP_REPLICATE if r else 0 for r in replicate]
+    return [WARP_REPLICATE if replicate else 0] * n
+
+
 def worker_cpus(bus: str, gpus: Sequence[str], sysfs_root: Optional[str] = None, only_allowed: bool = False):
     """hjd_debug_worker_cpus: the host CPUs the worker pool of the GPU at PCI
     address `bus` binds to, among the GPUs `gpus` (its NUMA node's CPUs split

@@ -410,6 +410,34 @@ int write_resize_records(hjd_gdec* g, const GdecCall& c)
     return HJD_OK;
 }
 
+// The warp kernel's records of a warped call (WarpStage): image i from its
+// crop in the scratch (c.d_outs[i], c.pitches[i], c.rois[i]) to its place in
+// the batch.  They lie where an oriented call's records would.
+int write_warp_records(hjd_gdec* g, const GdecCall& c)
+{
+    Staging& st = g->st;
+    const int n = static_cast<int>(st.frames.size());
+    const WarpStage& w = *c.warp;
+    hjd_internal::WarpRecord* recs = reinterpret_cast<hjd_internal::WarpRecord*>(
+        st.h_stage + st.H.recs + orient_records_offset(n, c.rois != nullptr));
+    const size_t image = 3 * static_cast<size_t>(w.out_pitch) * static_cast<size_t>(w.out_h);
+    for (int i = 0; i < n; ++i) {
+        hjd_internal::WarpRecord rec;
+        rec.src = c.d_outs[i];
+        rec.dst = static_cast<uint8_t*>(w.out) + image * static_cast<size_t>(i);
+        crop_size(g, c, i, rec.w, rec.h);
+        rec.pitch = c.pitches[i];
+        rec.flags = w.flags ? w.flags[i] : 0;
+        memcpy(rec.m, w.mats[i], sizeof(rec.m));
+        rec.fill = w.fills ? w.fills[i] : 0;
+        rec.reserved = 0;
+        const int rc = hjd_internal::warp_item_check(rec, i, g->out_format);
+        if (rc) return rc;
+        recs[i] = rec;
+    }
+    return HJD_OK;
+}
+
 }  // namespace
 
 int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
@@ -445,10 +473,13 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     g->batch_spec = spec;
     const uint32_t S = g->batch_sub_bits ? g->batch_sub_bits : static_cast<uint32_t>(st.caps.sub_bits);
     // a resized call's pixel kernels write planar bytes (the crops); its resize launch the decoder's format
-    // (an oriented call's too: its orient launch writes the decoder's format, or the resize's source)
-    const int pix_format = c.resize || c.orient ? HJD_OUT_RGB_PLANAR : g->out_format;
+    // (an oriented call's too: its orient launch writes the decoder's format, or the resize's source;
+    // and a warped call's: its warp launch writes the decoder's format)
+    const int pix_format = c.resize || c.orient || c.warp ? HJD_OUT_RGB_PLANAR : g->out_format;
     const bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
     const size_t recs_bytes = !c.d_outs ? 0
+                              : c.warp ? orient_records_offset(n, c.rois != nullptr) +
+                                             sizeof(hjd_internal::WarpRecord) * static_cast<size_t>(n)
                               : c.resize ? resize_records_offset(n, c.rois != nullptr, c.orient != nullptr) +
                                                resize_records_bytes(n, *c.resize)
                               : c.orient ? resize_records_offset(n, c.rois != nullptr, true)
@@ -468,6 +499,10 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
         }
         if (c.resize) {
             rc = write_resize_records(g, c);
+            if (rc) return rc;
+        }
+        if (c.warp) {
+            rc = write_warp_records(g, c);
             if (rc) return rc;
         }
     }
@@ -666,6 +701,13 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
                 rc = hjd_internal::launch_resize(g->device, recs, n, r.out_w, r.out_h, r.out_pitch, g->out_format,
                                                  g->norm, s);
             }
+            if (rc) return rc;
+        }
+        if (c.warp) {   // the crops -> the batch, behind the pixel kernels; `done` (below) covers it
+            const WarpStage& w = *c.warp;
+            const hjd_internal::WarpRecord* recs = reinterpret_cast<const hjd_internal::WarpRecord*>(
+                g->d_blob + g->st.H.recs + orient_records_offset(n, c.rois != nullptr));
+            rc = hjd_internal::launch_warp(g->device, recs, n, w.out_w, w.out_h, w.out_pitch, g->out_format, g->norm, s);
             if (rc) return rc;
         }
     }
@@ -1100,6 +1142,77 @@ int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, c
 {
     if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
     return decode_resized(g, datas, sizes, n, rois, orientations, flags, d_out, out_w, out_h, out_pitch, filter, stream);
+}
+
+int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
+                           const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
+                           int out_w, int out_h, int32_t out_pitch, void* stream)
+{
+    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
+    if (!m) return set_error(HJD_E_INVALID, "m is NULL");
+    if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
+    // everything that can refuse the call is checked before anything is staged, allocated or enqueued
+    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
+        return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
+                         hjd_internal::out_format_row_bytes(g->out_format));
+    if (n > g->st.caps.max_frames)
+        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
+    // per frame: the matrix on the stored image, the rectangle it reads (the
+    // crop, in the scratch: 16-byte aligned, its pitch rounded up to 4), the
+    // matrix on that crop
+    const size_t un = static_cast<size_t>(n);
+    std::vector<size_t> offs(un);
+    std::vector<int32_t> pitches(un);
+    std::vector<hjd_rect> rects(un);
+    std::vector<int32_t> mats(6 * un);
+    size_t need = 0;
+    hjd_internal::ScanHeader h;
+    for (int i = 0; i < n; ++i) {
+        if (!datas[i]) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
+        rc = hjd_internal::parse_scan_header(datas[i], sizes[i], &h);
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        const int sw = hjd_internal::scaled_dim(h.width, g->scale), sh = hjd_internal::scaled_dim(h.height, g->scale);
+        int32_t* mc = &mats[6 * static_cast<size_t>(i)];
+        rc = hjd_internal::warp_orient(m[i], sw, sh, orientations ? orientations[i] : 1, mc);
+        if (!rc) rc = hjd_internal::warp_roi(sw, sh, mc, out_w, out_h, &rects[i]);
+        if (!rc) {   // the rectangle, and the scale against the file's sampling
+            hjd_internal::RoiGeom rg;
+            rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rects[i], &rg);
+        }
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        const hjd_rect& r = rects[i];
+        if (r.w > hjd_internal::kResizeMaxDim || r.h > hjd_internal::kResizeMaxDim)
+            return set_error(HJD_E_INVALID, "frame %d: the warp reads a %d x %d crop, it takes up to %d", i, r.w, r.h,
+                             hjd_internal::kResizeMaxDim);
+        const int64_t tx = static_cast<int64_t>(mc[2]) - (static_cast<int64_t>(r.x) << 16);
+        const int64_t ty = static_cast<int64_t>(mc[5]) - (static_cast<int64_t>(r.y) << 16);
+        if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX)
+            return set_error(HJD_E_INVALID, "frame %d: the translation shifted to the crop at (%d, %d) leaves int32", i, r.x,
+                             r.y);
+        mc[2] = static_cast<int32_t>(tx);
+        mc[5] = static_cast<int32_t>(ty);
+        if (flags && (flags[i] & ~HJD_WARP_REPLICATE))
+            return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: HJD_WARP_REPLICATE)", i,
+                             static_cast<unsigned>(flags[i] & ~HJD_WARP_REPLICATE));
+        if (fills && fills[i] > 0xFFFFFFu)
+            return set_error(HJD_E_INVALID, "frame %d: fill 0x%x is above 0xFFFFFF (0x00RRGGBB)", i, fills[i]);
+        pitches[i] = (r.w + 3) & ~3;
+        offs[i] = need;
+        need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(r.h), 16);
+    }
+    rc = grow_scratch(g, need, "crops");
+    if (rc) return rc;
+    std::vector<void*> crops(un);
+    for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
+    WarpStage stage{d_out, out_w, out_h, out_pitch, reinterpret_cast<const int32_t(*)[6]>(mats.data()), flags, fills};
+    GdecCall c = make_call(datas, sizes, n, stream);
+    c.d_outs = crops.data();
+    c.pitches = pitches.data();
+    c.rois = rects.data();
+    c.warp = &stage;
+    return gdec_run(g, c);
 }
 
 int hjd_gdec_decode_coefs(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, int16_t* d_coefs,

@@ -103,6 +103,19 @@ struct OrientStage {
     int out_format;
 };
 
+// The second stage of hjd_gdec_decode_warped: the call's d_outs are the crops
+// hjd_warp_roi found, in the decoder's scratch (HJD_OUT_RGB_PLANAR), its rois
+// those rectangles, and one warp launch behind the pixel kernels takes crop i
+// through mats[i] -- orientation composed, translation shifted to the crop --
+// to `out` in the decoder's format.
+struct WarpStage {
+    void* out;                     // image i at out + i * 3 * out_pitch * out_h
+    int out_w, out_h, out_pitch;
+    const int32_t (*mats)[6];      // per image
+    const int32_t* flags;          // per image, or null
+    const uint32_t* fills;         // per image, or null
+};
+
 // One call of the decoder: everything that belongs to the call and not to
 // the object.  gdec_run reads all of it; gdec_issue (frames already staged in
 // g->st) all but datas, sizes and n.
@@ -119,6 +132,7 @@ struct GdecCall {
     const HostCopy* host = nullptr;     // per frame, or null
     const ResizeStage* resize = nullptr;   // hjd_gdec_decode_resized, or null
     const OrientStage* orient = nullptr;   // hjd_gdec_decode_oriented / _resized_oriented, or null
+    const WarpStage* warp = nullptr;       // hjd_gdec_decode_warped, or null (then neither of the two above)
     // early pull of a latency decoder's lone image (gdec_early_pull)
     hjd_gdec* early_g = nullptr;        // non-null while the call's host destuff may pull
     size_t prepulled = 0;               // data-area bytes of frame 0 already pulled

@@ -282,6 +282,30 @@ int orient_roi(int width, int height, int orientation, const ::hjd_rect& display
 int launch_orient(int device, const OrientRecord* d_items, int n, int64_t tiles, int out_format, const NormRecord& norm,
                   void* stream);
 
+// The affine warp kernel (hjd_warp.hip; include/hjd.h hjd_warp_*).  One
+// image's record as the kernel reads it (layout of hjd::WarpDev and of
+// hjd_warp_item).
+struct WarpRecord {
+    const void* src;
+    void* dst;
+    int32_t w, h, pitch, flags;
+    int32_t m[6];
+    uint32_t fill;
+    int32_t reserved;
+};
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: one item's side
+// of hjd_warp_check (the output's side is resize_out_check).
+int warp_item_check(const WarpRecord& it, int index, int out_format);
+// hjd_warp_roi and hjd_warp_orient without the NULL checks.
+int warp_roi(int width, int height, const int32_t m[6], int out_w, int out_h, ::hjd_rect* out);
+int warp_orient(const int32_t m[6], int stored_w, int stored_h, int orientation, int32_t out[6]);
+// One warp_kernel launch over n records in device memory (no host
+// synchronisation); the arguments have passed the two checks.  tiled: 1 a
+// wave takes 8 quads x 8 rows, 0 it takes 64 consecutive quads; -1 the
+// library's choice (hjd::kWarpTiled).
+int launch_warp(int device, const WarpRecord* d_items, int n, int out_w, int out_h, int out_pitch, int out_format,
+                const NormRecord& norm, void* stream, int tiled = -1);
+
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe
 // the whole image; the rest the scan.

@@ -597,6 +597,81 @@ class GpuDecoder:
                                    lambda: self.decode_resized(datas, out, stream, rois=rois, flips=flips,
                                                                antialias=antialias, orientations=orients), out)
 
+    def decode_warped(self, datas: Sequence[bytes], out, xforms, stream=None, fills=None, replicate=False,
+                      apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None):
+        """hjd_gdec_decode_warped: decode and sample every image through its
+        own affine map xforms[i] (six Q16 ints, the inverse map output ->
+        source pixel indices; warp_xform() makes them) into `out`, a
+        contiguous device tensor (N, 3, Ho, Wo) whose dtype is the decoder's
+        current planar format's.  The matrices address the grid of the
+        decoder's scale, and the displayed image where apply_exif_orientation
+        or orientations (as decode()) give an orientation: it is folded into
+        the matrix, at no launch.  fills: one colour 0xRRGGBB per image for
+        taps outside it (default 0); replicate (one value, or one per image):
+        the nearest pixel of the image instead.  Only the rectangle of each
+        frame the warp reads is decoded, into the scratch decode_resized()
+        uses, under its growth rule."""
+        from .backend import _warp_flags, _xform
+        _keep, arr_d, arr_s = _byte_arrays(datas)
+        n = len(datas)
+        if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
+            raise ValueError(f"out must be a contiguous device tensor ({n}, 3, Ho, Wo)")
+        elem = {3: 1, 5: 2, 6: 4}.get(self.out_format)   # the planar formats (any other: the library refuses)
+        if elem is not None and out.element_size() != elem:
+            raise ValueError(f"out's dtype {out.dtype} is not the decoder's output format ({self.out_format})")
+        if len(xforms) != n:
+            raise ValueError("one matrix per JPEG")
+        mats = ((ctypes.c_int32 * 6) * n)(*[(ctypes.c_int32 * 6)(*_xform(x)) for x in xforms])
+        fl = (ctypes.c_int32 * n)(*_warp_flags(replicate, n))
+        fi = None
+        if fills is not None:
+            if len(fills) != n:
+                raise ValueError("one fill colour per JPEG")
+            if any(not 0 <= int(f) <= 0xFFFFFF for f in fills):
+                raise ValueError("a fill colour is 0xRRGGBB")
+            fi = (ctypes.c_uint32 * n)(*[int(f) for f in fills])
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        ho, wo = int(out.shape[2]), int(out.shape[3])
+        check(self.lib.hjd_gdec_decode_warped(self.handle, arr_d, arr_s, n, mats,
+                                              (ctypes.c_int32 * n)(*orients) if orients is not None else None, fl, fi,
+                                              out.data_ptr(), wo, ho, wo * out.element_size(), _stream_handle(stream)),
+              "hjd_gdec_decode_warped")
+        self._n = n
+
+    def decode_rgb_warped(self, datas: Sequence[bytes], size, xforms, fill=0, replicate=False, out=None, stream=None,
+                          scale: int = 1, dtype=_UINT8, mean=None, std=None, apply_exif_orientation: bool = False,
+                          orientations: Optional[Sequence[int]] = None):
+        """decode_rgb with size = (h, w) and one affine map per image
+        (decode_warped): rotation, shear, zoom, flips and translation on the
+        GPU, and ONE (N, 3, h, w) tensor of the dtype comes back: `out` if
+        given (a contiguous device tensor of exactly that shape and dtype),
+        else a new one.  xforms[i]: six Q16 ints as warp_xform(W, H, w, h,
+        angle, zoom, ...) returns them for the image's size (W, H) at `scale`
+        -- as displayed, where an orientation applies.  fill: one colour
+        0xRRGGBB, or one per image, for what lies outside the image;
+        replicate: its border pixels instead.  No antialiasing: keep the zoom
+        within 2 by decoding at a `scale`.  dtype, mean, std and scale as
+        decode_rgb; the batch is planar.  Asynchronous; the decoder's format,
+        scale and constants are restored afterwards."""
+        import torch
+        _chw, dtype, fmt, norm = self._rgb_format("chw", dtype, mean, std)
+        size = (int(size[0]), int(size[1]))
+        if min(size) < 1:
+            raise ValueError(f"size must be (h, w) with h, w >= 1, got {size}")
+        if len(xforms) != len(datas):
+            raise ValueError("one matrix per JPEG")
+        fills = list(fill) if isinstance(fill, (list, tuple)) else [fill] * len(datas)
+        shape = (len(datas), 3) + size
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.ctx.device))
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == shape):
+            raise ValueError(f"out must be a contiguous {dtype} device tensor {shape}")
+        return self._with_settings(scale, fmt, norm,
+                                   lambda: self.decode_warped(datas, out, xforms, stream, fills=fills,
+                                                              replicate=replicate,
+                                                              apply_exif_orientation=apply_exif_orientation,
+                                                              orientations=orientations), out)
+
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
         returns each frame's first block."""
