@@ -1,7 +1,8 @@
 // hjd_gdec.hip -- the GPU entropy decoder object (include/hjd_host.h hjd_gdec_*;
 // DESIGN.md s10): its device buffers, the policy that picks a batch's sync and
 // subsequence length, and the issue of a staged batch -- uploads, the entropy
-// kernels (launched in hjd_entropy.hip), then the fused pixel kernel.
+// kernels (launched in hjd_entropy.hip), then the fused pixel kernel.  The
+// calls with stages behind the pixel kernels are hjd_gdec_post.hip's.
 #include "hjd_gdec.hpp"
 
 #include <algorithm>
@@ -18,12 +19,6 @@ using hjd_internal::FrameRecord;
 using hjd_internal::set_error;
 using hjd_internal::tuning;
 using namespace hjd::ent;
-
-#define HJD_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // Policy: a batch's sync, its subsequence length S and its lead-in
@@ -313,131 +308,6 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, int out_format, bool fno
     return HJD_OK;
 }
 
-// Where an oriented call's records lie behind the pixel kernel's tables (from H.recs).
-inline size_t orient_records_offset(int n, bool roi)
-{
-    return hjd_internal::align_up(pixel_tables_bytes(n, roi, false), 16);
-}
-
-// Where a resized call's records lie (from H.recs): behind the pixel kernel's
-// tables and, in an oriented call, the orient records.
-inline size_t resize_records_offset(int n, bool roi, bool orient)
-{
-    return orient_records_offset(n, roi) +
-           (orient ? hjd_internal::align_up(sizeof(hjd_internal::OrientRecord) * static_cast<size_t>(n), 16) : 0);
-}
-
-// The stored crop of image i as the pixel kernels write it: its size.
-inline void crop_size(const hjd_gdec* g, const GdecCall& c, int i, int& w, int& h)
-{
-    const Prepared& p = g->st.frames[i];
-    w = c.rois ? c.rois[i].w : hjd_internal::scaled_dim(p.width, g->scale);
-    h = c.rois ? c.rois[i].h : hjd_internal::scaled_dim(p.height, g->scale);
-}
-
-// The orient kernel's records of an oriented call (OrientStage): image i from
-// its stored crop in the scratch (c.d_outs[i], c.pitches[i]) to o.outs[i].
-// Returns the launch's tiles in *tiles.
-int write_orient_records(hjd_gdec* g, const GdecCall& c, int64_t* tiles)
-{
-    Staging& st = g->st;
-    const int n = static_cast<int>(st.frames.size());
-    const OrientStage& o = *c.orient;
-    hjd_internal::OrientRecord* recs = reinterpret_cast<hjd_internal::OrientRecord*>(
-        st.h_stage + st.H.recs + orient_records_offset(n, c.rois != nullptr));
-    *tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        hjd_internal::OrientRecord rec;
-        rec.src = c.d_outs[i];
-        rec.dst = o.outs[i];
-        crop_size(g, c, i, rec.w, rec.h);
-        rec.pitch = c.pitches[i];
-        rec.orientation = o.orientations[i];
-        rec.dst_pitch = o.out_pitches[i];
-        rec.tile_begin = static_cast<uint32_t>(*tiles);
-        const int rc = hjd_internal::orient_item_check(rec, i, o.out_format);
-        if (rc) return rc;
-        *tiles += hjd_internal::orient_tiles(rec.w, rec.h);
-        recs[i] = rec;
-    }
-    return HJD_OK;
-}
-
-// Resize records of a resized call: n, or with the antialiased filter 2 n
-// (the horizontal launch's, then the vertical launch's).
-inline size_t resize_records_bytes(int n, const ResizeStage& r)
-{
-    return sizeof(hjd_internal::ResizeRecord) * static_cast<size_t>(n) * (r.mids ? 2 : 1);
-}
-
-// The resize kernel's records of a resized call (ResizeStage): image i from
-// its crop in the scratch (c.d_outs[i], c.pitches[i]) to its place in the
-// batch -- with the antialiased filter by way of its intermediate r.mids[i].
-int write_resize_records(hjd_gdec* g, const GdecCall& c)
-{
-    Staging& st = g->st;
-    const int n = static_cast<int>(st.frames.size());
-    const ResizeStage& r = *c.resize;
-    hjd_internal::ResizeRecord* recs = reinterpret_cast<hjd_internal::ResizeRecord*>(
-        st.h_stage + st.H.recs + resize_records_offset(n, c.rois != nullptr, c.orient != nullptr));
-    const size_t image = 3 * static_cast<size_t>(r.out_pitch) * static_cast<size_t>(r.out_h);
-    for (int i = 0; i < n; ++i) {
-        hjd_internal::ResizeRecord rec;
-        rec.src = c.d_outs[i];
-        rec.dst = static_cast<uint8_t*>(r.out) + image * static_cast<size_t>(i);
-        crop_size(g, c, i, rec.w, rec.h);
-        rec.pitch = c.pitches[i];
-        if (c.orient) {   // the resize reads the oriented crop
-            rec.src = c.orient->outs[i];
-            rec.pitch = c.orient->out_pitches[i];
-            if (hjd_internal::orientation_transposes(c.orient->orientations[i])) std::swap(rec.w, rec.h);
-        }
-        rec.flags = r.flags ? r.flags[i] : 0;
-        const int rc = hjd_internal::resize_item_check(rec, i, g->out_format);
-        if (rc) return rc;
-        recs[i] = rec;
-        if (r.mids) {
-            hjd_internal::ResizeRecord& v = recs[n + i];
-            v.src = r.mids[i];
-            v.dst = rec.dst;
-            v.w = r.out_w;
-            v.h = rec.h;
-            v.pitch = hjd_internal::resize_aa_pitch(r.out_w);
-            v.flags = 0;   // (the flip is the horizontal pass's)
-            recs[i].dst = r.mids[i];
-        }
-    }
-    return HJD_OK;
-}
-
-// The warp kernel's records of a warped call (WarpStage): image i from its
-// crop in the scratch (c.d_outs[i], c.pitches[i], c.rois[i]) to its place in
-// the batch.  They lie where an oriented call's records would.
-int write_warp_records(hjd_gdec* g, const GdecCall& c)
-{
-    Staging& st = g->st;
-    const int n = static_cast<int>(st.frames.size());
-    const WarpStage& w = *c.warp;
-    hjd_internal::WarpRecord* recs = reinterpret_cast<hjd_internal::WarpRecord*>(
-        st.h_stage + st.H.recs + orient_records_offset(n, c.rois != nullptr));
-    const size_t image = 3 * static_cast<size_t>(w.out_pitch) * static_cast<size_t>(w.out_h);
-    for (int i = 0; i < n; ++i) {
-        hjd_internal::WarpRecord rec;
-        rec.src = c.d_outs[i];
-        rec.dst = static_cast<uint8_t*>(w.out) + image * static_cast<size_t>(i);
-        crop_size(g, c, i, rec.w, rec.h);
-        rec.pitch = c.pitches[i];
-        rec.flags = w.flags ? w.flags[i] : 0;
-        memcpy(rec.m, w.mats[i], sizeof(rec.m));
-        rec.fill = w.fills ? w.fills[i] : 0;
-        rec.reserved = 0;
-        const int rc = hjd_internal::warp_item_check(rec, i, g->out_format);
-        if (rc) return rc;
-        recs[i] = rec;
-    }
-    return HJD_OK;
-}
-
 }  // namespace
 
 int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
@@ -472,37 +342,24 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     }
     g->batch_spec = spec;
     const uint32_t S = g->batch_sub_bits ? g->batch_sub_bits : static_cast<uint32_t>(st.caps.sub_bits);
-    // a resized call's pixel kernels write planar bytes (the crops); its resize launch the decoder's format
-    // (an oriented call's too: its orient launch writes the decoder's format, or the resize's source;
-    // and a warped call's: its warp launch writes the decoder's format)
-    const int pix_format = c.resize || c.orient || c.warp ? HJD_OUT_RGB_PLANAR : g->out_format;
-    const bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
-    const size_t recs_bytes = !c.d_outs ? 0
-                              : c.warp ? orient_records_offset(n, c.rois != nullptr) +
-                                             sizeof(hjd_internal::WarpRecord) * static_cast<size_t>(n)
-                              : c.resize ? resize_records_offset(n, c.rois != nullptr, c.orient != nullptr) +
-                                               resize_records_bytes(n, *c.resize)
-                              : c.orient ? resize_records_offset(n, c.rois != nullptr, true)
-                                         : pixel_tables_bytes(n, c.rois != nullptr, fnorm);
+    int pix_format = g->out_format;
+    bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
+    size_t recs_bytes = c.d_outs ? pixel_tables_bytes(n, c.rois != nullptr, fnorm) : 0;
+    if (c.post) {   // the pixel kernels write planar bytes (the crops); the last stage the decoder's format
+        pix_format = HJD_OUT_RGB_PLANAR;
+        fnorm = false;
+        recs_bytes = c.post->recs_bytes;
+    }
     EntBatchDev b;
     int rc = st.assemble(g->d_blob, coefs, c.block_offsets, S, recs_bytes,
                          c.d_outs ? 192 * 4 * static_cast<size_t>(n) : 0, b);
     if (rc) return rc;
     PixelClasses px;
-    int64_t orient_tiles = 0;
     if (c.d_outs) {
         rc = write_pixel_records(g, c, pix_format, fnorm, px);
         if (rc) return rc;
-        if (c.orient) {
-            rc = write_orient_records(g, c, &orient_tiles);
-            if (rc) return rc;
-        }
-        if (c.resize) {
-            rc = write_resize_records(g, c);
-            if (rc) return rc;
-        }
-        if (c.warp) {
-            rc = write_warp_records(g, c);
+        if (c.post) {
+            rc = post_write_records(g, *c.post, n);
             if (rc) return rc;
         }
     }
@@ -677,37 +534,8 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
             rc = hjd_internal::launch_decode(l);
             if (rc) return rc;
         }
-        if (c.orient) {   // the stored crops -> the oriented images, behind the pixel kernels
-            const hjd_internal::OrientRecord* recs = reinterpret_cast<const hjd_internal::OrientRecord*>(
-                g->d_blob + g->st.H.recs + orient_records_offset(n, c.rois != nullptr));
-            rc = hjd_internal::launch_orient(g->device, recs, n, orient_tiles, c.orient->out_format, g->norm, s);
-            if (rc) return rc;
-        }
-        if (c.resize) {   // the crops -> the batch, behind the pixel kernels; `done` (below) covers it
-            const ResizeStage& r = *c.resize;
-            const hjd_internal::ResizeRecord* recs = reinterpret_cast<const hjd_internal::ResizeRecord*>(
-                g->d_blob + g->st.H.recs + resize_records_offset(n, c.rois != nullptr, c.orient != nullptr));
-            if (r.mids) {
-                int max_h = 1;
-                for (int i = 0; i < n; ++i) {
-                    int cw, ch;
-                    crop_size(g, c, i, cw, ch);
-                    if (c.orient && hjd_internal::orientation_transposes(c.orient->orientations[i])) ch = cw;
-                    max_h = std::max(max_h, ch);
-                }
-                rc = hjd_internal::launch_resize_aa(g->device, recs, recs + n, n, max_h, r.out_w, r.out_h, r.out_pitch,
-                                                    g->out_format, g->norm, s);
-            } else {
-                rc = hjd_internal::launch_resize(g->device, recs, n, r.out_w, r.out_h, r.out_pitch, g->out_format,
-                                                 g->norm, s);
-            }
-            if (rc) return rc;
-        }
-        if (c.warp) {   // the crops -> the batch, behind the pixel kernels; `done` (below) covers it
-            const WarpStage& w = *c.warp;
-            const hjd_internal::WarpRecord* recs = reinterpret_cast<const hjd_internal::WarpRecord*>(
-                g->d_blob + g->st.H.recs + orient_records_offset(n, c.rois != nullptr));
-            rc = hjd_internal::launch_warp(g->device, recs, n, w.out_w, w.out_h, w.out_pitch, g->out_format, g->norm, s);
+        if (c.post) {   // behind the pixel kernels; `done` (below) covers them
+            rc = post_launch(g, *c.post, n, s);
             if (rc) return rc;
         }
     }
@@ -740,8 +568,9 @@ int plan_staged(const Staging& st, const uint8_t* data, size_t size, RawCursor& 
     return plan_raw(st, data, size, cur, mode, raw_off, fits, data_room, reserve, true);
 }
 
-// Stage the call's JPEGs on the calling thread, then issue.
-int gdec_run(hjd_gdec* g, GdecCall& c)
+}  // namespace
+
+int hjd::ent::gdec_run(hjd_gdec* g, GdecCall& c)
 {
     if (!g || !c.datas || !c.sizes) return set_error(HJD_E_INVALID, "NULL argument");
     const auto t0 = std::chrono::steady_clock::now();
@@ -778,15 +607,53 @@ int gdec_run(hjd_gdec* g, GdecCall& c)
     return HJD_OK;
 }
 
-// The descriptor of an hjd_gdec_decode* call: its inputs and its stream.
-GdecCall make_call(const uint8_t* const* datas, const size_t* sizes, int n, void* stream)
+int hjd::ent::admit_frame(const Admit& a, const uint8_t* data, size_t size, int i, const hjd_rect* roi, hjd_rect* crop)
 {
-    GdecCall c;
-    c.datas = datas;
-    c.sizes = sizes;
-    c.n = n;
-    c.stream = static_cast<hipStream_t>(stream);
-    return c;
+    hjd_internal::ScanHeader h;
+    int rc = data ? hjd_internal::parse_scan_header(data, size, &h) : HJD_E_INVALID;
+    if (rc && a.lenient) return HJD_OK;
+    if (!data) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
+    if (!rc) {
+        *crop = hjd_rect{0, 0, hjd_internal::scaled_dim(h.width, a.scale), hjd_internal::scaled_dim(h.height, a.scale)};
+        if (a.map) rc = a.map(a.ctx, i, crop->w, crop->h, roi, crop);
+        else if (roi) *crop = *roi;
+    }
+    if (!rc && (a.map || roi)) {   // the rectangle, and the scale against the file's sampling
+        hjd_internal::RoiGeom rg;
+        rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, a.scale, crop, &rg);
+    } else if (!rc && a.scale != 1) {   // a whole frame: a file the scaled kernels do not serve
+        hjd_internal::DecodeShape shape;
+        shape.scale = a.scale;
+        shape.sampling = h.sampling;
+        rc = hjd_internal::shape_check(shape);
+    }
+    if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+    if (a.cap_fmt && (crop->w > hjd_internal::kResizeMaxDim || crop->h > hjd_internal::kResizeMaxDim))
+        return set_error(HJD_E_INVALID, a.cap_fmt, i, crop->w, crop->h, hjd_internal::kResizeMaxDim);
+    return HJD_OK;
+}
+
+namespace {
+
+// hjd_gdec_decode (rois null) and _roi.  An invalid rectangle, or a scale the
+// file's sampling does not serve, is refused before anything is staged or
+// enqueued (a file that is null or malformed fails in staging).
+int decode_pixels(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                  void* const* d_outs, const int32_t* pitches, void* stream)
+{
+    if (g && datas && sizes && (rois || g->scale != 1)) {
+        const Admit admit{g->scale, true, nullptr, nullptr, nullptr};
+        hjd_rect crop;
+        for (int i = 0; i < n; ++i) {
+            const int rc = admit_frame(admit, datas[i], sizes[i], i, rois ? &rois[i] : nullptr, &crop);
+            if (rc) return rc;
+        }
+    }
+    GdecCall c(datas, sizes, n, stream);
+    c.d_outs = d_outs;
+    c.pitches = pitches;
+    c.rois = rois;
+    return gdec_run(g, c);
 }
 
 }  // namespace
@@ -850,23 +717,7 @@ int hjd_gdec_decode(hjd_gdec* g, const uint8_t* const* datas, const size_t* size
                     const int32_t* pitches, void* stream)
 {
     if (!d_outs) return set_error(HJD_E_INVALID, "d_outs is NULL");
-    if (g && g->scale != 1 && datas && sizes) {
-        // a scaled call refuses a file the scaled kernels do not serve before
-        // anything is staged or enqueued (a malformed file fails in staging)
-        hjd_internal::ScanHeader h;
-        hjd_internal::DecodeShape shape;
-        shape.scale = g->scale;
-        for (int i = 0; i < n; ++i) {
-            if (!datas[i] || hjd_internal::parse_scan_header(datas[i], sizes[i], &h) != HJD_OK) continue;
-            shape.sampling = h.sampling;
-            if (hjd_internal::shape_check(shape) != HJD_OK)
-                return set_error(HJD_E_INVALID, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-        }
-    }
-    GdecCall c = make_call(datas, sizes, n, stream);
-    c.d_outs = d_outs;
-    c.pitches = pitches;
-    return gdec_run(g, c);
+    return decode_pixels(g, datas, sizes, n, nullptr, d_outs, pitches, stream);
 }
 
 int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
@@ -874,345 +725,7 @@ int hjd_gdec_decode_roi(hjd_gdec* g, const uint8_t* const* datas, const size_t* 
 {
     if (!d_outs) return set_error(HJD_E_INVALID, "d_outs is NULL");
     if (!rois) return set_error(HJD_E_INVALID, "rois is NULL");
-    if (g && datas && sizes) {
-        // an invalid rectangle, or a scale the file's sampling does not serve,
-        // is refused before anything is staged or enqueued (a malformed file
-        // fails in staging)
-        hjd_internal::ScanHeader h;
-        hjd_internal::RoiGeom rg;
-        for (int i = 0; i < n; ++i)
-            if (datas[i] && hjd_internal::parse_scan_header(datas[i], sizes[i], &h) == HJD_OK) {
-                const int rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rois[i], &rg);
-                if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-            }
-    }
-    GdecCall c = make_call(datas, sizes, n, stream);
-    c.d_outs = d_outs;
-    c.pitches = pitches;
-    c.rois = rois;
-    return gdec_run(g, c);
-}
-
-int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
-                            const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
-{
-    return hjd_gdec_decode_resized_filter(g, datas, sizes, n, rois, flags, d_out, out_w, out_h, out_pitch,
-                                          HJD_RESIZE_BILINEAR, stream);
-}
-
-// Grow the decoder's scratch to `need` bytes (grow-only; the previous call may
-// still use the old buffer, so growing waits for it).
-static int grow_scratch(hjd_gdec* g, size_t need, const char* what)
-{
-    if (need <= g->crops_bytes) return HJD_OK;
-    HJD_HIP(hipSetDevice(g->device));
-    if (g->pending) HJD_HIP(hipEventSynchronize(g->done));
-    if (g->d_crops) (void)hipFree(g->d_crops);
-    g->d_crops = nullptr;
-    g->crops_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&g->d_crops), need) != hipSuccess) {
-        (void)hipGetLastError();
-        g->d_crops = nullptr;
-        return set_error(HJD_E_NOMEM, "the %s of this call need %zu bytes of device memory", what, need);
-    }
-    g->crops_bytes = need;
-    return HJD_OK;
-}
-
-// HJD_OK if every orientation lies in 1..8; *any says whether one is not 1.
-static int orientations_check(const int32_t* orientations, int n, bool* any)
-{
-    *any = false;
-    for (int i = 0; i < n; ++i) {
-        if (!hjd_internal::orientation_ok(orientations[i]))
-            return set_error(HJD_E_INVALID, "frame %d: orientation %d is outside 1..8", i, orientations[i]);
-        *any = *any || orientations[i] != 1;
-    }
-    return HJD_OK;
-}
-
-// The stored crop of frame i of an oriented call, everything about it checked:
-// the file's header, the display rectangle (rois, or null: the whole frame)
-// mapped to the stored one (*stored; roi_geom checks it against the sampling
-// and the scale), the crop's size.
-static int oriented_crop(const hjd_gdec* g, const uint8_t* data, size_t size, int i, int orientation,
-                         const hjd_rect* rois, hjd_rect* stored, int* cw, int* ch)
-{
-    if (!data) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
-    hjd_internal::ScanHeader h;
-    int rc = hjd_internal::parse_scan_header(data, size, &h);
-    if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-    const int sw = hjd_internal::scaled_dim(h.width, g->scale), sh = hjd_internal::scaled_dim(h.height, g->scale);
-    if (rois) {
-        rc = hjd_internal::orient_roi(sw, sh, orientation, rois[i], stored);
-        if (!rc) {
-            hjd_internal::RoiGeom rg;
-            rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, stored, &rg);
-        }
-        *cw = stored->w;
-        *ch = stored->h;
-    } else {
-        hjd_internal::DecodeShape shape;
-        shape.scale = g->scale;
-        shape.sampling = h.sampling;
-        rc = g->scale != 1 ? hjd_internal::shape_check(shape) : HJD_OK;
-        *cw = sw;
-        *ch = sh;
-    }
-    if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-    if (*cw > hjd_internal::kResizeMaxDim || *ch > hjd_internal::kResizeMaxDim)
-        return set_error(HJD_E_INVALID, "frame %d: the crop is %d x %d, the orientation and the resize take up to %d", i,
-                         *cw, *ch, hjd_internal::kResizeMaxDim);
-    return HJD_OK;
-}
-
-int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
-                             const int32_t* orientations, void* const* d_outs, const int32_t* pitches, void* stream)
-{
-    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
-    if (!d_outs) return set_error(HJD_E_INVALID, "d_outs is NULL");
-    if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
-    if (!pitches) return set_error(HJD_E_INVALID, "pitches is NULL");
-    // everything that can refuse the call is checked before anything is staged, allocated or enqueued
-    int rc = hjd_internal::orient_out_check(n, g->out_format);
-    if (rc) return rc;
-    bool any = false;
-    rc = orientations_check(orientations, n, &any);
-    if (rc) return rc;
-    if (!any)   // nothing to orient: today's call, no scratch and no extra launch
-        return rois ? hjd_gdec_decode_roi(g, datas, sizes, n, rois, d_outs, pitches, stream)
-                    : hjd_gdec_decode(g, datas, sizes, n, d_outs, pitches, stream);
-    if (n > g->st.caps.max_frames)
-        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
-    // the stored crops in the scratch: each 16-byte aligned, its pitch rounded up to 4
-    std::vector<size_t> offs(static_cast<size_t>(n));
-    std::vector<int32_t> crop_pitches(static_cast<size_t>(n));
-    std::vector<hjd_rect> stored(rois ? static_cast<size_t>(n) : 0);
-    size_t need = 0;
-    int64_t tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        int cw, ch;
-        rc = oriented_crop(g, datas[i], sizes[i], i, orientations[i], rois, rois ? &stored[i] : nullptr, &cw, &ch);
-        if (rc) return rc;
-        // the record's checks on the caller's side of it (its source, a place in the scratch, comes below)
-        hjd_internal::OrientRecord rec{g, d_outs[i], cw, ch, (cw + 3) & ~3, orientations[i], pitches[i], 0};
-        rc = hjd_internal::orient_item_check(rec, i, g->out_format);
-        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-        tiles += hjd_internal::orient_tiles(cw, ch);
-        crop_pitches[i] = rec.pitch;
-        offs[i] = need;
-        need = hjd_internal::align_up(need + 3 * static_cast<size_t>(rec.pitch) * static_cast<size_t>(ch), 16);
-    }
-    if (tiles > hjd_internal::kOrientMaxTiles)
-        return set_error(HJD_E_INVALID, "the crops have %lld tiles of 128 x 128 in all (at most %lld per call)",
-                         static_cast<long long>(tiles), static_cast<long long>(hjd_internal::kOrientMaxTiles));
-    rc = grow_scratch(g, need, "stored crops");
-    if (rc) return rc;
-    std::vector<void*> crops(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
-    OrientStage ostage{orientations, d_outs, pitches, g->out_format};
-    GdecCall c = make_call(datas, sizes, n, stream);
-    c.d_outs = crops.data();
-    c.pitches = crop_pitches.data();
-    c.rois = rois ? stored.data() : nullptr;
-    c.orient = &ostage;
-    return gdec_run(g, c);
-}
-
-// hjd_gdec_decode_resized_filter (orientations null) and
-// hjd_gdec_decode_resized_oriented: decode to the scratch, with orientations
-// orient to a second scratch region, then the resize launches.
-static int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
-                          const int32_t* orientations, const int32_t* flags, void* d_out, int out_w, int out_h,
-                          int32_t out_pitch, int filter, void* stream)
-{
-    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
-    if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
-    // everything that can refuse the call is checked before anything is staged, allocated or enqueued
-    int rc = hjd_internal::resize_filter_check(filter);
-    if (rc) return rc;
-    const bool aa = filter == HJD_RESIZE_TRIANGLE_AA;
-    rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
-    if (rc) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
-        return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
-                         hjd_internal::out_format_row_bytes(g->out_format));
-    if (n > g->st.caps.max_frames)
-        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
-    if (orientations) {
-        bool any = false;
-        rc = orientations_check(orientations, n, &any);
-        if (rc) return rc;
-        if (!any) orientations = nullptr;   // nothing to orient: the plain resized call
-    }
-    // the crops in the scratch: each 16-byte aligned, its pitch rounded up to 4
-    // (whole strips of the pixel kernel keep their vector stores)
-    // (an oriented call's oriented crops follow them under the same rule, and
-    // the antialiased filter's intermediates follow those, each 16-byte aligned too)
-    const size_t un = static_cast<size_t>(n);
-    std::vector<size_t> offs(un), mid_offs(aa ? un : 0), or_offs(orientations ? un : 0);
-    std::vector<int32_t> pitches(un), or_pitches(or_offs.size());
-    std::vector<hjd_rect> stored(orientations && rois ? un : 0);
-    size_t need = 0, mid_need = 0, or_need = 0;
-    int64_t tiles = 0;
-    hjd_internal::ScanHeader h;
-    hjd_internal::DecodeShape shape;
-    shape.scale = g->scale;
-    for (int i = 0; i < n; ++i) {
-        int cw, ch;   // the stored crop
-        if (orientations) {
-            rc = oriented_crop(g, datas[i], sizes[i], i, orientations[i], rois, rois ? &stored[i] : nullptr, &cw, &ch);
-            if (rc) return rc;
-        } else {
-            if (!datas[i]) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
-            rc = hjd_internal::parse_scan_header(datas[i], sizes[i], &h);
-            if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-            if (rois) {   // the rectangle, and the scale against the file's sampling
-                hjd_internal::RoiGeom rg;
-                rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rois[i], &rg);
-                cw = rois[i].w;
-                ch = rois[i].h;
-            } else {
-                shape.sampling = h.sampling;
-                rc = g->scale != 1 ? hjd_internal::shape_check(shape) : HJD_OK;
-                cw = hjd_internal::scaled_dim(h.width, g->scale);
-                ch = hjd_internal::scaled_dim(h.height, g->scale);
-            }
-            if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-            if (cw > hjd_internal::kResizeMaxDim || ch > hjd_internal::kResizeMaxDim)
-                return set_error(HJD_E_INVALID, "frame %d: the crop is %d x %d, the resize takes up to %d", i, cw, ch,
-                                 hjd_internal::kResizeMaxDim);
-        }
-        if (flags && (flags[i] & ~1))
-            return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: horizontal flip)", i,
-                             static_cast<unsigned>(flags[i] & ~1));
-        // what the resize reads: the crop, or its oriented image
-        const bool tr = orientations && hjd_internal::orientation_transposes(orientations[i]);
-        const int rw = tr ? ch : cw, rh = tr ? cw : ch;
-        if (aa) {
-            rc = hjd_internal::resize_aa_ratio_check(rw, rh, out_w, out_h, i);
-            if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-            mid_offs[i] = mid_need;
-            mid_need += hjd_internal::resize_aa_item_bytes(out_w, rh);
-        }
-        pitches[i] = (cw + 3) & ~3;
-        offs[i] = need;
-        need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(ch), 16);
-        if (orientations) {
-            or_pitches[i] = (rw + 3) & ~3;
-            or_offs[i] = or_need;
-            or_need = hjd_internal::align_up(or_need + 3 * static_cast<size_t>(or_pitches[i]) * static_cast<size_t>(rh), 16);
-            tiles += hjd_internal::orient_tiles(cw, ch);
-        }
-    }
-    if (tiles > hjd_internal::kOrientMaxTiles)
-        return set_error(HJD_E_INVALID, "the crops have %lld tiles of 128 x 128 in all (at most %lld per call)",
-                         static_cast<long long>(tiles), static_cast<long long>(hjd_internal::kOrientMaxTiles));
-    const size_t or_base = need;
-    need += or_need;
-    const size_t mid_base = need;
-    need += mid_need;
-    rc = grow_scratch(g, need, aa ? "crops and the resize's intermediate" : "crops");
-    if (rc) return rc;
-    std::vector<void*> crops(un), mids(mid_offs.size()), oriented(or_offs.size());
-    for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
-    for (size_t i = 0; i < mids.size(); ++i) mids[i] = g->d_crops + mid_base + mid_offs[i];
-    for (size_t i = 0; i < oriented.size(); ++i) oriented[i] = g->d_crops + or_base + or_offs[i];
-    ResizeStage stage{d_out, out_w, out_h, out_pitch, flags, aa ? mids.data() : nullptr};
-    OrientStage ostage{orientations, oriented.data(), or_pitches.data(), HJD_OUT_RGB_PLANAR};
-    GdecCall c = make_call(datas, sizes, n, stream);
-    c.d_outs = crops.data();
-    c.pitches = pitches.data();
-    c.rois = orientations && rois ? stored.data() : rois;
-    c.resize = &stage;
-    c.orient = orientations ? &ostage : nullptr;
-    return gdec_run(g, c);
-}
-
-int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
-                                   const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
-                                   int32_t out_pitch, int filter, void* stream)
-{
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, d_out, out_w, out_h, out_pitch, filter, stream);
-}
-
-int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
-                                     const hjd_rect* rois, const int32_t* orientations, const int32_t* flags, void* d_out,
-                                     int out_w, int out_h, int32_t out_pitch, int filter, void* stream)
-{
-    if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, d_out, out_w, out_h, out_pitch, filter, stream);
-}
-
-int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
-                           const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
-                           int out_w, int out_h, int32_t out_pitch, void* stream)
-{
-    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
-    if (!m) return set_error(HJD_E_INVALID, "m is NULL");
-    if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
-    // everything that can refuse the call is checked before anything is staged, allocated or enqueued
-    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
-    if (rc) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
-        return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
-                         hjd_internal::out_format_row_bytes(g->out_format));
-    if (n > g->st.caps.max_frames)
-        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
-    // per frame: the matrix on the stored image, the rectangle it reads (the
-    // crop, in the scratch: 16-byte aligned, its pitch rounded up to 4), the
-    // matrix on that crop
-    const size_t un = static_cast<size_t>(n);
-    std::vector<size_t> offs(un);
-    std::vector<int32_t> pitches(un);
-    std::vector<hjd_rect> rects(un);
-    std::vector<int32_t> mats(6 * un);
-    size_t need = 0;
-    hjd_internal::ScanHeader h;
-    for (int i = 0; i < n; ++i) {
-        if (!datas[i]) return set_error(HJD_E_INVALID, "frame %d: NULL data", i);
-        rc = hjd_internal::parse_scan_header(datas[i], sizes[i], &h);
-        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-        const int sw = hjd_internal::scaled_dim(h.width, g->scale), sh = hjd_internal::scaled_dim(h.height, g->scale);
-        int32_t* mc = &mats[6 * static_cast<size_t>(i)];
-        rc = hjd_internal::warp_orient(m[i], sw, sh, orientations ? orientations[i] : 1, mc);
-        if (!rc) rc = hjd_internal::warp_roi(sw, sh, mc, out_w, out_h, &rects[i]);
-        if (!rc) {   // the rectangle, and the scale against the file's sampling
-            hjd_internal::RoiGeom rg;
-            rc = hjd_internal::roi_geom(h.width, h.height, h.sampling, g->scale, &rects[i], &rg);
-        }
-        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
-        const hjd_rect& r = rects[i];
-        if (r.w > hjd_internal::kResizeMaxDim || r.h > hjd_internal::kResizeMaxDim)
-            return set_error(HJD_E_INVALID, "frame %d: the warp reads a %d x %d crop, it takes up to %d", i, r.w, r.h,
-                             hjd_internal::kResizeMaxDim);
-        const int64_t tx = static_cast<int64_t>(mc[2]) - (static_cast<int64_t>(r.x) << 16);
-        const int64_t ty = static_cast<int64_t>(mc[5]) - (static_cast<int64_t>(r.y) << 16);
-        if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX)
-            return set_error(HJD_E_INVALID, "frame %d: the translation shifted to the crop at (%d, %d) leaves int32", i, r.x,
-                             r.y);
-        mc[2] = static_cast<int32_t>(tx);
-        mc[5] = static_cast<int32_t>(ty);
-        if (flags && (flags[i] & ~HJD_WARP_REPLICATE))
-            return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: HJD_WARP_REPLICATE)", i,
-                             static_cast<unsigned>(flags[i] & ~HJD_WARP_REPLICATE));
-        if (fills && fills[i] > 0xFFFFFFu)
-            return set_error(HJD_E_INVALID, "frame %d: fill 0x%x is above 0xFFFFFF (0x00RRGGBB)", i, fills[i]);
-        pitches[i] = (r.w + 3) & ~3;
-        offs[i] = need;
-        need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(r.h), 16);
-    }
-    rc = grow_scratch(g, need, "crops");
-    if (rc) return rc;
-    std::vector<void*> crops(un);
-    for (int i = 0; i < n; ++i) crops[i] = g->d_crops + offs[i];
-    WarpStage stage{d_out, out_w, out_h, out_pitch, reinterpret_cast<const int32_t(*)[6]>(mats.data()), flags, fills};
-    GdecCall c = make_call(datas, sizes, n, stream);
-    c.d_outs = crops.data();
-    c.pitches = pitches.data();
-    c.rois = rects.data();
-    c.warp = &stage;
-    return gdec_run(g, c);
+    return decode_pixels(g, datas, sizes, n, rois, d_outs, pitches, stream);
 }
 
 int hjd_gdec_decode_coefs(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, int16_t* d_coefs,
@@ -1220,7 +733,7 @@ int hjd_gdec_decode_coefs(hjd_gdec* g, const uint8_t* const* datas, const size_t
 {
     if (!d_coefs || (reinterpret_cast<uintptr_t>(d_coefs) & 15))
         return set_error(HJD_E_INVALID, "d_coefs must be a 16-byte aligned device pointer");
-    GdecCall c = make_call(datas, sizes, n, stream);
+    GdecCall c(datas, sizes, n, stream);
     c.coefs_out = d_coefs;
     c.block_offsets = block_offsets;
     return gdec_run(g, c);

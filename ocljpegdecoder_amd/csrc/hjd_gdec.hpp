@@ -1,6 +1,7 @@
 // hjd_gdec.hpp -- the GPU entropy decoder object (include/hjd_host.h hjd_gdec_*),
-// private to hjd_gdec.hip, which owns it, and hjd_gstream.hip, whose slots
-// stage into it and issue it.
+// private to hjd_gdec.hip, which owns it, hjd_gdec_post.hip, whose calls run
+// stages behind its pixel kernels, and hjd_gstream.hip, whose slots stage into
+// it and issue it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,12 @@
 #include "hjd.h"
 #include "hjd_entropy_prep.hpp"
 #include "hjd_internal.h"
+
+#define HJD_HIP(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
 
 struct hjd_gdec {
     hjd_ctx* ctx = nullptr;
@@ -26,9 +33,9 @@ struct hjd_gdec {
     int16_t* d_coefs = nullptr;
     uint8_t* d_raw = nullptr;           // raw scan bytes of device-destuffed frames (same offsets as the data area)
     uint32_t* d_tiles = nullptr;        // destuff scratch [3][max_tiles]
-    uint8_t* d_crops = nullptr;         // hjd_gdec_decode_resized / _oriented: the decoded crops the resize or orient
-                                        // kernel reads (and, behind them, a resized oriented call's oriented crops
-                                        // and the antialiased filter's intermediate);
+    uint8_t* d_crops = nullptr;         // the scratch of a call with stages (hjd_gdec_post.hip): the crops the pixel
+                                        // kernels write, then what one stage hands the next (oriented crops, the
+                                        // antialiased filter's intermediates);
     size_t crops_bytes = 0;             // grow-only, (re)allocated by a call that needs more, behind the previous call
     bool spec = false;                  // speculative sync (latency decoders: ent_spec/cand/sync_spec kernels)
     hjd::ent::SpecRec* d_spec = nullptr;   // [max_subs][kMaxBpm]
@@ -78,48 +85,48 @@ struct HostCopy {
     int32_t width, height;
 };
 
-// The second stage of hjd_gdec_decode_resized: the call's d_outs are the crops
-// in the decoder's scratch (HJD_OUT_RGB_PLANAR whatever the decoder's format),
-// and one resize launch takes them to `out` in that format.
-struct ResizeStage {
-    void* out;                 // image i at out + i * 3 * out_pitch * out_h
-    int out_w, out_h, out_pitch;
-    const int32_t* flags;      // per image, or null
-    // HJD_RESIZE_TRIANGLE_AA: image i's intermediate (hjd_resize_aa.hpp) at mids[i]
-    // in the scratch, and two launches; null: the bilinear kernel
-    void* const* mids;
+// What follows the pixel kernels of a call (hjd_gdec_post.hip).  Planar images in device memory:
+// image i at ptrs[i], rows pitches[i] apart, dims[i].w x dims[i].h (x, y not read; null where nobody asks).
+struct PostImages {
+    void* const* ptrs;
+    const int32_t* pitches;
+    const hjd_rect* dims;
 };
 
-// The orientation stage of hjd_gdec_decode_oriented / _resized_oriented: the
-// call's d_outs are the stored crops in the decoder's scratch
-// (HJD_OUT_RGB_PLANAR), its rois already the stored rectangles
-// (hjd_orient_roi), and one orient launch behind the pixel kernels takes crop
-// i to outs[i] in out_format: the caller's buffer in the decoder's format, or
-// (a resized call) planar bytes in a second scratch region the resize reads.
-struct OrientStage {
-    const int32_t* orientations;   // per image, 1..8
-    void* const* outs;
-    const int32_t* out_pitches;
-    int out_format;
+// One stage: its kind's launch (resize_aa: its two) over one record per image.  It reads `in` -- the
+// images the pixel kernels wrote (the call's d_outs, HJD_OUT_RGB_PLANAR in the decoder's scratch), or
+// the previous stage's outputs -- and knows no more of what preceded it.
+enum class PostKind { orient, resize, resize_aa, warp };
+struct PostStage {
+    PostKind kind;
+    PostImages in;
+    int out_format;                // the decoder's, or (a stage follows) HJD_OUT_RGB_PLANAR
+    PostImages out;                // orient: image i to out.ptrs[i] at out.pitches[i]
+    struct { void* ptr; int w, h, pitch; } batch;   // resize, warp: image i to ptr + i * 3 * pitch * h
+    const int32_t* orientations;   // orient: per image, 1..8
+    const int32_t* flags;          // resize, warp: per image, or null
+    void* const* mids;             // resize_aa: image i's intermediate (hjd_resize_aa.hpp) in the scratch
+    const int32_t (*mats)[6];      // warp: per image, orientation composed, translation shifted to the crop
+    const uint32_t* fills;         // warp: per image, or null
+    int64_t tiles;                 // orient: the launch's tiles
+    int max_h;                     // resize_aa: the tallest input, which sizes the horizontal launch
+    size_t recs_off, recs_bytes;   // its records in the batch header, from H.recs
 };
 
-// The second stage of hjd_gdec_decode_warped: the call's d_outs are the crops
-// hjd_warp_roi found, in the decoder's scratch (HJD_OUT_RGB_PLANAR), its rois
-// those rectangles, and one warp launch behind the pixel kernels takes crop i
-// through mats[i] -- orientation composed, translation shifted to the crop --
-// to `out` in the decoder's format.
-struct WarpStage {
-    void* out;                     // image i at out + i * 3 * out_pitch * out_h
-    int out_w, out_h, out_pitch;
-    const int32_t (*mats)[6];      // per image
-    const int32_t* flags;          // per image, or null
-    const uint32_t* fills;         // per image, or null
+// The stages of a call in launch order (orient, resize, both, or warp), built once by its entry
+// point.  Their records follow the pixel kernels' tables, each stage's at a 16-byte aligned offset.
+struct PostPlan {
+    int nstages;
+    PostStage stage[2];
+    size_t recs_bytes;             // the tables and every stage's records (Staging::assemble)
 };
 
 // One call of the decoder: everything that belongs to the call and not to
 // the object.  gdec_run reads all of it; gdec_issue (frames already staged in
 // g->st) all but datas, sizes and n.
 struct GdecCall {
+    GdecCall(const uint8_t* const* datas_ = nullptr, const size_t* sizes_ = nullptr, int n_ = 0, void* stream_ = nullptr)
+        : datas(datas_), sizes(sizes_), n(n_), stream(static_cast<hipStream_t>(stream_)) {}
     const uint8_t* const* datas = nullptr;
     const size_t* sizes = nullptr;
     int n = 0;
@@ -130,17 +137,37 @@ struct GdecCall {
     int64_t* block_offsets = nullptr;
     hipStream_t stream = nullptr;
     const HostCopy* host = nullptr;     // per frame, or null
-    const ResizeStage* resize = nullptr;   // hjd_gdec_decode_resized, or null
-    const OrientStage* orient = nullptr;   // hjd_gdec_decode_oriented / _resized_oriented, or null
-    const WarpStage* warp = nullptr;       // hjd_gdec_decode_warped, or null (then neither of the two above)
+    const PostPlan* post = nullptr;     // stages behind the pixel kernels, which then write planar bytes; or null
     // early pull of a latency decoder's lone image (gdec_early_pull)
     hjd_gdec* early_g = nullptr;        // non-null while the call's host destuff may pull
     size_t prepulled = 0;               // data-area bytes of frame 0 already pulled
 };
 
 // Upload the staged frames and run the entropy kernels (+ the pixel kernel
-// when c.d_outs is given) on c.stream.
+// when c.d_outs is given, + the stages of c.post) on c.stream.
 int gdec_issue(hjd_gdec* g, GdecCall& c);
+
+// Stage the call's JPEGs on the calling thread, then issue.
+int gdec_run(hjd_gdec* g, GdecCall& c);
+
+// Per-frame admission, the same for every hjd_gdec_decode* call: parse the file's header, check the
+// rectangle (roi, map's of it, or neither: the whole scaled frame) against the frame, its sampling and
+// the scale, and give the crop the pixel kernels will write -- or a refusal prefixed "frame i:".
+// CropMapFn: a rectangle that depends on the stored frame's size at the decoder's scale, sw x sh.
+typedef int (*CropMapFn)(const void* ctx, int i, int sw, int sh, const hjd_rect* roi, hjd_rect* crop);
+struct Admit {
+    int scale;              // the decoder's
+    bool lenient;           // a file that is null or does not parse passes: staging refuses it in its own words
+    const char* cap_fmt;    // a stage follows: its refusal of a crop above kResizeMaxDim (i, w, h, the cap); or null
+    CropMapFn map;          // or null
+    const void* ctx;
+};
+int admit_frame(const Admit& a, const uint8_t* data, size_t size, int i, const hjd_rect* roi, hjd_rect* crop);
+
+// All gdec_issue asks of a call's stages besides plan.recs_bytes: write every stage's records into the
+// staged header (with each *_item_check), and launch every stage on the stream behind the pixel kernels.
+int post_write_records(hjd_gdec* g, const PostPlan& plan, int n);
+int post_launch(hjd_gdec* g, const PostPlan& plan, int n, hipStream_t stream);
 
 // Destuff mode of a JPEG and, for the device modes, its place in the raw
 // area (PlanFn); with host_fallback, HJD_DESTUFF=auto picks the host path for

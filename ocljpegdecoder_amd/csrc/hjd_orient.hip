@@ -1,6 +1,6 @@
 // hjd_orient.hip -- the orientation object of include/hjd.h (hjd_orient_*), the
 // display-to-stored rectangle mapping (hjd_orient_roi) and the launch of
-// hjd::orient_kernel, which the GPU decoder's oriented decodes (hjd_gdec.hip)
+// hjd::orient_kernel, which the GPU decoder's oriented decodes (hjd_gdec_post.hip)
 // share.  DESIGN.md s3.11.
 #include "hjd_orient.hpp"
 

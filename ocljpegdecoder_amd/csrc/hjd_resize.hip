@@ -1,7 +1,7 @@
 // hjd_resize.hip -- the resize object of include/hjd.h (hjd_resize_*) and the
 // launches of hjd::resize_kernel (bilinear) and of hjd::resize_aa_h_kernel /
 // resize_aa_v_kernel (the antialiased filter), which the GPU decoder's resized
-// decode (hjd_gdec.hip) shares.  DESIGN.md s3.9, s3.10.
+// decode (hjd_gdec_post.hip) shares.  DESIGN.md s3.9, s3.10.
 #include "hjd_resize.hpp"
 #include "hjd_resize_aa.hpp"
 

@@ -1,6 +1,6 @@
 // hjd_warp.hip -- the warp object of include/hjd.h (hjd_warp_*), the host-only
 // geometry that goes with it (hjd_warp_roi, hjd_warp_orient) and the launch of
-// hjd::warp_kernel, which the GPU decoder's warped decode (hjd_gdec.hip)
+// hjd::warp_kernel, which the GPU decoder's warped decode (hjd_gdec_post.hip)
 // shares.  DESIGN.md s3.12.
 #include "hjd_warp.hpp"
 

@@ -352,6 +352,23 @@ class GpuDecoder:
             return [exif_orientation(d) for d in datas]
         return None
 
+    @staticmethod
+    def _rects(rois, n):
+        """The rois of a call as an HjdRect array, or None where it gives none."""
+        if rois is None:
+            return None
+        if len(rois) != n:
+            raise ValueError("one ROI per JPEG")
+        return (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
+
+    def _check_batch_out(self, out, n):
+        """`out` of a resized or warped call: (n, 3, Ho, Wo) in the decoder's planar format."""
+        if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
+            raise ValueError(f"out must be a contiguous device tensor ({n}, 3, Ho, Wo)")
+        elem = {3: 1, 5: 2, 6: 4}.get(self.out_format)   # the planar formats (any other: the library refuses)
+        if elem is not None and out.element_size() != elem:
+            raise ValueError(f"out's dtype {out.dtype} is not the decoder's output format ({self.out_format})")
+
     def decode(self, datas: Sequence[bytes], outs, stream=None, rois=None, apply_exif_orientation: bool = False,
                orientations: Optional[Sequence[int]] = None):
         """outs: contiguous device tensors, one row per image row: (H, W) int32
@@ -376,21 +393,14 @@ class GpuDecoder:
         pitches = (ctypes.c_int32 * n)(*[_out_pitch(o, self.out_format) for o in outs])
         orients = self._orientations(datas, apply_exif_orientation, orientations)
         if orients is not None:
-            rects = None
-            if rois is not None:
-                if len(rois) != n:
-                    raise ValueError("one ROI per JPEG")
-                rects = (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
-            check(self.lib.hjd_gdec_decode_oriented(self.handle, arr_d, arr_s, n, rects, (ctypes.c_int32 * n)(*orients),
-                                                    ptrs, pitches, _stream_handle(stream)), "hjd_gdec_decode_oriented")
+            check(self.lib.hjd_gdec_decode_oriented(self.handle, arr_d, arr_s, n, self._rects(rois, n),
+                                                    (ctypes.c_int32 * n)(*orients), ptrs, pitches,
+                                                    _stream_handle(stream)), "hjd_gdec_decode_oriented")
         elif rois is None:
             check(self.lib.hjd_gdec_decode(self.handle, arr_d, arr_s, n, ptrs, pitches, _stream_handle(stream)),
                   "hjd_gdec_decode")
         else:
-            if len(rois) != n:
-                raise ValueError("one ROI per JPEG")
-            rects = (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
-            check(self.lib.hjd_gdec_decode_roi(self.handle, arr_d, arr_s, n, rects, ptrs, pitches,
+            check(self.lib.hjd_gdec_decode_roi(self.handle, arr_d, arr_s, n, self._rects(rois, n), ptrs, pitches,
                                                _stream_handle(stream)), "hjd_gdec_decode_roi")
         self._n = n
 
@@ -411,16 +421,8 @@ class GpuDecoder:
         (hjd_gdec_decode_resized_oriented), rois and flips applying to it."""
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
-        if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
-            raise ValueError(f"out must be a contiguous device tensor ({n}, 3, Ho, Wo)")
-        elem = {3: 1, 5: 2, 6: 4}.get(self.out_format)   # the planar formats (any other: the library refuses)
-        if elem is not None and out.element_size() != elem:
-            raise ValueError(f"out's dtype {out.dtype} is not the decoder's output format ({self.out_format})")
-        rects = fl = None
-        if rois is not None:
-            if len(rois) != n:
-                raise ValueError("one ROI per JPEG")
-            rects = (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
+        self._check_batch_out(out, n)
+        rects, fl = self._rects(rois, n), None
         if flips is not None:
             if len(flips) != n:
                 raise ValueError("one flip flag per JPEG")
@@ -614,11 +616,7 @@ class GpuDecoder:
         from .backend import _warp_flags, _xform
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
-        if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
-            raise ValueError(f"out must be a contiguous device tensor ({n}, 3, Ho, Wo)")
-        elem = {3: 1, 5: 2, 6: 4}.get(self.out_format)   # the planar formats (any other: the library refuses)
-        if elem is not None and out.element_size() != elem:
-            raise ValueError(f"out's dtype {out.dtype} is not the decoder's output format ({self.out_format})")
+        self._check_batch_out(out, n)
         if len(xforms) != n:
             raise ValueError("one matrix per JPEG")
         mats = ((ctypes.c_int32 * 6) * n)(*[(ctypes.c_int32 * 6)(*_xform(x)) for x in xforms])

@@ -27,12 +27,18 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("HJD_ARCH", "gfx950")
 
 HIP_SOURCES = ["hjd_runtime.hip", "idct_compat.hip", "stream_pipeline.hip", "hjd_entropy.hip", "hjd_gdec.hip",
-               "hjd_gstream.hip", "numa_affinity.hip", "hjd_probe.hip", "hjd_resize.hip", "hjd_orient.hip",
-               "hjd_warp.hip"]
+               "hjd_gdec_post.hip", "hjd_gstream.hip", "numa_affinity.hip", "hjd_probe.hip", "hjd_resize.hip",
+               "hjd_orient.hip", "hjd_warp.hip"]
 # no __global__ function and no HIP call: plain C++
 CXX_SOURCES = ["jpeg_host.cpp", "hjd_entropy_prep.cpp", "hjd_entropy_emulate.cpp"]
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}"]
+# The host staging loops (hjd_entropy_prep.cpp's destuff) ran 11 % slower at three of the four
+# 16-byte positions their unit can take in the library, and every change in the size of a unit
+# linked before it moves it: 17.4 ms against 19.2-19.4 to stage 256 FHD files, the same objects
+# shifted by 16, 32 and 48 bytes (profiles/README.md, "Decoder post-stages: one plan").  Loops
+# aligned to 64 bytes do not depend on where the unit lands.
+HOST_CXXFLAGS = ["-falign-loops=64"]
 
 
 def _run(cmd):
@@ -88,7 +94,7 @@ def build(verbose: bool = False, force: bool = False, variant: str = "",
         if force or _needs(o, [s] + headers):
             # host-only C++ (no device code): compiled by hipcc's clang as plain C++
             extra = os.environ.get("HJD_HOST_CXXFLAGS", "").split()   # tuning A/Bs of the host decoder
-            jobs.append([HIPCC, *COMMON, *extra, "-x", "c++", "-pthread", "-c", s, "-o", o])
+            jobs.append([HIPCC, *COMMON, *HOST_CXXFLAGS, *extra, "-x", "c++", "-pthread", "-c", s, "-o", o])
     t0 = time.time()
     if force:   # a forced build starts from an empty object directory
         for f in os.listdir(OBJDIR):
