@@ -416,7 +416,82 @@ def resize_scale(src_w: int, src_h: int, out_w: int, out_h: int) -> int:
     return 1
 
 
-class Resize:
+def _planes(s, i, what, uint8=False):
+    """(tensor, pitch in bytes) of a (3, h, w) tensor or a (tensor, pitch) pair."""
+    t, p = s if isinstance(s, (tuple, list)) else (s, None)
+    if not (t.is_cuda and t.ndim == 3 and t.shape[0] == 3 and (not uint8 or t.element_size() == 1)):
+        raise ValueError(f"{what} {i} must be a (3, h, w) {'uint8 ' if uint8 else ''}device tensor")
+    if p is None:   # contiguous, or a [..., :w] view of wider rows
+        row = t.stride(1)
+        if t.stride(2) != 1 or row < t.shape[2] or t.stride(0) != t.shape[1] * row:
+            raise ValueError(f"{what} {i} must be contiguous, a [..., :w] view of wider rows, or come with its pitch")
+        p = row * t.element_size()
+    return t, p
+
+
+def _source(s, i):
+    """_planes of a source of Orient or Warp: uint8."""
+    t, p = _planes(s, i, "source")
+    if t.element_size() != 1:
+        raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
+    return t, p
+
+
+def _batch_out(out, n):
+    """(out_format, Wo, Ho, pitch in bytes) of the (N, 3, Ho, Wo) output of n sources (Resize, Warp)."""
+    if not (out.is_cuda and out.ndim == 4 and out.shape[1] == 3 and str(out.dtype) in _DTYPE_FORMATS):
+        raise ValueError("out must be a uint8 / float16 / float32 device tensor (N, 3, Ho, Wo)")
+    ho, wo = int(out.shape[2]), int(out.shape[3])
+    row = out.stride(2)   # elements between rows: Wo, or more for a [..., :Wo] view of wider rows
+    if out.stride(3) != 1 or row < wo or out.stride(1) != ho * row or (n > 1 and out.stride(0) != 3 * ho * row):
+        raise ValueError("out must be contiguous, or a [..., :Wo] view of a contiguous (N, 3, Ho, P) tensor")
+    if out.shape[0] != n:
+        raise ValueError(f"out holds {out.shape[0]} images, {n} sources given")
+    return _DTYPE_FORMATS[str(out.dtype)], wo, ho, row * out.element_size()
+
+
+class _Stage:
+    """The handle of an hjd_resize / hjd_orient / hjd_warp object and the calls
+    every kind has; _prefix is the kind's C prefix."""
+    _prefix = ""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.handle = None
+        self._keep = []
+
+    def _call(self, name, *args):
+        check(getattr(self.lib, f"{self._prefix}_{name}")(*args), f"{self._prefix}_{name}")
+
+    def _create(self, name, normalize, *args):
+        h = ctypes.c_void_p()
+        self._call(name, self.ctx.handle, *args, ctypes.byref(h))
+        self.handle = h
+        if normalize is not None:
+            self.set_normalize(*normalize)
+
+    def set_normalize(self, a, b):
+        """hjd_<kind>_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
+        self._call("set_normalize", self.handle, *_norm_arrays((a, b)))
+
+    def launch(self, stream=None):
+        """Enqueue the object's kernels (asynchronous)."""
+        self._call("launch", self.handle, _stream_ptr(stream))
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, f"{self._prefix}_destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resize(_Stage):
     """hjd_resize: N planar uint8 RGB images of different sizes -> one
     (N, 3, Ho, Wo) batch in one launch (include/hjd.h: bilinear, half-pixel
     centres, 11-bit integer weights, no antialiasing; sizes 1..16384).
@@ -425,6 +500,7 @@ class Resize:
     launches through an intermediate the object owns, so the launches of one
     object must be ordered, e.g. on one stream; a source dimension d going to
     o needs d * d <= 2**21 * o)."""
+    _prefix = "hjd_resize"
 
     def __init__(self, ctx: Context, srcs, out, flips=None, normalize=None, antialias=False):
         """srcs: N device tensors (3, h, w) uint8 (contiguous, or a [..., :w]
@@ -435,70 +511,26 @@ class Resize:
         values, image i mirrored horizontally where set.  normalize = (a, b):
         the float dtypes' constants (set_normalize; default a = 1, b = 0).
         antialias: the filter, RESIZE_TRIANGLE_AA if true."""
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self.handle = None
+        super().__init__(ctx)
         n = len(srcs)
-        if not (out.is_cuda and out.ndim == 4 and out.shape[1] == 3 and str(out.dtype) in _DTYPE_FORMATS):
-            raise ValueError("out must be a uint8 / float16 / float32 device tensor (N, 3, Ho, Wo)")
-        ho, wo = int(out.shape[2]), int(out.shape[3])
-        row = out.stride(2)   # elements between rows: Wo, or more for a [..., :Wo] view of wider rows
-        if out.stride(3) != 1 or row < wo or out.stride(1) != ho * row or (n > 1 and out.stride(0) != 3 * ho * row):
-            raise ValueError("out must be contiguous, or a [..., :Wo] view of a contiguous (N, 3, Ho, P) tensor")
-        if out.shape[0] != n:
-            raise ValueError(f"out holds {out.shape[0]} images, {n} sources given")
+        self.out_format, wo, ho, pitch = _batch_out(out, n)
         if flips is not None and len(flips) != n:
             raise ValueError("one flip flag per source")
-        self.out_format = _DTYPE_FORMATS[str(out.dtype)]
-        pitch = row * out.element_size()
         items = (_lib.HjdResizeItem * max(1, n))()
-        self._keep = []
         for i, s in enumerate(srcs):
-            t, sp = s if isinstance(s, (tuple, list)) else (s, None)
-            if not (t.is_cuda and t.element_size() == 1 and t.ndim == 3 and t.shape[0] == 3):
-                raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
-            if sp is None:   # contiguous, or a [..., :w] view of wider rows
-                sp = t.stride(1)
-                if t.stride(2) != 1 or sp < t.shape[2] or t.stride(0) != t.shape[1] * sp:
-                    raise ValueError(f"source {i} must be contiguous, a [..., :w] view of wider rows, or come with "
-                                     "its pitch")
+            t, sp = _planes(s, i, "source", uint8=True)
             self._keep.append(t)
             items[i] = _lib.HjdResizeItem(t.data_ptr(), out[i].data_ptr(), int(t.shape[2]), int(t.shape[1]), int(sp),
                                           RESIZE_FLIP_H if flips is not None and flips[i] else 0)
         self.out = out
-        h = ctypes.c_void_p()
         self.filter = RESIZE_TRIANGLE_AA if antialias else RESIZE_BILINEAR
-        check(self.lib.hjd_resize_create_filter(ctx.handle, items, n, wo, ho, pitch, self.out_format, self.filter,
-                                                ctypes.byref(h)), "hjd_resize_create_filter")
-        self.handle = h
-        if normalize is not None:
-            self.set_normalize(*normalize)
-
-    def set_normalize(self, a, b):
-        """hjd_resize_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
-        ca, cb = _norm_arrays((a, b))
-        check(self.lib.hjd_resize_set_normalize(self.handle, ca, cb), "hjd_resize_set_normalize")
-
-    def launch(self, stream=None):
-        """Enqueue the resize kernel (asynchronous)."""
-        check(self.lib.hjd_resize_launch(self.handle, _stream_ptr(stream)), "hjd_resize_launch")
+        self._create("create_filter", normalize, items, n, wo, ho, pitch, self.out_format, self.filter)
 
     def launch_pass(self, which: int, stream=None):
         """Timing only (hjd_debug_resize_launch_pass): one launch of an
         antialias=True object, 0 the horizontal kernel, 1 the vertical one."""
         check(self.lib.hjd_debug_resize_launch_pass(self.handle, int(which), _stream_ptr(stream)),
               "hjd_debug_resize_launch_pass")
-
-    def close(self):
-        if self.handle:
-            self.lib.hjd_resize_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def oriented_size(width: int, height: int, orientation: int):
@@ -521,11 +553,12 @@ def oriented_roi(width: int, height: int, orientation: int, roi):
     return (s.x, s.y, s.w, s.h)
 
 
-class Orient:
+class Orient(_Stage):
     """hjd_orient: N planar uint8 RGB images of different sizes, each permuted
     by its EXIF orientation (1..8; include/hjd.h has the table) into its own
     output, in one launch.  A pure permutation of bytes; the float dtypes are
     fma(float(u8), a, b) of the permuted bytes."""
+    _prefix = "hjd_orient"
 
     def __init__(self, ctx: Context, srcs, outs, orientations, normalize=None):
         """srcs: N device tensors (3, h, w) uint8 (contiguous, or a [..., :w]
@@ -535,20 +568,15 @@ class Orient:
         contiguous or a [..., :W] view of wider rows, or (tensor, pitch)
         pairs: 3 * H rows of `pitch` bytes from the tensor's data_ptr.
         normalize = (a, b): the float dtypes' constants."""
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self.handle = None
+        super().__init__(ctx)
         n = len(srcs)
         if len(outs) != n or len(orientations) != n:
             raise ValueError("one output and one orientation per source")
         items = (_lib.HjdOrientItem * max(1, n))()
-        self._keep = []
         fmt = None
         for i, (s, d) in enumerate(zip(srcs, outs)):
-            t, sp = self._planes(s, i, "source")
-            if t.element_size() != 1:
-                raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
-            u, dp = self._planes(d, i, "output")
+            t, sp = _source(s, i)
+            u, dp = _planes(d, i, "output")
             if str(u.dtype) not in _DTYPE_FORMATS or (fmt is not None and _DTYPE_FORMATS[str(u.dtype)] != fmt):
                 raise ValueError("outputs must be uint8 / float16 / float32 device tensors of one dtype")
             fmt = _DTYPE_FORMATS[str(u.dtype)]
@@ -560,44 +588,7 @@ class Orient:
             self._keep += [t, u]
             items[i] = _lib.HjdOrientItem(t.data_ptr(), u.data_ptr(), w, h, int(sp), int(orientations[i]), int(dp), 0)
         self.out_format = fmt if fmt is not None else OUT_RGB_PLANAR
-        h = ctypes.c_void_p()
-        check(self.lib.hjd_orient_create(ctx.handle, items, n, self.out_format, ctypes.byref(h)), "hjd_orient_create")
-        self.handle = h
-        if normalize is not None:
-            self.set_normalize(*normalize)
-
-    @staticmethod
-    def _planes(s, i, what):
-        """(tensor, pitch in bytes) of a (3, h, w) tensor or a (tensor, pitch) pair."""
-        t, p = s if isinstance(s, (tuple, list)) else (s, None)
-        if not (t.is_cuda and t.ndim == 3 and t.shape[0] == 3):
-            raise ValueError(f"{what} {i} must be a (3, h, w) device tensor")
-        if p is None:   # contiguous, or a [..., :w] view of wider rows
-            row = t.stride(1)
-            if t.stride(2) != 1 or row < t.shape[2] or t.stride(0) != t.shape[1] * row:
-                raise ValueError(f"{what} {i} must be contiguous, a [..., :w] view of wider rows, or come with its pitch")
-            p = row * t.element_size()
-        return t, p
-
-    def set_normalize(self, a, b):
-        """hjd_orient_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
-        ca, cb = _norm_arrays((a, b))
-        check(self.lib.hjd_orient_set_normalize(self.handle, ca, cb), "hjd_orient_set_normalize")
-
-    def launch(self, stream=None):
-        """Enqueue the orientation kernel (asynchronous)."""
-        check(self.lib.hjd_orient_launch(self.handle, _stream_ptr(stream)), "hjd_orient_launch")
-
-    def close(self):
-        if self.handle:
-            self.lib.hjd_orient_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("create", normalize, items, n, self.out_format)
 
 
 WARP_REPLICATE = 1   # hjd_warp_item.flags bit 0
@@ -685,79 +676,42 @@ def warp_orient(xform, stored_w: int, stored_h: int, orientation: int):
     return list(out)
 
 
-class Warp:
+class Warp(_Stage):
     """hjd_warp: N planar uint8 RGB images of different sizes, each sampled
     through its own affine map (six Q16 integers, warp_xform() makes them)
     into one (N, 3, Ho, Wo) batch in one launch (include/hjd.h: bilinear,
     11-bit integer weights, one rounding, no antialiasing).  Taps outside an
     image are its fill colour, or with replicate its nearest pixel."""
+    _prefix = "hjd_warp"
 
     def __init__(self, ctx: Context, srcs, out, xforms, fills=None, replicate=False, normalize=None):
         """srcs and out as Resize takes them.  xforms: N sequences of six
         ints.  fills: N colours 0xRRGGBB (default 0); replicate: one truthy
         value for all images or N of them (WARP_REPLICATE).  normalize =
         (a, b): the float dtypes' constants."""
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self.handle = None
+        super().__init__(ctx)
         n = len(srcs)
-        if not (out.is_cuda and out.ndim == 4 and out.shape[1] == 3 and str(out.dtype) in _DTYPE_FORMATS):
-            raise ValueError("out must be a uint8 / float16 / float32 device tensor (N, 3, Ho, Wo)")
-        ho, wo = int(out.shape[2]), int(out.shape[3])
-        row = out.stride(2)   # elements between rows: Wo, or more for a [..., :Wo] view of wider rows
-        if out.stride(3) != 1 or row < wo or out.stride(1) != ho * row or (n > 1 and out.stride(0) != 3 * ho * row):
-            raise ValueError("out must be contiguous, or a [..., :Wo] view of a contiguous (N, 3, Ho, P) tensor")
-        if out.shape[0] != n:
-            raise ValueError(f"out holds {out.shape[0]} images, {n} sources given")
+        self.out_format, wo, ho, pitch = _batch_out(out, n)
         if len(xforms) != n:
             raise ValueError("one matrix per source")
         if fills is not None and len(fills) != n:
             raise ValueError("one fill colour per source")
         flags = _warp_flags(replicate, n)
-        self.out_format = _DTYPE_FORMATS[str(out.dtype)]
         items = (_lib.HjdWarpItem * max(1, n))()
-        self._keep = []
         for i, s in enumerate(srcs):
-            t, sp = Orient._planes(s, i, "source")
-            if t.element_size() != 1:
-                raise ValueError(f"source {i} must be a (3, h, w) uint8 device tensor")
+            t, sp = _source(s, i)
             self._keep.append(t)
             items[i] = _lib.HjdWarpItem(t.data_ptr(), out[i].data_ptr(), int(t.shape[2]), int(t.shape[1]), int(sp),
                                         flags[i], (ctypes.c_int32 * 6)(*_xform(xforms[i])),
                                         int(fills[i]) if fills is not None else 0, 0)
         self.out = out
-        h = ctypes.c_void_p()
-        check(self.lib.hjd_warp_create(ctx.handle, items, n, wo, ho, row * out.element_size(), self.out_format,
-                                       ctypes.byref(h)), "hjd_warp_create")
-        self.handle = h
-        if normalize is not None:
-            self.set_normalize(*normalize)
-
-    def set_normalize(self, a, b):
-        """hjd_warp_set_normalize: out = fma(float(u8), a, b) for the launches that follow."""
-        ca, cb = _norm_arrays((a, b))
-        check(self.lib.hjd_warp_set_normalize(self.handle, ca, cb), "hjd_warp_set_normalize")
-
-    def launch(self, stream=None):
-        """Enqueue the warp kernel (asynchronous)."""
-        check(self.lib.hjd_warp_launch(self.handle, _stream_ptr(stream)), "hjd_warp_launch")
+        self._create("create", normalize, items, n, wo, ho, pitch, self.out_format)
 
     def launch_form(self, tiled: bool, stream=None):
         """Timing only (hjd_debug_warp_launch_form): the same launch with the
         output dealt to the waves row-major (False) or in 8 x 8-quad tiles (True)."""
         check(self.lib.hjd_debug_warp_launch_form(self.handle, 1 if tiled else 0, _stream_ptr(stream)),
               "hjd_debug_warp_launch_form")
-
-    def close(self):
-        if self.handle:
-            self.lib.hjd_warp_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _warp_flags(replicate, n):

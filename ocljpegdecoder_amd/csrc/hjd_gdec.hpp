@@ -10,12 +10,7 @@
 #include "hjd.h"
 #include "hjd_entropy_prep.hpp"
 #include "hjd_internal.h"
-
-#define HJD_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#include "hjd_post.hpp"   // HJD_HIP
 
 struct hjd_gdec {
     hjd_ctx* ctx = nullptr;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "hjd.h"
+#include "hjd_records.h"
 
 struct hjd_jpeg_info;
 
@@ -188,13 +189,13 @@ inline bool out_vector_ok(int out_format, int64_t pitch, int64_t out_base, uintp
     return (bits & out_format_row(out_format).vector_mask) == 0;
 }
 
-// The constants of the float formats as the kernels read them (layout of
-// hjd::NormDev): the record follows the frame table (and a ROI plan's
-// RoiRecord table).
-struct NormRecord {
-    float a[3], b[3];
-    float reserved[2];
-};
+// The records the host writes as the kernels read them (hjd_records.h): the
+// float formats' constants, which follow the frame table (and a ROI plan's
+// RoiRecord table), and one image of each stage kernel.
+using NormRecord = hjd::NormDev;
+using ResizeRecord = hjd::ResizeDev;   // (the layout of hjd_resize_item, too)
+using OrientRecord = hjd::OrientDev;   // (of hjd_orient_item, whose reserved word is tile_begin here)
+using WarpRecord = hjd::WarpDev;       // (of hjd_warp_item)
 // a = 1, b = 0: the C default (out = (float)u8).
 inline NormRecord norm_identity() { return NormRecord{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}}; }
 // HJD_OK, or HJD_E_INVALID (NULL or non-finite constants) with the cause in the error string.
@@ -215,14 +216,7 @@ inline FrameTable frame_table(int nframes, bool roi, bool norm)
     return t;
 }
 
-// The resize kernel (hjd_resize.hip; include/hjd.h hjd_resize_*).  One image's
-// record as the kernel reads it (layout of hjd::ResizeDev and of
-// hjd_resize_item): planar uint8 source w x h at `pitch`, destination plane R.
-struct ResizeRecord {
-    const void* src;
-    void* dst;
-    int32_t w, h, pitch, flags;
-};
+// The resize kernel (hjd_resize.hip; include/hjd.h hjd_resize_*).
 constexpr int kResizeMaxDim = 16384;      // source and output dimensions: 1..16384 (32-bit arithmetic)
 constexpr int kResizeMaxItems = 1 << 20;  // images per launch
 // HJD_OK, or HJD_E_INVALID with the cause in the error string: the output's
@@ -256,15 +250,7 @@ int resize_aa_ratio_check(int src_w, int src_h, int out_w, int out_h, int index)
 int launch_resize_aa(int device, const ResizeRecord* d_h, const ResizeRecord* d_v, int n, int max_src_h, int out_w,
                      int out_h, int out_pitch, int out_format, const NormRecord& norm, void* stream, int passes = 3);
 
-// The orientation kernel (hjd_orient.hip; include/hjd.h hjd_orient_*).  One
-// image's record as the kernel reads it (layout of hjd::OrientDev and of
-// hjd_orient_item, whose reserved word is tile_begin here).
-struct OrientRecord {
-    const void* src;
-    void* dst;
-    int32_t w, h, pitch, orientation, dst_pitch;
-    uint32_t tile_begin;
-};
+// The orientation kernel (hjd_orient.hip; include/hjd.h hjd_orient_*).
 constexpr int64_t kOrientMaxTiles = INT32_MAX;   // tiles per launch (the grid)
 inline bool orientation_ok(int o) { return o >= 1 && o <= 8; }
 inline bool orientation_transposes(int o) { return o >= 5; }
@@ -282,17 +268,7 @@ int orient_roi(int width, int height, int orientation, const ::hjd_rect& display
 int launch_orient(int device, const OrientRecord* d_items, int n, int64_t tiles, int out_format, const NormRecord& norm,
                   void* stream);
 
-// The affine warp kernel (hjd_warp.hip; include/hjd.h hjd_warp_*).  One
-// image's record as the kernel reads it (layout of hjd::WarpDev and of
-// hjd_warp_item).
-struct WarpRecord {
-    const void* src;
-    void* dst;
-    int32_t w, h, pitch, flags;
-    int32_t m[6];
-    uint32_t fill;
-    int32_t reserved;
-};
+// The affine warp kernel (hjd_warp.hip; include/hjd.h hjd_warp_*).
 // HJD_OK, or HJD_E_INVALID with the cause in the error string: one item's side
 // of hjd_warp_check (the output's side is resize_out_check).
 int warp_item_check(const WarpRecord& it, int index, int out_format);

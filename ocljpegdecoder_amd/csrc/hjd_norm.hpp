@@ -1,21 +1,15 @@
 // hjd_norm.hpp -- the arithmetic of the normalised float output formats
 // (HJD_OUT_RGB_PLANAR_F16 / _F32), shared by the fused pixel
-// kernels (hjd_kernels.hpp) and the resize kernel (hjd_resize.hpp): one
+// kernels (hjd_kernels.hpp) and the stage kernels (hjd_store.hpp): one
 // definition of out = fma((float)u8, a[c], b[c]) and of its rounding to half.
+// The constants' record, NormDev, is in hjd_records.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace hjd {
+#include "hjd_records.h"
 
-// The plan-level constants of the float formats, per channel R, G, B: the
-// 32-byte record that follows the frame table (and the RoiDev table of a ROI
-// plan).  Only the float instantiations read it.
-struct NormDev {
-    float a[3], b[3];
-    float reserved[2];   // 0
-};
-static_assert(sizeof(NormDev) == 32, "NormDev layout");
+namespace hjd {
 
 // Channel c (0 R, 1 G, 2 B) of BGRX word p as the normalised fp32 value: the
 // byte is converted in place (v_cvt_f32_ubyte2/1/0), then one fused

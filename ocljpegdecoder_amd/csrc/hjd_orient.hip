@@ -6,40 +6,24 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "hjd.h"
-#include "hjd_internal.h"
+#include "hjd_post.hpp"
 
 using hjd_internal::set_error;
-
-#define HJD_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 static_assert(sizeof(hjd_orient_item) == sizeof(hjd::OrientDev) && offsetof(hjd_orient_item, dst) == 8 &&
                   offsetof(hjd_orient_item, src_w) == 16 && offsetof(hjd_orient_item, orientation) == 28 &&
                   offsetof(hjd_orient_item, dst_pitch) == 32 && offsetof(hjd_orient_item, reserved) == 36,
               "hjd_orient_item is the kernel's record");
-static_assert(sizeof(hjd_internal::OrientRecord) == sizeof(hjd::OrientDev) &&
-                  offsetof(hjd_internal::OrientRecord, tile_begin) == offsetof(hjd::OrientDev, tile_begin),
-              "OrientRecord is the kernel's record");
 static_assert(hjd::kOrientTile == 128, "orient_tiles counts 128 x 128 tiles");
 
-struct hjd_orient {
-    int device = 0;
-    int n = 0, out_format = 0;
+struct hjd_orient : hjd_internal::StageTable<hjd::OrientDev> {
+    using StageTable::StageTable;
     int64_t tiles = 0;
-    hjd::OrientDev* d_items = nullptr;
-    hjd_internal::NormRecord norm = hjd_internal::norm_identity();
 };
 
 namespace {
-
-inline bool dim_ok(int d) { return d >= 1 && d <= hjd_internal::kResizeMaxDim; }
 
 // An address range of one item: its source (dst false) or its output.
 struct Span {
@@ -62,19 +46,11 @@ int hjd_internal::orient_out_check(int n, int out_format)
 
 int hjd_internal::orient_item_check(const OrientRecord& it, int index, int out_format)
 {
-    if (!it.src || !it.dst) return set_error(HJD_E_INVALID, "orient item %d: src or dst is NULL", index);
-    const int elem = out_format_row_bytes(out_format);
-    if (reinterpret_cast<uintptr_t>(it.dst) & out_format_align_mask(out_format))
-        return set_error(HJD_E_INVALID, "orient item %d: dst must be a multiple of the element size (%d bytes)", index,
-                         elem);
-    if (!dim_ok(it.w) || !dim_ok(it.h))
-        return set_error(HJD_E_INVALID, "orient item %d: source size %d x %d is outside 1..%d", index, it.w, it.h,
-                         kResizeMaxDim);
-    if (it.pitch < it.w)
-        return set_error(HJD_E_INVALID, "orient item %d: src_pitch %d is below src_w %d", index, it.pitch, it.w);
+    const int rc = item_common_check("orient", it, index, out_format);
+    if (rc) return rc;
     if (!orientation_ok(it.orientation))
         return set_error(HJD_E_INVALID, "orient item %d: orientation %d is outside 1..8", index, it.orientation);
-    const int out_w = orientation_transposes(it.orientation) ? it.h : it.w;
+    const int out_w = orientation_transposes(it.orientation) ? it.h : it.w, elem = out_format_row_bytes(out_format);
     if (it.dst_pitch < elem * out_w || (it.dst_pitch & out_format_pitch_mask(out_format)))
         return set_error(HJD_E_INVALID,
                          "orient item %d: dst_pitch %d must be >= %d (%d bytes x the oriented width %d) and a multiple of %d",
@@ -113,27 +89,14 @@ int hjd_internal::launch_orient(int device, const OrientRecord* d_items, int n, 
     if (tiles < 1 || tiles > kOrientMaxTiles)
         return set_error(HJD_E_INVALID, "orient: %lld tiles in one launch (at most %lld)", static_cast<long long>(tiles),
                          static_cast<long long>(kOrientMaxTiles));
-    HJD_HIP(hipSetDevice(device));
-    hjd::NormDev nk;
-    memcpy(&nk, &norm, sizeof(nk));
-    const dim3 grid(static_cast<uint32_t>(tiles)), block(hjd::kOrientThreads);
-    const hjd::OrientDev* items = reinterpret_cast<const hjd::OrientDev*>(d_items);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (out_format) {
-    case HJD_OUT_RGB_PLANAR:
-        hipLaunchKernelGGL(hjd::orient_kernel<0>, grid, block, 0, s, items, n, nk);
-        break;
-    case HJD_OUT_RGB_PLANAR_F16:
-        hipLaunchKernelGGL(hjd::orient_kernel<hjd::kOrientOutF16>, grid, block, 0, s, items, n, nk);
-        break;
-    case HJD_OUT_RGB_PLANAR_F32:
-        hipLaunchKernelGGL(hjd::orient_kernel<hjd::kOrientOutF32>, grid, block, 0, s, items, n, nk);
-        break;
-    default:
-        return set_error(HJD_E_INVALID, "orient: output format %d has no kernel", out_format);   // (no fallback)
-    }
-    HJD_HIP(hipGetLastError());
-    return HJD_OK;
+    return with_out_format("orient", out_format, [&](auto format) -> int {
+        HJD_HIP(hipSetDevice(device));
+        const dim3 grid(static_cast<uint32_t>(tiles)), block(hjd::kOrientThreads);
+        hipLaunchKernelGGL(hjd::orient_kernel<decltype(format)::value>, grid, block, 0, static_cast<hipStream_t>(stream),
+                           d_items, n, norm);
+        HJD_HIP(hipGetLastError());
+        return HJD_OK;
+    });
 }
 
 extern "C" {
@@ -198,28 +161,20 @@ int hjd_orient_create(hjd_ctx* ctx, const hjd_orient_item* items, int n, int out
 {
     if (!ctx || !out) return set_error(HJD_E_INVALID, "orient: ctx or out is NULL");
     *out = nullptr;
-    const int rc = hjd_orient_check(items, n, out_format);
+    int rc = hjd_orient_check(items, n, out_format);
     if (rc) return rc;
-    hjd_orient* r = new (std::nothrow) hjd_orient;
+    hjd_orient* r = new (std::nothrow) hjd_orient(ctx, n, out_format);
     if (!r) return set_error(HJD_E_NOMEM, "orient allocation");
-    r->device = hjd_ctx_device(ctx);
-    r->n = n;
-    r->out_format = out_format;
     std::vector<hjd::OrientDev> table(static_cast<size_t>(n));
     memcpy(table.data(), items, sizeof(hjd::OrientDev) * static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
         table[i].tile_begin = static_cast<uint32_t>(r->tiles);
         r->tiles += hjd_internal::orient_tiles(table[i].w, table[i].h);
     }
-    const size_t bytes = sizeof(hjd::OrientDev) * table.size();
-    hipError_t e = hipSetDevice(r->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_items), bytes);
-    if (e == hipSuccess) e = hipMemcpy(r->d_items, table.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        hjd_orient_destroy(r);
-        return set_error(e == hipErrorOutOfMemory ? HJD_E_NOMEM : HJD_E_HIP, "orient table upload (%zu bytes): %s", bytes,
-                         hipGetErrorString(e));
+    rc = r->upload("orient", table.data(), table.size());
+    if (rc) {
+        delete r;
+        return rc;
     }
     *out = r;
     return HJD_OK;
@@ -227,34 +182,18 @@ int hjd_orient_create(hjd_ctx* ctx, const hjd_orient_item* items, int n, int out
 
 int hjd_orient_set_normalize(hjd_orient* r, const float a[3], const float b[3])
 {
-    const int rc = hjd_internal::norm_check(a, b);
-    if (rc) return rc;
-    if (!r) return set_error(HJD_E_INVALID, "orient is NULL");
-    if (!hjd_internal::out_format_float_bytes(r->out_format))
-        return set_error(HJD_E_INVALID, "hjd_orient_set_normalize: output format %d is not HJD_OUT_RGB_PLANAR_F16 / _F32",
-                         r->out_format);
-    for (int c = 0; c < 3; ++c) {   // a launch argument: an enqueued launch keeps its own
-        r->norm.a[c] = a[c];
-        r->norm.b[c] = b[c];
-    }
-    return HJD_OK;
+    return hjd_internal::table_set_normalize("orient", r, a, b);
 }
 
 int hjd_orient_launch(hjd_orient* r, void* stream)
 {
     if (!r) return set_error(HJD_E_INVALID, "orient is NULL");
-    return hjd_internal::launch_orient(r->device, reinterpret_cast<const hjd_internal::OrientRecord*>(r->d_items), r->n,
-                                       r->tiles, r->out_format, r->norm, stream);
+    return hjd_internal::launch_orient(r->device, r->d_items, r->n, r->tiles, r->out_format, r->norm, stream);
 }
 
 int hjd_orient_destroy(hjd_orient* r)
 {
-    if (!r) return HJD_OK;
-    if (r->d_items) {
-        (void)hipSetDevice(r->device);
-        (void)hipFree(r->d_items);   // (waits for the launches that read the table)
-    }
-    delete r;
+    delete r;   // (its destructor frees the table)
     return HJD_OK;
 }
 

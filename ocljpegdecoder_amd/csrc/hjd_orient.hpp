@@ -33,27 +33,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hjd_norm.hpp"
+#include "hjd_store.hpp"
 
 namespace hjd {
 
 constexpr int kOrientThreads = 256;
 constexpr int kOrientTile = 128;       // bytes per tile edge: one cache line
-constexpr int kOrientOutF16 = 1;       // orient_kernel<kFormat>: 0 bytes, else one of these
-constexpr int kOrientOutF32 = 2;
-
-// Device record of one image: the layout of hjd_orient_item, whose reserved
-// word the host fills with the image's first tile.
-struct OrientDev {
-    const uint8_t* src;   // plane R; G and B follow at pitch * h
-    uint8_t* dst;         // plane R of the oriented image; G and B follow at dst_pitch * (its rows)
-    int32_t w, h, pitch, orientation, dst_pitch;
-    uint32_t tile_begin;
-};
-static_assert(sizeof(OrientDev) == 40, "OrientDev layout");
 
 // Bytes 3, 2, 1, 0 of w.
 __device__ __forceinline__ uint32_t orient_bswap(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x00010203u); }
+
+// Byte k of q as the output element of channel constants (a, b).
+__device__ __forceinline__ float orient_norm(uint32_t q, int k, float a, float b)
+{
+    return __builtin_fmaf(static_cast<float>((q >> (8 * k)) & 0xffu), a, b);
+}
 
 // Four output elements (the bytes of q, lowest first) of channel constants
 // (a, b) at d: one dword / dwordx2 / dwordx4, non-temporal.
@@ -65,20 +59,8 @@ __device__ __forceinline__ void orient_store_vec(uint32_t q, __attribute__((addr
         typedef __attribute__((address_space(1))) uint32_t gword;
         __builtin_nontemporal_store(q, (gword*)d);
     } else {
-        float f[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f[k] = __builtin_fmaf(static_cast<float>((q >> (8 * k)) & 0xffu), a, b);
-        if constexpr (kFormat == kOrientOutF16) {
-            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-            typedef __attribute__((address_space(1))) u32x2 gvec2;
-            const u32x2 v = {pack_half2(f[0], f[1]), pack_half2(f[2], f[3])};
-            __builtin_nontemporal_store(v, (gvec2*)d);
-        } else {
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            typedef __attribute__((address_space(1))) f32x4 gvec4;
-            const f32x4 v = {f[0], f[1], f[2], f[3]};
-            __builtin_nontemporal_store(v, (gvec4*)d);
-        }
+        store_vec4<kFormat>(d, orient_norm(q, 0, a, b), orient_norm(q, 1, a, b), orient_norm(q, 2, a, b),
+                            orient_norm(q, 3, a, b));
     }
 }
 
@@ -87,24 +69,14 @@ template <int kFormat>
 __device__ __forceinline__ void orient_store_one(uint32_t u8, __attribute__((address_space(1))) uint8_t* d, uint32_t x,
                                                  float a, float b)
 {
-    if constexpr (kFormat == 0) {
-        d[x] = static_cast<uint8_t>(u8);
-    } else {
-        const float f = __builtin_fmaf(static_cast<float>(u8), a, b);
-        if constexpr (kFormat == kOrientOutF16) {
-            typedef __attribute__((address_space(1))) uint16_t ghalf;
-            ((ghalf*)d)[x] = static_cast<uint16_t>(half_bits(f));
-        } else {
-            typedef __attribute__((address_space(1))) float gfloat;
-            ((gfloat*)d)[x] = f;
-        }
-    }
+    if constexpr (kFormat == 0) d[x] = static_cast<uint8_t>(u8);
+    else store_one<kFormat>(d, x, orient_norm(u8, 0, a, b));
 }
 
 template <int kFormat>
 __global__ __launch_bounds__(kOrientThreads) void orient_kernel(const OrientDev* __restrict__ items, int n, NormDev nk)
 {
-    constexpr int kElem = kFormat == kOrientOutF32 ? 4 : kFormat == kOrientOutF16 ? 2 : 1;
+    constexpr int kElem = out_elem_bytes(kFormat);
     constexpr uint32_t T = kOrientTile;
     constexpr uint32_t kCols = T / 4;                       // dword columns of a tile: 32, one per lane of a half-wave
     constexpr uint32_t kRowsPerPass = kOrientThreads / kCols;   // 8 row quads (loads) / 8 rows (stores) per pass
@@ -187,9 +159,7 @@ __global__ __launch_bounds__(kOrientThreads) void orient_kernel(const OrientDev*
     const float na = c == 0 ? nk.a[0] : c == 1 ? nk.a[1] : nk.a[2];
     const float nb = c == 0 ? nk.b[0] : c == 1 ? nk.b[1] : nk.b[2];
     gbyte* dp = (gbyte*)it.dst + static_cast<int64_t>(c) * it.dst_pitch * static_cast<int64_t>(uh);
-    const bool store_vec =
-        ((reinterpret_cast<uintptr_t>(it.dst) | static_cast<uintptr_t>(it.dst_pitch)) & (4 * kElem - 1)) == 0 &&
-        ((uw & 3u) == 0 || (!fh && ux0 + T <= uw));
+    const bool store_vec = store_vec_ok<kFormat>(it.dst, it.dst_pitch) && ((uw & 3u) == 0 || (!fh && ux0 + T <= uw));
     const uint32_t ux = ux0 + 4 * cd;
 #pragma unroll
     for (uint32_t m = 0; m < 4 * kPasses; ++m) {

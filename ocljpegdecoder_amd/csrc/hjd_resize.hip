@@ -6,51 +6,31 @@
 #include "hjd_resize_aa.hpp"
 
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "hjd.h"
-#include "hjd_internal.h"
+#include "hjd_post.hpp"
 
 using hjd_internal::set_error;
-
-#define HJD_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 static_assert(sizeof(hjd_resize_item) == sizeof(hjd::ResizeDev) && offsetof(hjd_resize_item, dst) == 8 &&
                   offsetof(hjd_resize_item, src_w) == 16 && offsetof(hjd_resize_item, flags) == 28,
               "hjd_resize_item is the kernel's record");
-static_assert(sizeof(hjd_internal::ResizeRecord) == sizeof(hjd::ResizeDev), "ResizeRecord is the kernel's record");
-static_assert(sizeof(hjd_internal::NormRecord) == sizeof(hjd::NormDev), "NormRecord is the kernel's record");
 
-struct hjd_resize {
-    int device = 0;
-    int n = 0, out_w = 0, out_h = 0, out_pitch = 0, out_format = 0;
+// d_items, filter 1: n horizontal records, then n vertical ones
+struct hjd_resize : hjd_internal::StageTable<hjd::ResizeDev> {
+    using StageTable::StageTable;
+    ~hjd_resize() { release(d_mid); }
+    int out_w = 0, out_h = 0, out_pitch = 0;
     int filter = HJD_RESIZE_BILINEAR;
     int max_src_h = 0;                    // filter 1: sizes the horizontal launch
-    hjd::ResizeDev* d_items = nullptr;    // filter 1: n horizontal records, then n vertical ones
     uint8_t* d_mid = nullptr;             // filter 1: the intermediate every launch of this object shares
-    hjd_internal::NormRecord norm = hjd_internal::norm_identity();
 };
 
-namespace {
-
-inline bool dim_ok(int d) { return d >= 1 && d <= hjd_internal::kResizeMaxDim; }
-
-// Groups of 256 threads per image: one quad per thread up to kMaxGroups
-// groups, beyond that the threads loop.
-constexpr int kMaxGroups = 256;
-int resize_groups(int out_w, int out_h)
+// Groups per image of a launch over rows of out_w / 4 quads, one quad per thread.
+static int resize_groups(int out_w, int rows)
 {
-    const int64_t quads = static_cast<int64_t>((out_w + 3) / 4) * out_h;
-    const int64_t g = (quads + hjd::kResizeThreads - 1) / hjd::kResizeThreads;
-    return static_cast<int>(g < kMaxGroups ? g : kMaxGroups);
+    return hjd_internal::groups_per_image(static_cast<int64_t>((out_w + 3) / 4) * rows, hjd::kResizeThreads);
 }
-
-}  // namespace
 
 int hjd_internal::resize_out_check(int n, int out_w, int out_h, int out_pitch, int out_format)
 {
@@ -70,15 +50,8 @@ int hjd_internal::resize_out_check(int n, int out_w, int out_h, int out_pitch, i
 
 int hjd_internal::resize_item_check(const ResizeRecord& it, int index, int out_format)
 {
-    if (!it.src || !it.dst) return set_error(HJD_E_INVALID, "resize item %d: src or dst is NULL", index);
-    if (reinterpret_cast<uintptr_t>(it.dst) & out_format_align_mask(out_format))
-        return set_error(HJD_E_INVALID, "resize item %d: dst must be a multiple of the element size (%d bytes)", index,
-                         out_format_row_bytes(out_format));
-    if (!dim_ok(it.w) || !dim_ok(it.h))
-        return set_error(HJD_E_INVALID, "resize item %d: source size %d x %d is outside 1..%d", index, it.w, it.h,
-                         kResizeMaxDim);
-    if (it.pitch < it.w)
-        return set_error(HJD_E_INVALID, "resize item %d: src_pitch %d is below src_w %d", index, it.pitch, it.w);
+    const int rc = item_common_check("resize", it, index, out_format);
+    if (rc) return rc;
     if (it.flags & ~hjd::kResizeFlipH)
         return set_error(HJD_E_INVALID, "resize item %d: unknown flag bits 0x%x (bit 0: horizontal flip)", index,
                          static_cast<unsigned>(it.flags & ~hjd::kResizeFlipH));
@@ -110,68 +83,38 @@ int hjd_internal::resize_aa_ratio_check(int src_w, int src_h, int out_w, int out
 int hjd_internal::launch_resize(int device, const ResizeRecord* d_items, int n, int out_w, int out_h, int out_pitch,
                                 int out_format, const NormRecord& norm, void* stream)
 {
-    HJD_HIP(hipSetDevice(device));
-    hjd::NormDev nk;
-    memcpy(&nk, &norm, sizeof(nk));
-    const int groups = resize_groups(out_w, out_h);
-    const dim3 grid(static_cast<uint32_t>(n) * static_cast<uint32_t>(groups)), block(hjd::kResizeThreads);
-    const hjd::ResizeDev* items = reinterpret_cast<const hjd::ResizeDev*>(d_items);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (out_format) {
-    case HJD_OUT_RGB_PLANAR:
-        hipLaunchKernelGGL(hjd::resize_kernel<0>, grid, block, 0, s, items, groups, out_w, out_h, out_pitch, nk);
-        break;
-    case HJD_OUT_RGB_PLANAR_F16:
-        hipLaunchKernelGGL(hjd::resize_kernel<hjd::kResizeOutF16>, grid, block, 0, s, items, groups, out_w, out_h,
-                           out_pitch, nk);
-        break;
-    case HJD_OUT_RGB_PLANAR_F32:
-        hipLaunchKernelGGL(hjd::resize_kernel<hjd::kResizeOutF32>, grid, block, 0, s, items, groups, out_w, out_h,
-                           out_pitch, nk);
-        break;
-    default:
-        return set_error(HJD_E_INVALID, "resize: output format %d has no kernel", out_format);   // (no fallback)
-    }
-    HJD_HIP(hipGetLastError());
-    return HJD_OK;
+    return with_out_format("resize", out_format, [&](auto format) -> int {
+        HJD_HIP(hipSetDevice(device));
+        const int groups = resize_groups(out_w, out_h);
+        const dim3 grid(static_cast<uint32_t>(n) * static_cast<uint32_t>(groups)), block(hjd::kResizeThreads);
+        hipLaunchKernelGGL(hjd::resize_kernel<decltype(format)::value>, grid, block, 0, static_cast<hipStream_t>(stream),
+                           d_items, groups, out_w, out_h, out_pitch, norm);
+        HJD_HIP(hipGetLastError());
+        return HJD_OK;
+    });
 }
 
 int hjd_internal::launch_resize_aa(int device, const ResizeRecord* d_h, const ResizeRecord* d_v, int n, int max_src_h,
                                    int out_w, int out_h, int out_pitch, int out_format, const NormRecord& norm,
                                    void* stream, int passes)
 {
-    if (!out_format_planar(out_format))
-        return set_error(HJD_E_INVALID, "resize: output format %d has no kernel", out_format);   // (no fallback)
-    HJD_HIP(hipSetDevice(device));
-    hjd::NormDev nk;
-    memcpy(&nk, &norm, sizeof(nk));
-    // horizontal: an image's quads are its src_h rows of out_w / 4; every image gets the largest one's groups
-    const int hgroups = resize_groups(out_w, max_src_h), vgroups = resize_groups(out_w, out_h);
-    const dim3 hgrid(static_cast<uint32_t>(n) * static_cast<uint32_t>(hgroups)),
-        vgrid(static_cast<uint32_t>(n) * static_cast<uint32_t>(vgroups)), block(hjd::kResizeThreads);
-    const hjd::ResizeDev* hitems = reinterpret_cast<const hjd::ResizeDev*>(d_h);
-    const hjd::ResizeDev* vitems = reinterpret_cast<const hjd::ResizeDev*>(d_v);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (passes & 1) {
-        hipLaunchKernelGGL(hjd::resize_aa_h_kernel, hgrid, block, 0, s, hitems, hgroups, out_w);
+    return with_out_format("resize", out_format, [&](auto format) -> int {
+        HJD_HIP(hipSetDevice(device));
+        // horizontal: an image's quads are its src_h rows of out_w / 4; every image gets the largest one's groups
+        const int hgroups = resize_groups(out_w, max_src_h), vgroups = resize_groups(out_w, out_h);
+        const dim3 hgrid(static_cast<uint32_t>(n) * static_cast<uint32_t>(hgroups)),
+            vgrid(static_cast<uint32_t>(n) * static_cast<uint32_t>(vgroups)), block(hjd::kResizeThreads);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (passes & 1) {
+            hipLaunchKernelGGL(hjd::resize_aa_h_kernel, hgrid, block, 0, s, d_h, hgroups, out_w);
+            HJD_HIP(hipGetLastError());
+        }
+        if (!(passes & 2)) return HJD_OK;
+        hipLaunchKernelGGL(hjd::resize_aa_v_kernel<decltype(format)::value>, vgrid, block, 0, s, d_v, vgroups, out_w, out_h,
+                           out_pitch, norm);
         HJD_HIP(hipGetLastError());
-    }
-    if (!(passes & 2)) return HJD_OK;
-    switch (out_format) {
-    case HJD_OUT_RGB_PLANAR:
-        hipLaunchKernelGGL(hjd::resize_aa_v_kernel<0>, vgrid, block, 0, s, vitems, vgroups, out_w, out_h, out_pitch, nk);
-        break;
-    case HJD_OUT_RGB_PLANAR_F16:
-        hipLaunchKernelGGL(hjd::resize_aa_v_kernel<hjd::kResizeOutF16>, vgrid, block, 0, s, vitems, vgroups, out_w, out_h,
-                           out_pitch, nk);
-        break;
-    default:
-        hipLaunchKernelGGL(hjd::resize_aa_v_kernel<hjd::kResizeOutF32>, vgrid, block, 0, s, vitems, vgroups, out_w, out_h,
-                           out_pitch, nk);
-        break;
-    }
-    HJD_HIP(hipGetLastError());
-    return HJD_OK;
+        return HJD_OK;
+    });
 }
 
 extern "C" {
@@ -209,14 +152,11 @@ int hjd_resize_create_filter(hjd_ctx* ctx, const hjd_resize_item* items, int n, 
     *out = nullptr;
     int rc = hjd_resize_check_filter(items, n, out_w, out_h, out_pitch, out_format, filter);
     if (rc) return rc;
-    hjd_resize* r = new (std::nothrow) hjd_resize;
+    hjd_resize* r = new (std::nothrow) hjd_resize(ctx, n, out_format);
     if (!r) return set_error(HJD_E_NOMEM, "resize allocation");
-    r->device = hjd_ctx_device(ctx);
-    r->n = n;
     r->out_w = out_w;
     r->out_h = out_h;
     r->out_pitch = out_pitch;
-    r->out_format = out_format;
     r->filter = filter;
     const bool aa = filter == HJD_RESIZE_TRIANGLE_AA;
     // the table: the items as they are; for the antialiased filter the
@@ -246,15 +186,10 @@ int hjd_resize_create_filter(hjd_ctx* ctx, const hjd_resize_item* items, int n, 
             off += hjd_internal::resize_aa_item_bytes(out_w, hrec.h);
         }
     }
-    const size_t bytes = sizeof(hjd::ResizeDev) * table.size();
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_items), bytes);
-    if (e == hipSuccess) e = hipMemcpy(r->d_items, table.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        hjd_resize_destroy(r);   // (frees whichever of the two it holds)
-        return set_error(e == hipErrorOutOfMemory ? HJD_E_NOMEM : HJD_E_HIP,
-                         "resize table upload (%zu bytes) and intermediate (%zu bytes): %s", bytes, mid_bytes,
-                         hipGetErrorString(e));
+    rc = r->upload("resize", table.data(), table.size(), e, " and intermediate (" + std::to_string(mid_bytes) + " bytes)");
+    if (rc) {
+        delete r;   // (frees whichever of the two it holds)
+        return rc;
     }
     *out = r;
     return HJD_OK;
@@ -268,23 +203,12 @@ int hjd_resize_create(hjd_ctx* ctx, const hjd_resize_item* items, int n, int out
 
 int hjd_resize_set_normalize(hjd_resize* r, const float a[3], const float b[3])
 {
-    const int rc = hjd_internal::norm_check(a, b);
-    if (rc) return rc;
-    if (!r) return set_error(HJD_E_INVALID, "resize is NULL");
-    if (!hjd_internal::out_format_float_bytes(r->out_format))
-        return set_error(HJD_E_INVALID, "hjd_resize_set_normalize: output format %d is not HJD_OUT_RGB_PLANAR_F16 / _F32",
-                         r->out_format);
-    for (int c = 0; c < 3; ++c) {   // a launch argument: an enqueued launch keeps its own
-        r->norm.a[c] = a[c];
-        r->norm.b[c] = b[c];
-    }
-    return HJD_OK;
+    return hjd_internal::table_set_normalize("resize", r, a, b);
 }
 
 static int launch_aa_object(hjd_resize* r, void* stream, int passes)
 {
-    const hjd_internal::ResizeRecord* recs = reinterpret_cast<const hjd_internal::ResizeRecord*>(r->d_items);
-    return hjd_internal::launch_resize_aa(r->device, recs, recs + r->n, r->n, r->max_src_h, r->out_w, r->out_h,
+    return hjd_internal::launch_resize_aa(r->device, r->d_items, r->d_items + r->n, r->n, r->max_src_h, r->out_w, r->out_h,
                                           r->out_pitch, r->out_format, r->norm, stream, passes);
 }
 
@@ -300,19 +224,13 @@ int hjd_resize_launch(hjd_resize* r, void* stream)
 {
     if (!r) return set_error(HJD_E_INVALID, "resize is NULL");
     if (r->filter == HJD_RESIZE_TRIANGLE_AA) return launch_aa_object(r, stream, 3);
-    return hjd_internal::launch_resize(r->device, reinterpret_cast<const hjd_internal::ResizeRecord*>(r->d_items), r->n,
-                                       r->out_w, r->out_h, r->out_pitch, r->out_format, r->norm, stream);
+    return hjd_internal::launch_resize(r->device, r->d_items, r->n, r->out_w, r->out_h, r->out_pitch, r->out_format,
+                                       r->norm, stream);
 }
 
 int hjd_resize_destroy(hjd_resize* r)
 {
-    if (!r) return HJD_OK;
-    if (r->d_items || r->d_mid) {
-        (void)hipSetDevice(r->device);
-        if (r->d_items) (void)hipFree(r->d_items);   // (waits for the launches that read the table)
-        if (r->d_mid) (void)hipFree(r->d_mid);
-    }
-    delete r;
+    delete r;   // (its destructors free the table and the intermediate)
     return HJD_OK;
 }
 

@@ -17,23 +17,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hjd_norm.hpp"
+#include "hjd_store.hpp"
 
 namespace hjd {
 
 constexpr int kResizeThreads = 256;
 constexpr int kResizeFlipH = 1;        // hjd_resize_item.flags bit 0
-constexpr int kResizeOutF16 = 1;       // resize_kernel<kFormat>: 0 bytes, else one of these
-constexpr int kResizeOutF32 = 2;
 constexpr int kResizeWeightBits = 11;
-
-// Device record of one image: the layout of hjd_resize_item.
-struct ResizeDev {
-    const uint8_t* src;   // plane R; G and B follow at pitch * h
-    uint8_t* dst;         // plane R of the output; G and B follow at out_pitch * out_h
-    int32_t w, h, pitch, flags;
-};
-static_assert(sizeof(ResizeDev) == 32, "ResizeDev layout");
 
 // Source sample position of output index j on one axis (size -> out_size):
 // the first tap p0 and the weight f (0..2047) of the second tap min(p0 + 1,
@@ -46,81 +36,19 @@ __device__ __forceinline__ void resize_tap(uint32_t j, uint32_t size, uint32_t o
     f = ((n - p0 * den) << kResizeWeightBits) / den;
 }
 
-// Store one quad: px[k] = 0x00RRGGBB of output columns j0 .. j0 + 3 of one row,
-// d the address of plane R's element j0.  vec: one dword / dwordx2 / dwordx4
-// per plane; else element stores of the columns below wo.  Non-temporal.
-template <int kFormat>
-__device__ __forceinline__ void resize_store_quad(const uint32_t (&px)[4],
-                                                  __attribute__((address_space(1))) uint8_t* d, int64_t dplane, bool vec,
-                                                  uint32_t j0, uint32_t wo, const NormDev& nk)
+// The bilinear blend's second step: top and bot, the rows' blends with the 11-bit
+// horizontal weight, blended with fy (0..2047), the weight of bot; 22 fraction
+// bits, one rounding.  The warp kernel's, too.
+__device__ __forceinline__ uint32_t resize_blend(uint32_t top, uint32_t bot, uint32_t fy)
 {
-    typedef __attribute__((address_space(1))) uint8_t gbyte;
-    if constexpr (kFormat == 0) {
-        if (vec) {
-            typedef __attribute__((address_space(1))) uint32_t gword;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int sh = 16 - 8 * c;
-                const uint32_t v = ((px[0] >> sh) & 0xffu) | (((px[1] >> sh) & 0xffu) << 8) |
-                                   (((px[2] >> sh) & 0xffu) << 16) | (((px[3] >> sh) & 0xffu) << 24);
-                __builtin_nontemporal_store(v, (gword*)(d + c * dplane));
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k < wo) {
-                    d[k] = static_cast<uint8_t>(px[k] >> 16);
-                    d[dplane + k] = static_cast<uint8_t>(px[k] >> 8);
-                    d[2 * dplane + k] = static_cast<uint8_t>(px[k]);
-                }
-        }
-    } else {
-        float f[3][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            f[0][k] = norm_px<0>(px[k], nk);
-            f[1][k] = norm_px<1>(px[k], nk);
-            f[2][k] = norm_px<2>(px[k], nk);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            gbyte* dc = d + c * dplane;
-            if constexpr (kFormat == kResizeOutF16) {
-                if (vec) {
-                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                    typedef __attribute__((address_space(1))) u32x2 gvec2;
-                    const u32x2 v = {pack_half2(f[c][0], f[c][1]), pack_half2(f[c][2], f[c][3])};
-                    __builtin_nontemporal_store(v, (gvec2*)dc);
-                } else {
-                    typedef __attribute__((address_space(1))) uint16_t ghalf;
-                    ghalf* e = (ghalf*)dc;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (j0 + k < wo) e[k] = static_cast<uint16_t>(half_bits(f[c][k]));
-                }
-            } else {
-                if (vec) {
-                    typedef float f32x4 __attribute__((ext_vector_type(4)));
-                    typedef __attribute__((address_space(1))) f32x4 gvec4;
-                    const f32x4 v = {f[c][0], f[c][1], f[c][2], f[c][3]};
-                    __builtin_nontemporal_store(v, (gvec4*)dc);
-                } else {
-                    typedef __attribute__((address_space(1))) float gfloat;
-                    gfloat* e = (gfloat*)dc;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (j0 + k < wo) e[k] = f[c][k];
-                }
-            }
-        }
-    }
+    return (top * (2048u - fy) + bot * fy + (1u << 21)) >> 22;
 }
 
 template <int kFormat>
 __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeDev* __restrict__ items, int groups,
                                                                  int out_w, int out_h, int out_pitch, NormDev nk)
 {
-    constexpr int kElem = kFormat == kResizeOutF32 ? 4 : kFormat == kResizeOutF16 ? 2 : 1;
+    constexpr int kElem = out_elem_bytes(kFormat);
     typedef __attribute__((address_space(1))) uint8_t gbyte;
     typedef __attribute__((address_space(1))) const uint8_t gcbyte;
     const uint32_t img = blockIdx.x / static_cast<uint32_t>(groups);
@@ -131,9 +59,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeDev*
     const int64_t splane = static_cast<int64_t>(it.pitch) * it.h;
     const int64_t dplane = static_cast<int64_t>(out_pitch) * out_h;
     const bool flip = (it.flags & kResizeFlipH) != 0;
-    // whole quads as one dword / dwordx2 / dwordx4 per plane (group-uniform)
-    const bool vec = ((reinterpret_cast<uintptr_t>(it.dst) | static_cast<uintptr_t>(out_pitch)) & (4 * kElem - 1)) == 0 &&
-                     (wo & 3) == 0;
+    const bool vec = store_vec_ok<kFormat>(it.dst, out_pitch) && (wo & 3) == 0;   // whole quads, one vector per plane
     const uint32_t qw = (wo + 3) >> 2, quads = qw * ho;
     for (uint32_t q = grp * kResizeThreads + threadIdx.x; q < quads; q += static_cast<uint32_t>(groups) * kResizeThreads) {
         const uint32_t i = q / qw, j0 = 4 * (q - i * qw);
@@ -158,12 +84,12 @@ __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeDev*
                 const gcbyte* b = r1 + c * splane;
                 const uint32_t top = a[x0] * (2048u - fx) + a[x1] * fx;
                 const uint32_t bot = b[x0] * (2048u - fx) + b[x1] * fx;
-                p = (p << 8) | ((top * (2048u - fy) + bot * fy + (1u << 21)) >> 22);
+                p = (p << 8) | resize_blend(top, bot, fy);
             }
             px[k] = p;
         }
         gbyte* d = (gbyte*)it.dst + static_cast<int64_t>(i) * out_pitch + static_cast<int64_t>(j0) * kElem;
-        resize_store_quad<kFormat>(px, d, dplane, vec, j0, wo, nk);
+        store_quad<kFormat>(px, d, dplane, vec, j0, wo, nk);
     }
 }
 

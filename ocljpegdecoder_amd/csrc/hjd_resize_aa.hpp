@@ -6,7 +6,7 @@
 //                           per item three planes of src_h rows x out_w bytes, the
 //                           pitch out_w rounded up to 4, the item 16-byte aligned
 //   resize_aa_v_kernel<F>   intermediate -> the output planes, with the bilinear
-//                           kernel's store forms (resize_store_quad)
+//                           kernel's store forms (store_quad, hjd_store.hpp)
 //
 // Both keep resize_kernel's decomposition: every image gets the same number of
 // 256-thread groups, blockIdx.x / groups is the group-uniform image (its 32-byte
@@ -19,7 +19,8 @@
 // plane, on both sides.  The weights are computed in the tap loop; no tables,
 // no LDS, no barrier.
 #pragma once
-#include "hjd_resize.hpp"
+#include "hjd_resize.hpp"   // kResizeThreads, kResizeFlipH
+#include "hjd_store.hpp"
 
 namespace hjd {
 
@@ -91,7 +92,7 @@ template <int kFormat>
 __global__ __launch_bounds__(kResizeThreads) void resize_aa_v_kernel(const ResizeDev* __restrict__ items, int groups,
                                                                       int out_w, int out_h, int out_pitch, NormDev nk)
 {
-    constexpr int kElem = kFormat == kResizeOutF32 ? 4 : kFormat == kResizeOutF16 ? 2 : 1;
+    constexpr int kElem = out_elem_bytes(kFormat);
     typedef __attribute__((address_space(1))) uint8_t gbyte;
     typedef __attribute__((address_space(1))) const uint32_t gcword;
     const uint32_t img = blockIdx.x / static_cast<uint32_t>(groups);
@@ -100,8 +101,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_aa_v_kernel(const Resiz
     const uint32_t h = static_cast<uint32_t>(it.h);
     const uint32_t wo = static_cast<uint32_t>(out_w), ho = static_cast<uint32_t>(out_h);
     const int64_t dplane = static_cast<int64_t>(out_pitch) * out_h;
-    const bool vec = ((reinterpret_cast<uintptr_t>(it.dst) | static_cast<uintptr_t>(out_pitch)) & (4 * kElem - 1)) == 0 &&
-                     (wo & 3) == 0;
+    const bool vec = store_vec_ok<kFormat>(it.dst, out_pitch) && (wo & 3) == 0;   // whole quads, one vector per plane
     const uint32_t qw = (wo + 3) >> 2, quads = qw * ho;
     const int64_t mplane = static_cast<int64_t>(qw) * h;   // in dwords
     const uint32_t s2 = 2 * max(h, ho);
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_aa_v_kernel(const Resiz
             px[k] = (((acc[0][k] + r) / T) << 16) | (((acc[1][k] + r) / T) << 8) | ((acc[2][k] + r) / T);
         const uint32_t j0 = 4 * qx;
         gbyte* dst = (gbyte*)it.dst + static_cast<int64_t>(i) * out_pitch + static_cast<int64_t>(j0) * kElem;
-        resize_store_quad<kFormat>(px, dst, dplane, vec, j0, wo, nk);
+        store_quad<kFormat>(px, dst, dplane, vec, j0, wo, nk);
     }
 }
 

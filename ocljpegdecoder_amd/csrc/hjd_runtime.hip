@@ -744,7 +744,6 @@ int hjd_plan_create_roi(hjd_ctx* ctx, const hjd_frame* frames, int nframes, int 
     // records, a float plan's NormDev record both; a = 1, b = 0 until hjd_plan_set_normalize
     static_assert(sizeof(hjd_internal::FrameRecord) == sizeof(FrameDev), "frame record layout");
     static_assert(sizeof(hjd_internal::RoiRecord) == sizeof(hjd::RoiDev), "side record layout");
-    static_assert(sizeof(hjd_internal::NormRecord) == sizeof(hjd::NormDev), "norm record layout");
     const bool norm = hjd_internal::out_format_float_bytes(out_format) != 0;
     const hjd_internal::FrameTable tab = hjd_internal::frame_table(nframes, rois != nullptr, norm);
     p->norm_off = norm ? tab.norm : 0;

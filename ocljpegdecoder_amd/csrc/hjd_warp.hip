@@ -6,82 +6,45 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
-#include "hjd.h"
-#include "hjd_internal.h"
+#include "hjd_post.hpp"
 
 using hjd_internal::set_error;
-
-#define HJD_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return set_error(HJD_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 static_assert(sizeof(hjd_warp_item) == sizeof(hjd::WarpDev) && offsetof(hjd_warp_item, dst) == 8 &&
                   offsetof(hjd_warp_item, src_w) == 16 && offsetof(hjd_warp_item, flags) == 28 &&
                   offsetof(hjd_warp_item, m) == 32 && offsetof(hjd_warp_item, fill) == 56 &&
                   offsetof(hjd_warp_item, reserved) == 60,
               "hjd_warp_item is the kernel's record");
-static_assert(sizeof(hjd_internal::WarpRecord) == sizeof(hjd::WarpDev) &&
-                  offsetof(hjd_internal::WarpRecord, m) == offsetof(hjd::WarpDev, m) &&
-                  offsetof(hjd_internal::WarpRecord, fill) == offsetof(hjd::WarpDev, fill),
-              "WarpRecord is the kernel's record");
 static_assert(HJD_WARP_REPLICATE == hjd::kWarpReplicate, "flags bit 0");
 
-struct hjd_warp {
-    int device = 0;
-    int n = 0, out_w = 0, out_h = 0, out_pitch = 0, out_format = 0;
-    hjd::WarpDev* d_items = nullptr;
-    hjd_internal::NormRecord norm = hjd_internal::norm_identity();
+struct hjd_warp : hjd_internal::StageTable<hjd::WarpDev> {
+    using StageTable::StageTable;
+    int out_w = 0, out_h = 0, out_pitch = 0;
 };
 
 namespace {
 
-inline bool dim_ok(int d) { return d >= 1 && d <= hjd_internal::kResizeMaxDim; }
-
-// Groups of 256 threads per image: one unit (a quad, or a thread's place in a
-// wave's tile) per thread up to kMaxGroups groups, beyond that the threads loop.
-constexpr int kMaxGroups = 256;
-int warp_groups(int out_w, int out_h, bool tiled)
+// The units of an image dealt to its groups' threads: its quads, or (tiled) a
+// thread's place in each wave's tile.
+int64_t warp_units(int out_w, int out_h, bool tiled)
 {
     const int64_t qw = (out_w + 3) / 4;
-    const int64_t units = tiled ? ((qw + hjd::kWarpTileQuads - 1) / hjd::kWarpTileQuads) *
-                                      ((out_h + hjd::kWarpTileRows - 1) / hjd::kWarpTileRows) * 64
-                                : qw * out_h;
-    const int64_t g = (units + hjd::kWarpThreads - 1) / hjd::kWarpThreads;
-    return static_cast<int>(g < kMaxGroups ? g : kMaxGroups);
+    return tiled ? ((qw + hjd::kWarpTileQuads - 1) / hjd::kWarpTileQuads) *
+                       ((out_h + hjd::kWarpTileRows - 1) / hjd::kWarpTileRows) * 64
+                 : qw * out_h;
 }
 
 inline int64_t floor_q16(int64_t v) { return v >> 16; }   // (arithmetic shift: floor)
 
 inline int clamp_int(int64_t v, int lo, int hi) { return static_cast<int>(v < lo ? lo : v > hi ? hi : v); }
 
-template <int kFormat>
-void launch_form(bool tiled, dim3 grid, dim3 block, hipStream_t s, const hjd::WarpDev* items, int groups, int out_w,
-                 int out_h, int out_pitch, const hjd::NormDev& nk)
-{
-    if (tiled == hjd::kWarpTiled)
-        hipLaunchKernelGGL(hjd::warp_kernel<kFormat>, grid, block, 0, s, items, groups, out_w, out_h, out_pitch, nk);
-    else
-        hipLaunchKernelGGL(hjd::warp_other_form_kernel<kFormat>, grid, block, 0, s, items, groups, out_w, out_h,
-                           out_pitch, nk);
-}
-
 }  // namespace
 
 int hjd_internal::warp_item_check(const WarpRecord& it, int index, int out_format)
 {
-    if (!it.src || !it.dst) return set_error(HJD_E_INVALID, "warp item %d: src or dst is NULL", index);
-    if (reinterpret_cast<uintptr_t>(it.dst) & out_format_align_mask(out_format))
-        return set_error(HJD_E_INVALID, "warp item %d: dst must be a multiple of the element size (%d bytes)", index,
-                         out_format_row_bytes(out_format));
-    if (!dim_ok(it.w) || !dim_ok(it.h))
-        return set_error(HJD_E_INVALID, "warp item %d: source size %d x %d is outside 1..%d", index, it.w, it.h,
-                         kResizeMaxDim);
-    if (it.pitch < it.w)
-        return set_error(HJD_E_INVALID, "warp item %d: src_pitch %d is below src_w %d", index, it.pitch, it.w);
+    const int rc = item_common_check("warp", it, index, out_format);
+    if (rc) return rc;
     if (it.flags & ~hjd::kWarpReplicate)
         return set_error(HJD_E_INVALID, "warp item %d: unknown flag bits 0x%x (bit 0: HJD_WARP_REPLICATE)", index,
                          static_cast<unsigned>(it.flags & ~hjd::kWarpReplicate));
@@ -144,25 +107,21 @@ int hjd_internal::warp_orient(const int32_t m[6], int stored_w, int stored_h, in
 int hjd_internal::launch_warp(int device, const WarpRecord* d_items, int n, int out_w, int out_h, int out_pitch,
                               int out_format, const NormRecord& norm, void* stream, int tiled)
 {
-    if (!out_format_planar(out_format))
-        return set_error(HJD_E_INVALID, "warp: output format %d has no kernel", out_format);   // (no fallback)
-    HJD_HIP(hipSetDevice(device));
-    hjd::NormDev nk;
-    memcpy(&nk, &norm, sizeof(nk));
-    const bool form = tiled < 0 ? hjd::kWarpTiled : tiled != 0;
-    const int groups = warp_groups(out_w, out_h, form);
-    const dim3 grid(static_cast<uint32_t>(n) * static_cast<uint32_t>(groups)), block(hjd::kWarpThreads);
-    const hjd::WarpDev* items = reinterpret_cast<const hjd::WarpDev*>(d_items);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (out_format) {
-    case HJD_OUT_RGB_PLANAR: launch_form<0>(form, grid, block, s, items, groups, out_w, out_h, out_pitch, nk); break;
-    case HJD_OUT_RGB_PLANAR_F16:
-        launch_form<hjd::kResizeOutF16>(form, grid, block, s, items, groups, out_w, out_h, out_pitch, nk);
-        break;
-    default: launch_form<hjd::kResizeOutF32>(form, grid, block, s, items, groups, out_w, out_h, out_pitch, nk); break;
-    }
-    HJD_HIP(hipGetLastError());
-    return HJD_OK;
+    return with_out_format("warp", out_format, [&](auto format) -> int {
+        constexpr int kFormat = decltype(format)::value;
+        HJD_HIP(hipSetDevice(device));
+        const bool form = tiled < 0 ? hjd::kWarpTiled : tiled != 0;
+        const int groups = groups_per_image(warp_units(out_w, out_h, form), hjd::kWarpThreads);
+        const dim3 grid(static_cast<uint32_t>(n) * static_cast<uint32_t>(groups)), block(hjd::kWarpThreads);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (form == hjd::kWarpTiled)
+            hipLaunchKernelGGL(hjd::warp_kernel<kFormat>, grid, block, 0, s, d_items, groups, out_w, out_h, out_pitch, norm);
+        else
+            hipLaunchKernelGGL(hjd::warp_other_form_kernel<kFormat>, grid, block, 0, s, d_items, groups, out_w, out_h,
+                               out_pitch, norm);
+        HJD_HIP(hipGetLastError());
+        return HJD_OK;
+    });
 }
 
 extern "C" {
@@ -198,26 +157,17 @@ int hjd_warp_create(hjd_ctx* ctx, const hjd_warp_item* items, int n, int out_w, 
 {
     if (!ctx || !out) return set_error(HJD_E_INVALID, "warp: ctx or out is NULL");
     *out = nullptr;
-    const int rc = hjd_warp_check(items, n, out_w, out_h, out_pitch, out_format);
+    int rc = hjd_warp_check(items, n, out_w, out_h, out_pitch, out_format);
     if (rc) return rc;
-    hjd_warp* w = new (std::nothrow) hjd_warp;
+    hjd_warp* w = new (std::nothrow) hjd_warp(ctx, n, out_format);
     if (!w) return set_error(HJD_E_NOMEM, "warp allocation");
-    w->device = hjd_ctx_device(ctx);
-    w->n = n;
     w->out_w = out_w;
     w->out_h = out_h;
     w->out_pitch = out_pitch;
-    w->out_format = out_format;
-    const size_t bytes = sizeof(hjd::WarpDev) * static_cast<size_t>(n);
-    hipError_t e = hipSetDevice(w->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_items), bytes);
-    if (e != hipSuccess) w->d_items = nullptr;
-    if (e == hipSuccess) e = hipMemcpy(w->d_items, items, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        hjd_warp_destroy(w);
-        return set_error(e == hipErrorOutOfMemory ? HJD_E_NOMEM : HJD_E_HIP, "warp table upload (%zu bytes): %s", bytes,
-                         hipGetErrorString(e));
+    rc = w->upload("warp", items, static_cast<size_t>(n));   // (hjd_warp_item is the kernel's record)
+    if (rc) {
+        delete w;
+        return rc;
     }
     *out = w;
     return HJD_OK;
@@ -225,24 +175,14 @@ int hjd_warp_create(hjd_ctx* ctx, const hjd_warp_item* items, int n, int out_w, 
 
 int hjd_warp_set_normalize(hjd_warp* w, const float a[3], const float b[3])
 {
-    const int rc = hjd_internal::norm_check(a, b);
-    if (rc) return rc;
-    if (!w) return set_error(HJD_E_INVALID, "warp is NULL");
-    if (!hjd_internal::out_format_float_bytes(w->out_format))
-        return set_error(HJD_E_INVALID, "hjd_warp_set_normalize: output format %d is not HJD_OUT_RGB_PLANAR_F16 / _F32",
-                         w->out_format);
-    for (int c = 0; c < 3; ++c) {   // a launch argument: an enqueued launch keeps its own
-        w->norm.a[c] = a[c];
-        w->norm.b[c] = b[c];
-    }
-    return HJD_OK;
+    return hjd_internal::table_set_normalize("warp", w, a, b);
 }
 
 int hjd_warp_launch(hjd_warp* w, void* stream)
 {
     if (!w) return set_error(HJD_E_INVALID, "warp is NULL");
-    return hjd_internal::launch_warp(w->device, reinterpret_cast<const hjd_internal::WarpRecord*>(w->d_items), w->n,
-                                     w->out_w, w->out_h, w->out_pitch, w->out_format, w->norm, stream);
+    return hjd_internal::launch_warp(w->device, w->d_items, w->n, w->out_w, w->out_h, w->out_pitch, w->out_format,
+                                     w->norm, stream);
 }
 
 int hjd_debug_warp_launch_form(hjd_warp* w, int tiled, void* stream)
@@ -250,18 +190,13 @@ int hjd_debug_warp_launch_form(hjd_warp* w, int tiled, void* stream)
     if (!w) return set_error(HJD_E_INVALID, "warp is NULL");
     if (tiled != 0 && tiled != 1)
         return set_error(HJD_E_INVALID, "hjd_debug_warp_launch_form: form %d is neither 0 (row-major) nor 1 (tiled)", tiled);
-    return hjd_internal::launch_warp(w->device, reinterpret_cast<const hjd_internal::WarpRecord*>(w->d_items), w->n,
-                                     w->out_w, w->out_h, w->out_pitch, w->out_format, w->norm, stream, tiled);
+    return hjd_internal::launch_warp(w->device, w->d_items, w->n, w->out_w, w->out_h, w->out_pitch, w->out_format,
+                                     w->norm, stream, tiled);
 }
 
 int hjd_warp_destroy(hjd_warp* w)
 {
-    if (!w) return HJD_OK;
-    if (w->d_items) {
-        (void)hipSetDevice(w->device);
-        (void)hipFree(w->d_items);   // (waits for the launches that read the table)
-    }
-    delete w;
+    delete w;   // (its destructor frees the table)
     return HJD_OK;
 }
 

@@ -11,10 +11,10 @@
 // 64-byte record read with scalar loads; a lane produces quads of 4
 // horizontally adjacent output pixels, all three channels; byte loads straight
 // from the planes (the crops were written by the kernel before and sit in
-// L2); no LDS, no barrier; resize_store_quad writes the quad.  What differs is
-// how the quads are dealt.  Once the map rotates, the 256 output pixels of a
-// wave that takes 64 consecutive quads of a row lie on one slanted line
-// through the source, 256 source pixels long.  Tiled (kTiled), a wave takes 8
+// L2); no LDS, no barrier; store_quad (hjd_store.hpp) writes the quad.  What
+// differs is how the quads are dealt.  Once the map rotates, the 256 output
+// pixels of a wave that takes 64 consecutive quads of a row lie on one slanted
+// line through the source, 256 source pixels long.  Tiled (kTiled), a wave takes 8
 // quads x 8 rows -- 32 x 8 output pixels -- whose taps lie within a few dozen
 // source rows and columns; a group's four waves take four consecutive tiles of
 // a tile row.  DESIGN.md s3.12 has both forms' times.
@@ -28,7 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hjd_resize.hpp"
+#include "hjd_resize.hpp"   // resize_blend
+#include "hjd_store.hpp"
 
 namespace hjd {
 
@@ -38,22 +39,11 @@ constexpr int kWarpTileQuads = 8;      // a wave's tile: 8 quads (32 pixels) x 8
 constexpr int kWarpTileRows = 8;
 constexpr bool kWarpTiled = true;      // the form hjd_warp_launch takes
 
-// Device record of one image: the layout of hjd_warp_item.
-struct WarpDev {
-    const uint8_t* src;   // plane R; G and B follow at pitch * h
-    uint8_t* dst;         // plane R of the output; G and B follow at out_pitch * out_h
-    int32_t w, h, pitch, flags;
-    int32_t m[6];         // X = m0 j + m1 i + m2, Y = m3 j + m4 i + m5 (Q16 source pixel indices)
-    uint32_t fill;        // 0x00RRGGBB
-    int32_t reserved;
-};
-static_assert(sizeof(WarpDev) == 64, "WarpDev layout");
-
 template <int kFormat, bool kTiled>
 __device__ __forceinline__ void warp_image(const WarpDev* __restrict__ items, int groups, int out_w, int out_h,
                                            int out_pitch, const NormDev& nk)
 {
-    constexpr int kElem = kFormat == kResizeOutF32 ? 4 : kFormat == kResizeOutF16 ? 2 : 1;
+    constexpr int kElem = out_elem_bytes(kFormat);
     typedef __attribute__((address_space(1))) uint8_t gbyte;
     typedef __attribute__((address_space(1))) const uint8_t gcbyte;
     const uint32_t img = blockIdx.x / static_cast<uint32_t>(groups);
@@ -64,9 +54,7 @@ __device__ __forceinline__ void warp_image(const WarpDev* __restrict__ items, in
     const int64_t splane = static_cast<int64_t>(it.pitch) * it.h;
     const int64_t dplane = static_cast<int64_t>(out_pitch) * out_h;
     const bool replicate = (it.flags & kWarpReplicate) != 0;
-    // whole quads as one dword / dwordx2 / dwordx4 per plane (group-uniform)
-    const bool vec = ((reinterpret_cast<uintptr_t>(it.dst) | static_cast<uintptr_t>(out_pitch)) & (4 * kElem - 1)) == 0 &&
-                     (wo & 3) == 0;
+    const bool vec = store_vec_ok<kFormat>(it.dst, out_pitch) && (wo & 3) == 0;   // whole quads, one vector per plane
     const uint32_t qw = (wo + 3) >> 2;
     // the units dealt round-robin: quads, or a thread's place in a wave's tile
     const uint32_t tiles_x = (qw + kWarpTileQuads - 1) / kWarpTileQuads;
@@ -111,14 +99,14 @@ __device__ __forceinline__ void warp_image(const WarpDev* __restrict__ items, in
                 const uint32_t C = ix0 && iy1 ? b[cx0] : fb, D = ix1 && iy1 ? b[cx1] : fb;
                 const uint32_t top = A * (2048u - fx) + B * fx;
                 const uint32_t bot = C * (2048u - fx) + D * fx;
-                p = (p << 8) | ((top * (2048u - fy) + bot * fy + (1u << 21)) >> 22);
+                p = (p << 8) | resize_blend(top, bot, fy);
             }
             px[k] = p;
             X += it.m[0];
             Y += it.m[3];
         }
         gbyte* d = (gbyte*)it.dst + static_cast<int64_t>(i) * out_pitch + static_cast<int64_t>(j0) * kElem;
-        resize_store_quad<kFormat>(px, d, dplane, vec, j0, wo, nk);
+        store_quad<kFormat>(px, d, dplane, vec, j0, wo, nk);
     }
 }
 
