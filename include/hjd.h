@@ -68,7 +68,9 @@ enum hjd_out_format {
      * form (N, 3, H, W).  HJD_GRAY frames write three identical planes.
      *
      * HJD_OUT_RGB24 and HJD_OUT_RGB_PLANAR take ANY out_pitch >= 3*width
-     * (planar: >= width), any out_offset and any per-image output pointer, so
+     * (planar: >= width) up to HJD_MAX_OUT_PITCH (2^28, the bound of every
+     * format: a larger pitch is HJD_E_INVALID, see hjd_frame.out_pitch), any
+     * out_offset and any per-image output pointer, so
      * a contiguous array of any width can be the destination.  A frame whose
      * out_pitch, out_offset (and output pointer) are all multiples of 4 is
      * written with full-width vector stores; any other frame takes the
@@ -125,6 +127,15 @@ enum hjd_input_format {
     HJD_IN_I32_NATURAL = 1
 };
 
+/* The largest out_pitch of a frame, in bytes, for every sampling, scale and
+ * output format (also of hjd_gdec_decode's per-image pitches): the fused pixel
+ * kernel adds up to 15 rows of out_pitch and one strip row in a 32-bit lane
+ * offset, and 2^28 is the largest power of two for which that fits.  A larger
+ * pitch is refused with HJD_E_INVALID ("frame N: out_pitch P is above
+ * HJD_MAX_OUT_PITCH (268435456)").  Pinned on the device at the bound for
+ * every sampling and format (tests/test_gpu_pitch_limits.py). */
+#define HJD_MAX_OUT_PITCH (1 << 28)
+
 /*
  * One frame of a batch.  Blocks are MCU-major in raster MCU order; per MCU the
  * Y blocks in HxV raster order, then Cb, then Cr (src/decoder.cpp:286-344).
@@ -140,7 +151,8 @@ typedef struct hjd_frame {
     int32_t height;
     int32_t out_pitch;    /* bytes per output row, >= 4*width (BGR24: 3*width), multiple of 4;
                            * RGB24: >= 3*width, planar RGB: >= width, any value; float planar: >= 2*width
-                           * (F16) or 4*width (F32), multiple of the element size (see hjd_out_format) */
+                           * (F16) or 4*width (F32), multiple of the element size (see hjd_out_format);
+                           * every format: <= HJD_MAX_OUT_PITCH */
     int32_t sampling;     /* enum hjd_sampling (not HJD_OTHER) */
     int32_t qt_index[3];  /* per component (Y, Cb, Cr): index into the qtable set */
     int32_t out_format;   /* enum hjd_out_format (HJD_OUT_BGRX = 0); the same for all frames of a plan */
@@ -334,7 +346,12 @@ int hjd_plan_launch_shape(const hjd_plan* plan, hjd_launch_shape* out);
  * Source: three uint8 planes R, G, B of src_w x src_h as HJD_OUT_RGB_PLANAR
  * writes them: rows src_pitch bytes apart, planes src_pitch * src_h apart;
  * any pointer and any src_pitch >= src_w.  All four dimensions lie in
- * 1..16384 (every expression below then fits 32-bit arithmetic).
+ * 1..16384 (every expression below then fits 32-bit arithmetic).  Pinned on
+ * the device for the resize, its antialiased filter, hjd_orient_* and
+ * hjd_warp_* (tests/test_gpu_stage_limits.py): dimensions of 16384, the
+ * antialiased filter's edge, and src_pitch / out_pitch of 2^30 bytes, whose row
+ * and plane offsets (64-bit in these kernels: no upper bound on their pitches)
+ * pass 2^32 inside one image.
  *
  * Definition (exact, integer): bilinear with half-pixel centres
  * (align_corners = false), 11-bit weights, no antialiasing.  Per axis (x

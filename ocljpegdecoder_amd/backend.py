@@ -227,7 +227,8 @@ class FrameSpec:
     sampling: int
     coef_offset: int = 0          # in blocks
     out_offset: int = 0           # bytes
-    out_pitch: int = 0            # bytes (0 -> default_pitch(width, out_format); of the scaled width in a scaled plan)
+    out_pitch: int = 0            # bytes (0 -> default_pitch(width, out_format); of the scaled width in a scaled plan);
+    #                               at most 2**28 (HJD_MAX_OUT_PITCH, include/hjd.h)
     qt_index: Sequence[int] = field(default_factory=lambda: (0, 1, 1))
     out_format: int = OUT_BGRX
     roi: Optional[Sequence[int]] = None   # (x, y, w, h) on the output grid: the frame comes out cropped to it

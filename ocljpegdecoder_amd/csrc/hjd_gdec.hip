@@ -276,6 +276,9 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, int out_format, bool fno
                              "BGR24: 4-byte aligned, >= 3*width; RGB24: >= 3*width; planar RGB: >= width; "
                              "float planar: element-aligned, >= 2*width (F16) or 4*width (F32); "
                              "width = the scaled width, or the ROI's)", i);
+        if (c.pitches[i] > hjd_internal::kMaxOutPitch)
+            return set_error(HJD_E_INVALID, "frame %d: out_pitch %d is above HJD_MAX_OUT_PITCH (%d)", i, c.pitches[i],
+                             hjd_internal::kMaxOutPitch);
         ++px.nrec[sampling_class(p.sampling)];
     }
     for (int k = 1; k < hjd_internal::kSamplingClasses; ++k)

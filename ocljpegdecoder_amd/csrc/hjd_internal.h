@@ -180,6 +180,27 @@ inline bool out_format_any_alignment(int out_format)
 inline int out_format_pitch_mask(int out_format) { return out_format_row(out_format).pitch_mask; }
 inline uintptr_t out_format_align_mask(int out_format) { return out_format_row(out_format).align_mask; }
 
+// The largest out_pitch of the fused pixel kernel (HJD_MAX_OUT_PITCH, include/hjd.h).
+// The kernel adds a 32-bit per-lane byte offset to a 64-bit wave-uniform row
+// base (store4, hjd_kernels.hpp); the offset is rows * pitch + the lane's bytes
+// within the strip row, with `rows` the row of the strip the base does not
+// already hold.  Per branch of colour_stage / colour_stage_scaled, the most
+// rows and the strip row's bytes at 4 bytes per pixel or element (BGRX, F32):
+//     4:2:0, 4:4:4   2 (ylane; the row pair is in the base)       128 px   512
+//     4:2:2          7 (y = u / 48, u <= 383)                     192 px   768
+//     4:1:1          7 (y)                                        256 px  1024
+//     4:4:0         15 (y0 = 2p <= 14, then lo + pitch)            96 px   384
+//     gray           7 (y = u / 96, u <= 767)                     384 px  1536
+//     scaled         7 (y < kMcuH >> kLog <= 8)               <= 192 px   768
+// A ROI moves the 64-bit strip base only.  The offset stays below 2^32 when
+// 15 * pitch + 1536 <= 2^32 - 1, that is pitch <= 286331050; the largest power
+// of two is 2^28 (15 * 2^28 + 1536 = 4026533376 < 4294967296; 15 * 2^29 is
+// not).  One bound for every sampling, scale and format.
+constexpr int32_t kMaxOutPitch = HJD_MAX_OUT_PITCH;
+static_assert(15ll * kMaxOutPitch + 1536 <= 0xffffffffll && 15ll * 2 * kMaxOutPitch + 1536 > 0xffffffffll &&
+                  (kMaxOutPitch & (kMaxOutPitch - 1)) == 0,
+              "the largest power of two whose 15 rows and one strip row fit a 32-bit lane offset");
+
 // Rows of this format can take the kernel's full-width vector stores.
 // out_base: the frame's offset; base_bits: low bits of the address out_base
 // is relative to, where that address is not known to be 16-byte aligned.

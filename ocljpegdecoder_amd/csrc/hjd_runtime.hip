@@ -321,6 +321,8 @@ int64_t hjd_internal::make_frame_record(int width, int height, int sampling, int
     int rc = geometry(width, height, sampling, mw, mh, bpm, tasks_mcus);
     if (rc) return rc;
     if ((rc = shape_check(make_shape(sampling, scale)))) return rc;
+    if (pitch > kMaxOutPitch)   // every caller's records: plans, the GPU decoder, the stream pipeline
+        return set_error(HJD_E_INVALID, "out_pitch %d is above HJD_MAX_OUT_PITCH (%d)", pitch, kMaxOutPitch);
     static_assert(sizeof(FrameRecord) == sizeof(FrameDev), "record layout");
     FrameDev d;
     memset(&d, 0, sizeof(d));
@@ -653,6 +655,9 @@ static int check_frame(const hjd_frame& f, const hjd_frame& first, DecodeShape s
     if (f.out_pitch < static_cast<int64_t>(hjd_internal::out_format_row_bytes(f.out_format)) * sw ||
         (f.out_pitch & amask) || (f.out_offset & amask))
         return fail(HJD_E_INVALID, "frame %d: bad output pitch/offset", i);
+    if (f.out_pitch > hjd_internal::kMaxOutPitch)   // (the kernel's 32-bit lane offset: hjd_internal.h)
+        return fail(HJD_E_INVALID, "frame %d: out_pitch %d is above HJD_MAX_OUT_PITCH (%d)", i, f.out_pitch,
+                    hjd_internal::kMaxOutPitch);
     *pixels = static_cast<int64_t>(sw) * sh;
     *blocks = roi ? rg.blocks : static_cast<int64_t>(mw) * mh * bpm;
     return HJD_OK;
