@@ -400,6 +400,23 @@ int hjd_debug_entropy_emulate(const uint8_t* data, size_t size, int sub_bits, in
  * entries of the first scan; *runs compared, *mismatches in exit state or
  * statistics. */
 int hjd_debug_entropy_sync_check(const uint8_t* data, size_t size, int sub_bits, int64_t* runs, int64_t* mismatches);
+/* Test hook (no GPU, nothing staged): the uploads a GPU decoder would issue for
+ * a batch of n frames given as numbers, frames[i][8] = {destuff mode (0 host,
+ * 1 raw from the caller's pinned memory, 2 raw from the staging), data_off,
+ * data_bits, raw_len, raw_off, raw_src (the address), a further scan's data_off
+ * and data_bits (< 0: none)}; data_base: where the data area starts in staging
+ * and blob; hdr_used: the header's bytes; latency: a latency decoder, which
+ * pulls a batch destuffed on the host throughout; prepulled: bytes of frame 0
+ * an early pull moved.  rows[k][6] = {kind (0 header, 1 data run, 2 raw from
+ * the staging, 3 raw span from the caller), destination offset (0, 1: in the
+ * blob; 2, 3: in the raw area), source (staging offset; 3: the address), bytes,
+ * first, last: the frames [first, last) it covers}, in issue order; segs[k][2]
+ * = {offset, length} of the pull's segments in 16-byte words (room for 4);
+ * totals = {bytes moved host to device, scan bytes the host CPU read + wrote},
+ * as hjd_gdec_last_bytes reports them. */
+int hjd_debug_upload_plan(const int64_t* frames, int n, int64_t data_base, int64_t hdr_used, int latency,
+                          int64_t prepulled, int64_t* rows, int cap_rows, int* nrows, int64_t* segs, int* nsegs,
+                          int* pull, int64_t totals[2]);
 
 /* Test hook: the state a decoder carries from call to call (read-only; the
  * batch_* fields describe the most recent issued call, the lead_* fields the

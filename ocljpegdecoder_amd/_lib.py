@@ -320,6 +320,11 @@ def _bind_host(lib):
                                                      ctypes.POINTER(ctypes.c_int16), ctypes.c_int64, c_i32p]),
         "hjd_debug_entropy_sync_check": (ctypes.c_int, [u8p, ctypes.c_size_t, ctypes.c_int,
                                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+        "hjd_debug_upload_plan": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                                 ctypes.POINTER(ctypes.c_int64), ctypes.c_int, c_i32p,
+                                                 ctypes.POINTER(ctypes.c_int64), c_i32p, c_i32p,
+                                                 ctypes.POINTER(ctypes.c_int64)]),
         "hjd_debug_gdec_state": (ctypes.c_int, [vp, ctypes.POINTER(HjdGdecDebugState)]),
         "hjd_debug_gdec_set_chain_epoch": (ctypes.c_int, [vp, ctypes.c_uint32]),
     })

@@ -498,6 +498,20 @@ __host__ __device__ __forceinline__ void repair_frame(const EntBatchDev& b, uint
 // decoder's policy, hjd_gdec.hip; the emulation runs step 0).
 uint32_t spec_lead_bits(uint32_t step);
 
+// pull_kernel's argument: 16-B words of `src` copied to the same offsets of `dst`.
+constexpr int kPullSegs = 4;
+struct PullSegs {
+    uint64_t off[kPullSegs];     // 16-B words
+    uint64_t words[kPullSegs];
+    uint32_t n;
+    // The next segment: `bytes` at byte offset `off16` (a multiple of 16) of the staging.
+    void add(size_t off16, size_t bytes)
+    {
+        off[n] = off16 / 16;
+        words[n++] = (bytes + 15) / 16;
+    }
+};
+
 #ifdef __HIPCC__
 // The launches live with the kernels (hjd_entropy.hip).
 //
@@ -506,13 +520,6 @@ uint32_t spec_lead_bits(uint32_t step);
 // was last derived from (updated here).
 int launch_entropy(const EntBatchDev& b, const uint8_t* tabs_h, std::vector<uint8_t>& steps_tabs, hipStream_t s);
 
-// pull_kernel: 16-B words of `src` copied to the same offsets of `dst`.
-constexpr int kPullSegs = 4;
-struct PullSegs {
-    uint64_t off[kPullSegs];     // 16-B words
-    uint64_t words[kPullSegs];
-    uint32_t n;
-};
 hipError_t launch_pull(const uint8_t* src, uint8_t* dst, const PullSegs& segs, hipStream_t s);
 #endif
 

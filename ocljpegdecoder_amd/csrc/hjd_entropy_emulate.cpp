@@ -449,6 +449,55 @@ int hjd_debug_destuff_host(const uint8_t* scan, size_t n, uint8_t* out, size_t c
     return HJD_OK;
 }
 
+// Test hook for the upload plan alone (Staging::plan_uploads): the frames come
+// as numbers, nothing is staged.  frames[i][8]: destuff mode, data_off,
+// data_bits, raw_len, raw_off, raw_src (an address, only compared), and a
+// further scan's data_off and data_bits (data_bits < 0: none).
+int hjd_debug_upload_plan(const int64_t* frames, int n, int64_t data_base, int64_t hdr_used, int latency,
+                          int64_t prepulled, int64_t* rows, int cap_rows, int* nrows, int64_t* segs, int* nsegs,
+                          int* pull, int64_t totals[2])
+{
+    if (!frames || n <= 0 || !rows || !nrows || !segs || !nsegs || !pull || !totals)
+        return set_error(HJD_E_INVALID, "invalid upload-plan arguments");
+    Staging st;
+    st.caps.data = static_cast<size_t>(data_base);
+    st.H.used = static_cast<size_t>(hdr_used);
+    st.frames.resize(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        const int64_t* f = frames + 8 * i;
+        Prepared& p = st.frames[i];
+        p.destuff = static_cast<int>(f[0]);
+        p.data_off = static_cast<size_t>(f[1]);
+        p.data_bits = static_cast<uint32_t>(f[2]);
+        p.raw_len = static_cast<uint32_t>(f[3]);
+        p.raw_off = static_cast<uint64_t>(f[4]);
+        p.raw_src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(f[5]));
+        if (f[7] < 0) continue;
+        p.more.resize(1);
+        p.more[0].data_off = static_cast<size_t>(f[6]);
+        p.more[0].data_bits = static_cast<uint32_t>(f[7]);
+    }
+    UploadPlan plan;
+    st.plan_uploads(latency != 0, static_cast<size_t>(prepulled), plan);
+    if (plan.copies.size() > static_cast<size_t>(cap_rows)) return set_error(HJD_E_INVALID, "more rows than cap_rows");
+    *nrows = static_cast<int>(plan.copies.size());
+    for (const UploadCopy& u : plan.copies) {
+        const int64_t row[6] = {u.kind, static_cast<int64_t>(u.dst_off), static_cast<int64_t>(u.src),
+                                static_cast<int64_t>(u.bytes), u.first, u.last};
+        memcpy(rows, row, sizeof(row));
+        rows += 6;
+    }
+    *pull = plan.pull;
+    *nsegs = static_cast<int>(plan.segs.n);
+    for (uint32_t k = 0; k < plan.segs.n; ++k) {
+        segs[2 * k] = static_cast<int64_t>(plan.segs.off[k]);
+        segs[2 * k + 1] = static_cast<int64_t>(plan.segs.words[k]);
+    }
+    totals[0] = plan.moved;
+    totals[1] = plan.host_bytes;
+    return HJD_OK;
+}
+
 // The decoder's steps on the host, one JPEG: staged as a batch of one
 // (Staging, in calloc'd memory), then emulate() over work arrays of its own.
 int hjd_debug_entropy_emulate(const uint8_t* data, size_t size, int sub_bits, int16_t* coefs,

@@ -417,5 +417,57 @@ int Staging::assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, uin
     return HJD_OK;
 }
 
+void Staging::plan_uploads(bool latency, size_t prepulled, UploadPlan& out) const
+{
+    const int n = static_cast<int>(frames.size());
+    out.copies.clear();
+    out.segs = PullSegs{};
+    out.moved = static_cast<int64_t>(H.used);
+    out.host_bytes = 0;
+    out.pull = latency;
+    for (const Prepared& p : frames) {
+        out.pull = out.pull && p.destuff == kDestuffHost;
+        if (p.destuff == kDestuffFromStaging) out.host_bytes += 2 * static_cast<int64_t>(p.raw_len);
+        if (p.destuff != kDestuffHost) continue;
+        out.host_bytes += static_cast<int64_t>(p.raw_len) + p.data_bits / 8;
+        for (const Prepared& q : p.more) out.host_bytes += q.data_bits / 8;
+    }
+    if (out.pull) out.segs.add(0, H.used);
+    else out.copies.push_back({kUploadHeader, 0, 0, H.used, 0, 0});
+    // In batch order: a run of consecutive host-destuffed frames (all their scans) moves in one
+    // copy to the data area, a raw scan in the staging in one to the raw area.
+    for (int i = 0, j; i < n; i = j) {
+        const Prepared& p = frames[i];
+        j = i + 1;
+        if (p.destuff == kDestuffFromStaging) {
+            out.copies.push_back({kUploadRawStaged, p.raw_off, caps.data + p.data_off, p.raw_len, i, j});
+            out.moved += p.raw_len;
+        } else if (p.destuff == kDestuffHost) {
+            while (j < n && frames[j].destuff == kDestuffHost) ++j;
+            const size_t off = caps.data + p.data_off, len = frames[j - 1].data_end() - p.data_off;
+            // Pulled: every frame is host-destuffed, so this run is the whole batch, i is 0 (frame 0
+            // starts the data area, where an early pull began) and segs holds two of its kPullSegs.
+            if (out.pull) out.segs.add(off + prepulled, len - prepulled);
+            else out.copies.push_back({kUploadData, off, off, len, i, j});
+            out.moved += static_cast<int64_t>(len);
+        }
+    }
+    // Last, raw scans in the caller's pinned memory, straight from there to the raw area: a run
+    // of scans placed at their distance in the caller's memory (RawCursor) moves in one DMA.
+    for (int i = 0, j; i < n; i = j) {
+        const Prepared& p = frames[i];
+        j = i + 1;
+        if (p.destuff != kDestuffFromCaller) continue;
+        size_t span = p.raw_len;
+        while (j < n && frames[j].destuff == kDestuffFromCaller && frames[j].raw_src > p.raw_src &&
+               frames[j].raw_off - p.raw_off == static_cast<uint64_t>(frames[j].raw_src - p.raw_src)) {
+            span = static_cast<size_t>(frames[j].raw_src - p.raw_src) + frames[j].raw_len;
+            ++j;
+        }
+        out.copies.push_back({kUploadRawCaller, p.raw_off, reinterpret_cast<uintptr_t>(p.raw_src), span, i, j});
+        out.moved += static_cast<int64_t>(span);
+    }
+}
+
 }  // namespace ent
 }  // namespace hjd

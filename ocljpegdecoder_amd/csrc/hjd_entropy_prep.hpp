@@ -1,7 +1,7 @@
 // hjd_entropy_prep.hpp -- host preparation of a GPU entropy batch
 // (hjd_entropy_prep.cpp): one JPEG to tables + destuffed scan (Prepared), and
-// the staging of a batch of them under the layout of hjd_entropy_batch.hpp.
-// Plain C++: nothing here touches the GPU runtime.
+// the staging of a batch of them under the layout of hjd_entropy_batch.hpp,
+// with the plan of its uploads.  Plain C++: nothing here touches the GPU runtime.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -134,6 +134,30 @@ struct Staging;
 typedef int (*PlanFn)(const Staging& st, const uint8_t* data, size_t size, RawCursor& cur, int& mode,
                       uint64_t& raw_off, bool& fits, size_t data_room, uint64_t reserve);
 
+// The uploads of a staged batch as data (Staging::plan_uploads), in the order
+// they are issued.  Staging and device blob share their layout, so a header or
+// data copy has one offset for both sides.
+enum UploadKind {
+    kUploadHeader,      // staging [0, bytes) -> blob
+    kUploadData,        // a run of host-destuffed frames: staging [dst_off, + bytes) -> blob, same offset
+    kUploadRawStaged,   // a raw scan in the staging's data area at `src` -> raw area at dst_off
+    kUploadRawCaller,   // raw scans in the caller's pinned memory at address `src` -> raw area at dst_off
+};
+struct UploadCopy {
+    int kind;
+    uint64_t dst_off, src;
+    size_t bytes;
+    int first, last;    // the frames [first, last) it covers (the header: none)
+};
+struct UploadPlan {
+    std::vector<UploadCopy> copies;
+    bool pull;          // pull_kernel moves `segs` (header, then the one data run) and there are no copies
+    PullSegs segs;
+    int64_t moved;      // bytes host -> device, counted as ever: a data run in full though part of it was
+                        // pulled early, a caller span with the gaps between its scans
+    int64_t host_bytes; // scan bytes the host CPU read + wrote (a caller-pinned scan: none)
+};
+
 // The host side of one batch: the frames prepared into the owner's staging
 // memory (caps.data + data_cap() bytes: header, then the data area), and the
 // entropy header that describes them.
@@ -165,6 +189,10 @@ struct Staging {
     // (pointers into `blob`, the work arrays left null).
     int assemble(uint8_t* blob, int16_t* coefs, int64_t* block_offsets, uint32_t S, size_t recs_bytes,
                  size_t qt_bytes, EntBatchDev& d);
+    // What moves the assembled batch (H.used header bytes, the frames' scans) to the device, and how.
+    // latency: the owner is a latency decoder, whose all-host-destuffed batches are pulled;
+    // prepulled: data-area bytes of frame 0 an early pull has moved already.  `out` keeps its storage.
+    void plan_uploads(bool latency, size_t prepulled, UploadPlan& out) const;
 };
 
 }  // namespace ent

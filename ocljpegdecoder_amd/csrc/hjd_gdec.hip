@@ -106,6 +106,33 @@ int hjd::ent::stream_sub_bits(int max_frames)
     return max_frames >= 24 ? 4 * kDefaultSubBits : default_sub_bits(max_frames);
 }
 
+// The sync of the batch staged in g (g->batch_spec) and its S, which it returns
+// (g->batch_sub_bits: 0 unless a dense tier's): kDenseBitsPerBlock, kDenseTiers.
+static uint32_t choose_sync(hjd_gdec* g)
+{
+    g->batch_spec = g->spec;
+    g->batch_sub_bits = 0;
+    const uint32_t S = static_cast<uint32_t>(g->st.caps.sub_bits);
+    if (!g->spec) return S;
+    uint64_t bits = 0, blocks = 0;
+    for (const Prepared& p : g->st.frames) {
+        bits += p.data_bits;
+        blocks += static_cast<uint64_t>(p.nblocks);
+        for (const Prepared& q : p.more) {
+            bits += q.data_bits;
+            blocks += static_cast<uint64_t>(q.nblocks);
+        }
+    }
+    if (bits <= kDenseBitsPerBlock * blocks) return S;
+    g->batch_spec = false;
+    const auto& e = tuning().dense_sub_bits;   // tuning: the dense scans' S
+    constexpr size_t nt = sizeof(kDenseTiers) / sizeof(kDenseTiers[0]);
+    size_t t = 0;
+    while (t + 1 < nt && bits > kDenseTiers[t].bits_per_block * blocks) ++t;
+    const uint32_t want = e.is_set() ? static_cast<uint32_t>(e.get()) : kDenseTiers[t].sub_bits;
+    return g->batch_sub_bits = std::max(want, S);
+}
+
 // ---------------------------------------------------------------------------
 // Batch object
 // ---------------------------------------------------------------------------
@@ -174,37 +201,30 @@ int gdec_alloc(hjd_gdec* g)
 {
     const Caps& caps = g->st.caps;
     const size_t total = g->st.bytes();
+    const size_t subs = static_cast<size_t>(caps.max_subs), wgs = static_cast<size_t>(caps.max_wgs);
+    const size_t ef = kMaxScans * static_cast<size_t>(caps.max_frames);   // entropy frames
     HJD_HIP(hipSetDevice(g->device));
-    HJD_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->st.h_stage), total, hipHostMallocDefault));
-    HJD_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->h_status),
-                          4 * kMaxScans * static_cast<size_t>(caps.max_frames), hipHostMallocDefault));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_blob), total));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_entries), 8 * static_cast<size_t>(caps.max_subs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_stats), sizeof(SubStats) * static_cast<size_t>(caps.max_subs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_mids), 8 * static_cast<size_t>(caps.max_subs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_stats1), sizeof(SubStats) * static_cast<size_t>(caps.max_subs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_wentries), 8 * kWarm * static_cast<size_t>(caps.max_wgs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_linked), 4 * static_cast<size_t>(caps.max_wgs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_agg), sizeof(SubStats) * static_cast<size_t>(caps.max_wgs)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_coefs), 128 * static_cast<size_t>(caps.max_blocks)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_raw), g->st.data_cap()));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_tiles), 12 * static_cast<size_t>(caps.max_tiles)));
-    HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_steps),
-                      (static_cast<size_t>(kMaxTables) * kMaxScans * static_cast<size_t>(caps.max_frames)) << kStepBits));
+    // (a failed alloc has set the error text)
+    bool bad = g->alloc(g->st.h_stage, total, true) || g->alloc(g->h_status, 4 * ef, true) ||
+               g->alloc(g->d_blob, total) || g->alloc(g->d_entries, 8 * subs) ||
+               g->alloc(g->d_stats, sizeof(SubStats) * subs) || g->alloc(g->d_mids, 8 * subs) ||
+               g->alloc(g->d_stats1, sizeof(SubStats) * subs) || g->alloc(g->d_wentries, 8 * kWarm * wgs) ||
+               g->alloc(g->d_linked, 4 * wgs) || g->alloc(g->d_agg, sizeof(SubStats) * wgs) ||
+               g->alloc(g->d_coefs, 128 * static_cast<size_t>(caps.max_blocks)) ||
+               g->alloc(g->d_raw, g->st.data_cap()) || g->alloc(g->d_tiles, 12 * static_cast<size_t>(caps.max_tiles)) ||
+               g->alloc(g->d_steps, (kMaxTables * ef) << kStepBits);
+    // chunk functions: [entropy frame][chunks of the largest frame]
+    g->chain_fn_rows = g->spec ? static_cast<int64_t>(ef * (subs / kChainChunk + 1)) : 0;
+    const size_t fn_bytes = 4 * kLbWords * static_cast<size_t>(g->chain_fn_rows);
+    if (g->spec)
+        bad = bad || g->alloc(g->d_spec, sizeof(SpecRec) * kMaxBpm * subs) ||
+              g->alloc(g->d_cand, sizeof(CandRec) * kCandRow * subs) || g->alloc(g->d_cmap, kSlotRow * subs) ||
+              g->alloc(g->d_cslot, subs + 16) || g->alloc(g->d_chainfn, fn_bytes) ||
+              g->alloc(g->d_chain_broken, 4 * ef) || g->alloc(g->d_agg2, sizeof(SubStats) * wgs);
+    if (bad) return HJD_E_HIP;
     if (g->spec) {
-        const size_t n = static_cast<size_t>(caps.max_subs);
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_spec), sizeof(SpecRec) * kMaxBpm * n));
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cand), sizeof(CandRec) * kCandRow * n));
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cmap), kSlotRow * n));
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cslot), n + 16));
-        // chunk functions: [entropy frame][chunks of the largest frame]
-        const size_t ef = kMaxScans * static_cast<size_t>(caps.max_frames);
-        g->chain_fn_rows = static_cast<int64_t>(ef * (n / kChainChunk + 1));
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_chainfn), 4 * kLbWords * static_cast<size_t>(g->chain_fn_rows)));
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_chain_broken), 4 * ef));
         HJD_HIP(hipMemset(g->d_chain_broken, 0, 4 * ef));
-        HJD_HIP(hipMemset(g->d_chainfn, 0, 4 * kLbWords * static_cast<size_t>(g->chain_fn_rows)));
-        HJD_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_agg2), sizeof(SubStats) * static_cast<size_t>(caps.max_wgs)));
+        HJD_HIP(hipMemset(g->d_chainfn, 0, fn_bytes));
     }
     HJD_HIP(hipEventCreateWithFlags(&g->staged, hipEventDisableTiming));
     HJD_HIP(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
@@ -223,9 +243,7 @@ void gdec_early_pull(DestuffHook* h, size_t done)
     const size_t upto = done & ~static_cast<size_t>(15);
     if (upto <= c.prepulled) return;
     PullSegs segs{};
-    segs.off[0] = (g->st.caps.data + c.prepulled) / 16;   // frame 0: data_off 0
-    segs.words[0] = (upto - c.prepulled) / 16;
-    segs.n = 1;
+    segs.add(g->st.caps.data + c.prepulled, upto - c.prepulled);   // frame 0: data_off 0
     if (hipSetDevice(g->device) != hipSuccess) return;
     if (g->pending && hipStreamWaitEvent(c.stream, g->done, 0) != hipSuccess) return;
     if (launch_pull(g->st.h_stage, g->d_blob, segs, c.stream) == hipSuccess) c.prepulled = upto;
@@ -242,6 +260,7 @@ struct PixelClasses {
     uint8_t* out_base[hjd_internal::kSamplingClasses] = {};
     size_t table[hjd_internal::kSamplingClasses] = {};
     bool roi = false;
+    int out_format = 0;   // what the pixel kernels write: the decoder's, or planar bytes for the stages
 };
 
 // Pixel-kernel launch class of a sampling (parse_scan_header admits only known ones).
@@ -311,61 +330,37 @@ int write_pixel_records(hjd_gdec* g, const GdecCall& c, int out_format, bool fno
     return HJD_OK;
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------
+// The steps of gdec_issue, in its order
+// ---------------------------------------------------------------------------
 
-int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
+// The batch header at subsequence length S (Staging::assemble) with the call's
+// records in it: the pixel kernels' tables (px; px.out_format is what those
+// kernels write) and the stages'.
+int assemble_batch(hjd_gdec* g, const GdecCall& c, uint32_t S, int16_t* coefs, EntBatchDev& b, PixelClasses& px)
 {
-    HJD_HIP(hipSetDevice(g->device));
-    Staging& st = g->st;
-    const hipStream_t s = c.stream;
-    const int n = static_cast<int>(st.frames.size());
-    int16_t* coefs = c.coefs_out ? c.coefs_out : g->d_coefs;
-    // the sync and S of this batch (kDenseBitsPerBlock, kDenseTiers)
-    bool spec = g->spec;
-    g->batch_sub_bits = 0;
-    if (spec) {
-        uint64_t bits = 0, blocks = 0;
-        for (const Prepared& p : st.frames) {
-            bits += p.data_bits;
-            blocks += static_cast<uint64_t>(p.nblocks);
-            for (const Prepared& q : p.more) {
-                bits += q.data_bits;
-                blocks += static_cast<uint64_t>(q.nblocks);
-            }
-        }
-        if (bits > kDenseBitsPerBlock * blocks) {
-            spec = false;
-            const auto& e = tuning().dense_sub_bits;   // tuning: the dense scans' S
-            constexpr size_t nt = sizeof(kDenseTiers) / sizeof(kDenseTiers[0]);
-            size_t t = 0;
-            while (t + 1 < nt && bits > kDenseTiers[t].bits_per_block * blocks) ++t;
-            const uint32_t want = e.is_set() ? static_cast<uint32_t>(e.get()) : kDenseTiers[t].sub_bits;
-            g->batch_sub_bits = std::max(want, static_cast<uint32_t>(g->st.caps.sub_bits));
-        }
-    }
-    g->batch_spec = spec;
-    const uint32_t S = g->batch_sub_bits ? g->batch_sub_bits : static_cast<uint32_t>(st.caps.sub_bits);
-    int pix_format = g->out_format;
-    bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(pix_format) != 0;
+    const int n = static_cast<int>(g->st.frames.size());
+    px.out_format = g->out_format;
+    bool fnorm = c.d_outs && hjd_internal::out_format_float_bytes(px.out_format) != 0;
     size_t recs_bytes = c.d_outs ? pixel_tables_bytes(n, c.rois != nullptr, fnorm) : 0;
     if (c.post) {   // the pixel kernels write planar bytes (the crops); the last stage the decoder's format
-        pix_format = HJD_OUT_RGB_PLANAR;
+        px.out_format = HJD_OUT_RGB_PLANAR;
         fnorm = false;
         recs_bytes = c.post->recs_bytes;
     }
-    EntBatchDev b;
-    int rc = st.assemble(g->d_blob, coefs, c.block_offsets, S, recs_bytes,
-                         c.d_outs ? 192 * 4 * static_cast<size_t>(n) : 0, b);
-    if (rc) return rc;
-    PixelClasses px;
-    if (c.d_outs) {
-        rc = write_pixel_records(g, c, pix_format, fnorm, px);
-        if (rc) return rc;
-        if (c.post) {
-            rc = post_write_records(g, *c.post, n);
-            if (rc) return rc;
-        }
-    }
+    int rc = g->st.assemble(g->d_blob, coefs, c.block_offsets, S, recs_bytes,
+                            c.d_outs ? 192 * 4 * static_cast<size_t>(n) : 0, b);
+    if (rc || !c.d_outs) return rc;
+    rc = write_pixel_records(g, c, px.out_format, fnorm, px);
+    if (rc || !c.post) return rc;
+    return post_write_records(g, *c.post, n);
+}
+
+// The decoder's work arrays in b, for the sync choose_sync picked.  The
+// look-back chain kernel's launch takes the next 24-bit tag: true when the tag
+// started over at 1 (issue_uploads then clears the words).
+bool bind_work_arrays(hjd_gdec* g, EntBatchDev& b)
+{
     b.entries = g->d_entries;
     b.stats = g->d_stats;
     b.mids = g->d_mids;
@@ -381,24 +376,28 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     g->batch_lookback = false;
     g->batch_chain_chunks = b.chain_chunks;
     g->batch_lead = 0;
-    bool epoch_wrapped = false;
-    if (spec) {
-        b.spec = g->d_spec;
-        b.cand = g->d_cand;
-        b.cmap = g->d_cmap;
-        b.cslot = g->d_cslot;
-        b.spec_lead = spec_lead_bits(g->lead_step);
-        g->batch_lead = b.spec_lead;
-        if (static_cast<int64_t>(b.chain_chunks) * b.nframes <= g->chain_fn_rows) {
-            b.chainfn = g->d_chainfn;
-            b.chain_broken = g->d_chain_broken;
-            b.agg2 = g->d_agg2;
-            epoch_wrapped = g->chain_epoch >= 0xFFFFFFu;
-            g->chain_epoch = g->chain_epoch % 0xFFFFFFu + 1u;   // 1 .. 2^24 - 1
-            b.chain_epoch = g->chain_epoch;
-            g->batch_lookback = true;
-        }
-    }
+    if (!g->batch_spec) return false;
+    b.spec = g->d_spec;
+    b.cand = g->d_cand;
+    b.cmap = g->d_cmap;
+    b.cslot = g->d_cslot;
+    b.spec_lead = spec_lead_bits(g->lead_step);
+    g->batch_lead = b.spec_lead;
+    if (static_cast<int64_t>(b.chain_chunks) * b.nframes > g->chain_fn_rows) return false;
+    b.chainfn = g->d_chainfn;
+    b.chain_broken = g->d_chain_broken;
+    b.agg2 = g->d_agg2;
+    const bool wrapped = g->chain_epoch >= 0xFFFFFFu;
+    g->chain_epoch = g->chain_epoch % 0xFFFFFFu + 1u;   // 1 .. 2^24 - 1
+    b.chain_epoch = g->chain_epoch;
+    g->batch_lookback = true;
+    return wrapped;
+}
+
+// Everything the kernels wait for, on s: the previous call, the clearing of
+// the look-back words at the tag's wrap, then the plan's uploads as it lists them.
+int issue_uploads(hjd_gdec* g, const UploadPlan& plan, bool epoch_wrapped, hipStream_t s)
+{
     // the device buffers are reused: order this call after the previous one
     // (which may have been issued on another stream)
     if (g->pending) HJD_HIP(hipStreamWaitEvent(s, g->done, 0));
@@ -410,155 +409,123 @@ int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
     // (one memset per 16.7 M launches).
     if (epoch_wrapped)
         HJD_HIP(hipMemsetAsync(g->d_chainfn, 0, 4 * kLbWords * static_cast<size_t>(g->chain_fn_rows), s));
-    bool pull = g->spec;   // latency decoders, every scan host-destuffed (one data run)
-    for (const Prepared& p : g->st.frames) pull = pull && p.destuff == kDestuffHost;
-    PullSegs segs{};
-    if (pull) {
-        segs.off[0] = 0;
-        segs.words[0] = g->st.H.used / 16;
-        segs.n = 1;
-    } else {
-        HJD_HIP(hipMemcpyAsync(g->d_blob, g->st.h_stage, g->st.H.used, hipMemcpyHostToDevice, s));
-    }
-    // scan bytes: runs of consecutive frames staged the same way move in one copy
-    // (host-destuffed -> data area; raw in staging -> raw area); raw bytes in the
-    // caller's pinned memory go straight from there to the raw area.
-    int64_t moved = static_cast<int64_t>(g->st.H.used), host_bytes = 0;
-    std::vector<void*> bd, bs;          // caller-pinned raw scans: one batched DMA submission
-    std::vector<size_t> bn;
-    std::vector<std::pair<int, int>> bf;   // frames [first, last) each copy covers
-    for (int i = 0; i < n;) {
-        const Prepared& p = g->st.frames[i];
-        const size_t len = p.destuff == kDestuffHost ? p.data_bits / 8 : p.raw_len;
-        host_bytes += p.destuff == kDestuffHost ? static_cast<int64_t>(p.raw_len) + static_cast<int64_t>(len)
-                    : p.destuff == kDestuffFromStaging ? 2 * static_cast<int64_t>(len) : 0;
-        if (p.destuff == kDestuffFromCaller) {
-            // a run of scans placed at their distance in the caller's memory moves in one DMA
-            int j = i + 1;
-            size_t span = len;
-            while (j < n && g->st.frames[j].destuff == kDestuffFromCaller && g->st.frames[j].raw_src > p.raw_src &&
-                   g->st.frames[j].raw_off - p.raw_off == static_cast<uint64_t>(g->st.frames[j].raw_src - p.raw_src)) {
-                span = static_cast<size_t>(g->st.frames[j].raw_src - p.raw_src) + g->st.frames[j].raw_len;
-                ++j;
-            }
-            bd.push_back(g->d_raw + p.raw_off);
-            bs.push_back(const_cast<uint8_t*>(p.raw_src));
-            bn.push_back(span);
-            bf.emplace_back(i, j);
-            moved += static_cast<int64_t>(span);
-            i = j;
+    if (plan.pull) HJD_HIP(launch_pull(g->st.h_stage, g->d_blob, plan.segs, s));   // (and no copies)
+    for (const UploadCopy& u : plan.copies) {
+        uint8_t* dst = (u.kind == kUploadHeader || u.kind == kUploadData ? g->d_blob : g->d_raw) + u.dst_off;
+        if (u.kind != kUploadRawCaller) {
+            HJD_HIP(hipMemcpyAsync(dst, g->st.h_stage + u.src, u.bytes, hipMemcpyHostToDevice, s));
             continue;
         }
-        if (p.destuff == kDestuffFromStaging) {
-            HJD_HIP(hipMemcpyAsync(g->d_raw + p.raw_off, g->st.h_stage + g->st.caps.data + p.data_off, len,
-                                   hipMemcpyHostToDevice, s));
-            moved += static_cast<int64_t>(len);
-            ++i;
+        // (hipMemcpyBatchAsync would submit the caller's spans at once, but the HIP runtime
+        // this library shares with PyTorch -- DESIGN.md s8 -- predates it)
+        if (hipMemcpyAsync(dst, reinterpret_cast<const void*>(u.src), u.bytes, hipMemcpyHostToDevice, s) == hipSuccess)
             continue;
-        }
-        int j = i + 1;                   // host-destuffed: one copy per run of frames (all their scans)
-        size_t hi = p.data_end();
-        for (const Prepared& q : p.more) host_bytes += static_cast<int64_t>(q.data_bits / 8);
-        while (j < n && g->st.frames[j].destuff == kDestuffHost) {
-            const Prepared& q = g->st.frames[j];
-            hi = q.data_end();
-            host_bytes += static_cast<int64_t>(q.raw_len) + q.data_bits / 8;
-            for (const Prepared& r : q.more) host_bytes += static_cast<int64_t>(r.data_bits / 8);
-            ++j;
-        }
-        uint8_t* dst = g->d_blob + g->st.caps.data + p.data_off;
-        if (pull && segs.n < kPullSegs) {
-            const size_t pre = i == 0 ? c.prepulled : 0;   // (frame 0 starts the data area)
-            segs.off[segs.n] = (g->st.caps.data + p.data_off + pre) / 16;
-            segs.words[segs.n] = (hi - p.data_off - pre + 15) / 16;
-            ++segs.n;
-        } else {
-            HJD_HIP(hipMemcpyAsync(dst, g->st.h_stage + g->st.caps.data + p.data_off, hi - p.data_off, hipMemcpyHostToDevice, s));
-        }
-        moved += static_cast<int64_t>(hi - p.data_off);
-        i = j;
-    }
-    if (pull) {
-        HJD_HIP(launch_pull(g->st.h_stage, g->d_blob, segs, s));
-    }
-    // (hipMemcpyBatchAsync would submit these at once, but the HIP runtime this
-    // library shares with PyTorch -- DESIGN.md s8 -- predates it)
-    for (size_t k = 0; k < bd.size(); ++k) {
-        if (hipMemcpyAsync(bd[k], bs[k], bn[k], hipMemcpyHostToDevice, s) == hipSuccess) continue;
         // A merged span can cross from one pinned allocation into another (the
         // caller's buffers merely lie close together), which the DMA rejects
         // before queueing anything: copy those scans one by one.
         (void)hipGetLastError();
-        if (bf[k].second - bf[k].first < 2)
-            return set_error(HJD_E_HIP, "hipMemcpyAsync of a pinned scan (%zu bytes) failed", bn[k]);
-        for (int f = bf[k].first; f < bf[k].second; ++f) {
+        if (u.last - u.first < 2)
+            return set_error(HJD_E_HIP, "hipMemcpyAsync of a pinned scan (%zu bytes) failed", u.bytes);
+        for (int f = u.first; f < u.last; ++f) {
             const Prepared& q = g->st.frames[f];
             HJD_HIP(hipMemcpyAsync(g->d_raw + q.raw_off, const_cast<uint8_t*>(q.raw_src), q.raw_len,
                                    hipMemcpyHostToDevice, s));
         }
     }
-    g->last_h2d = moved;
-    g->last_host_scan_bytes = host_bytes;
+    g->last_h2d = plan.moved;
+    g->last_host_scan_bytes = plan.host_bytes;
     // (pulled: the staging is free when `done` fires -- an event between the
     // pull and the first entropy kernel delayed that kernel by ~6 us, and a
     // latency decoder's next call waits for `done` anyway)
-    if (!pull) HJD_HIP(hipEventRecord(g->staged, s));
-    g->staged_by_done = pull;
+    if (!plan.pull) HJD_HIP(hipEventRecord(g->staged, s));
+    g->staged_by_done = plan.pull;
     g->pending = true;
-    // a multi-scan file's non-interleaved scans leave its MCU-padding blocks
-    // uncoded: they must read as zeros (as the host decoder's)
-    {
-        size_t first = 0;
-        for (int i = 0; i < n; ++i) {
-            const Prepared& p = g->st.frames[i];
-            if (!p.more.empty())
-                HJD_HIP(hipMemsetAsync(coefs + first * 64, 0, static_cast<size_t>(p.out_blocks) * 128, s));
-            first += static_cast<size_t>(p.out_blocks);
-        }
+    return HJD_OK;
+}
+
+// A multi-scan file's non-interleaved scans leave its MCU-padding blocks
+// uncoded: they must read as zeros (as the host decoder's).
+int zero_multiscan_padding(const Staging& st, int16_t* coefs, hipStream_t s)
+{
+    size_t first = 0;
+    for (const Prepared& p : st.frames) {
+        if (!p.more.empty()) HJD_HIP(hipMemsetAsync(coefs + first * 64, 0, static_cast<size_t>(p.out_blocks) * 128, s));
+        first += static_cast<size_t>(p.out_blocks);
     }
-    rc = launch_entropy(b, g->st.h_stage + g->st.H.tabs, g->steps_tabs, s);
-    if (rc) return rc;
-    if (c.d_outs) {
-        for (int sidx = 0; sidx < hjd_internal::kSamplingClasses; ++sidx) {
-            if (!px.nrec[sidx]) continue;
-            hjd_internal::DecodeLaunch l;   // int16 input, HJD_KERNEL_AUTO, the default grid
-            l.sampling = kClassSampling[sidx];
-            l.out_format = pix_format;
-            l.scale = g->scale;
-            l.roi = px.roi;
-            l.tasks = px.tasks[sidx];
-            l.device = g->device;
-            l.d_coefs = coefs;
-            l.d_qt_nat = reinterpret_cast<const int32_t*>(g->d_blob + g->st.H.qt);
-            l.d_frames = reinterpret_cast<const FrameRecord*>(g->d_blob + g->st.H.recs + px.table[sidx]);
-            l.nframes = px.nrec[sidx];
-            l.d_out = px.out_base[sidx];
-            l.stream = s;
-            rc = hjd_internal::launch_decode(l);
-            if (rc) return rc;
-        }
-        if (c.post) {   // behind the pixel kernels; `done` (below) covers them
-            rc = post_launch(g, *c.post, n, s);
-            if (rc) return rc;
-        }
+    return HJD_OK;
+}
+
+// One pixel-kernel launch per sampling class the batch has, then the call's stages.
+int launch_pixels(hjd_gdec* g, const GdecCall& c, const PixelClasses& px, const int16_t* coefs, hipStream_t s)
+{
+    for (int sidx = 0; sidx < hjd_internal::kSamplingClasses; ++sidx) {
+        if (!px.nrec[sidx]) continue;
+        hjd_internal::DecodeLaunch l;   // int16 input, HJD_KERNEL_AUTO, the default grid
+        l.sampling = kClassSampling[sidx];
+        l.out_format = px.out_format;
+        l.scale = g->scale;
+        l.roi = px.roi;
+        l.tasks = px.tasks[sidx];
+        l.device = g->device;
+        l.d_coefs = coefs;
+        l.d_qt_nat = reinterpret_cast<const int32_t*>(g->d_blob + g->st.H.qt);
+        l.d_frames = reinterpret_cast<const FrameRecord*>(g->d_blob + g->st.H.recs + px.table[sidx]);
+        l.nframes = px.nrec[sidx];
+        l.d_out = px.out_base[sidx];
+        l.stream = s;
+        const int rc = hjd_internal::launch_decode(l);
+        if (rc) return rc;
     }
-    if (c.host && c.d_outs) {   // D2H sink: pixels of host-output frames back to the caller's memory
-        const HostCopy* host = c.host;
-        for (int i = 0; i < n; ++i) {
-            if (!host[i].host) continue;
-            // planar: the planes are contiguous at pitch * height on both
-            // sides, so one copy of 3 * height rows moves all three
-            HJD_HIP(hipMemcpy2DAsync(
-                host[i].host, static_cast<size_t>(host[i].host_pitch), c.d_outs[i], static_cast<size_t>(c.pitches[i]),
-                static_cast<size_t>(host[i].width) * hjd_internal::out_format_row_bytes(g->out_format),
-                static_cast<size_t>(hjd_internal::out_format_rows(g->out_format, host[i].height)),
-                hipMemcpyDeviceToHost, s));
-        }
+    // behind the pixel kernels; `done` covers them
+    return c.post ? post_launch(g, *c.post, static_cast<int>(g->st.frames.size()), s) : HJD_OK;
+}
+
+// What goes back to the host: the pixels of host-output frames (the D2H sink)
+// to the caller's memory, and the status words unless the write kernel delivers them.
+int copy_back(hjd_gdec* g, const GdecCall& c, const EntBatchDev& b, hipStream_t s)
+{
+    for (size_t i = 0; c.host && c.d_outs && i < g->st.frames.size(); ++i) {
+        const HostCopy& h = c.host[i];
+        if (!h.host) continue;
+        // planar: the planes are contiguous at pitch * height on both
+        // sides, so one copy of 3 * height rows moves all three
+        HJD_HIP(hipMemcpy2DAsync(h.host, static_cast<size_t>(h.host_pitch), c.d_outs[i],
+                                 static_cast<size_t>(c.pitches[i]),
+                                 static_cast<size_t>(h.width) * hjd_internal::out_format_row_bytes(g->out_format),
+                                 static_cast<size_t>(hjd_internal::out_format_rows(g->out_format, h.height)),
+                                 hipMemcpyDeviceToHost, s));
     }
     if (!b.host_status)
         HJD_HIP(hipMemcpyAsync(g->h_status, b.status, 4 * static_cast<size_t>(b.nframes), hipMemcpyDeviceToHost, s));
+    return HJD_OK;
+}
+
+}  // namespace
+
+int hjd::ent::gdec_issue(hjd_gdec* g, GdecCall& c)
+{
+    HJD_HIP(hipSetDevice(g->device));
+    const hipStream_t s = c.stream;
+    int16_t* coefs = c.coefs_out ? c.coefs_out : g->d_coefs;
+    const uint32_t S = choose_sync(g);
+    EntBatchDev b;
+    PixelClasses px;
+    int rc = assemble_batch(g, c, S, coefs, b, px);
+    if (rc) return rc;
+    const bool epoch_wrapped = bind_work_arrays(g, b);
+    g->st.plan_uploads(g->spec, c.prepulled, g->uploads);
+    rc = issue_uploads(g, g->uploads, epoch_wrapped, s);
+    if (rc) return rc;
+    rc = zero_multiscan_padding(g->st, coefs, s);
+    if (rc) return rc;
+    rc = launch_entropy(b, g->st.h_stage + g->st.H.tabs, g->steps_tabs, s);
+    if (rc) return rc;
+    if (c.d_outs) rc = launch_pixels(g, c, px, coefs, s);
+    if (rc) return rc;
+    rc = copy_back(g, c, b, s);
+    if (rc) return rc;
     HJD_HIP(hipEventRecord(g->done, s));
-    g->nframes_issued = n;
+    g->nframes_issued = static_cast<int>(g->st.frames.size());
     return HJD_OK;
 }
 
@@ -703,13 +670,7 @@ int hjd_gdec_destroy(hjd_gdec* g)
                 g->host_us[2] / g->host_calls);
     (void)hipSetDevice(g->device);
     if (g->done) (void)hipEventSynchronize(g->done);
-    if (g->st.h_stage) (void)hipHostFree(g->st.h_stage);
-    if (g->h_status) (void)hipHostFree(g->h_status);
-    void* dev[] = {g->d_blob, g->d_entries, g->d_stats, g->d_mids, g->d_stats1, g->d_wentries, g->d_linked, g->d_agg,
-                   g->d_coefs, g->d_raw, g->d_tiles, g->d_spec, g->d_cand, g->d_cmap, g->d_cslot,
-                   g->d_steps, g->d_chainfn, g->d_chain_broken, g->d_agg2, g->d_crops};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
+    while (!g->owned.empty()) g->release(g->owned.front().first);   // in the order they were allocated
     if (g->staged) (void)hipEventDestroy(g->staged);
     if (g->done) (void)hipEventDestroy(g->done);
     delete g;

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <utility>
 #include <vector>
 
 #include "hjd.h"
@@ -16,6 +17,28 @@ struct hjd_gdec {
     hjd_ctx* ctx = nullptr;
     int device = 0, num_cu = 256;
     hjd::ent::Staging st;               // the host side of the batch; st.h_stage is pinned
+    hjd::ent::UploadPlan uploads;       // of the call being issued (kept for its storage: no allocation per call)
+    // Every buffer of the decoder (st.h_stage and those below) comes from alloc(), which notes it here
+    // (true: pinned host memory), so hjd_gdec_destroy frees this list and names none of them;
+    // release() frees one early.
+    std::vector<std::pair<void*, bool>> owned;
+    template <class T> int alloc(T*& p, size_t bytes, bool host = false)
+    {
+        void* v = nullptr;
+        HJD_HIP(host ? hipHostMalloc(&v, bytes, hipHostMallocDefault) : hipMalloc(&v, bytes));
+        owned.emplace_back(v, host);
+        p = static_cast<T*>(v);
+        return HJD_OK;
+    }
+    void release(void* p)
+    {
+        for (size_t k = 0; k < owned.size(); ++k)
+            if (owned[k].first == p) {
+                (void)(owned[k].second ? hipHostFree(p) : hipFree(p));
+                owned.erase(owned.begin() + static_cast<ptrdiff_t>(k));
+                return;
+            }
+    }
     uint8_t* d_blob = nullptr;
     uint64_t* d_entries = nullptr;
     hjd::ent::SubStats* d_stats = nullptr;

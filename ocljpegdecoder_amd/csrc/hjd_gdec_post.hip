@@ -53,12 +53,11 @@ int grow_scratch(hjd_gdec* g, std::initializer_list<Region*> regions, const char
     if (need > g->crops_bytes) {
         HJD_HIP(hipSetDevice(g->device));
         if (g->pending) HJD_HIP(hipEventSynchronize(g->done));
-        if (g->d_crops) (void)hipFree(g->d_crops);
+        g->release(g->d_crops);
         g->d_crops = nullptr;
         g->crops_bytes = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g->d_crops), need) != hipSuccess) {
+        if (g->alloc(g->d_crops, need)) {
             (void)hipGetLastError();
-            g->d_crops = nullptr;
             return set_error(HJD_E_NOMEM, "the %s of this call need %zu bytes of device memory", what, need);
         }
         g->crops_bytes = need;

@@ -472,3 +472,52 @@ def test_pinned_arena_stream(hjd, ctx, tuning):
         exp = O.decode_q16(ref, info.qt, info.width, info.height, info.sampling)
         np.testing.assert_array_equal(o.cpu().numpy().view(np.uint32), exp)
     del arena
+
+
+def _mixed_files():
+    """Two 4:2:0 files, a 4:4:4 one with a restart interval and a grayscale one,
+    32 x 32 (tests/jpeg_writer.py from synthetic coefficients)."""
+    import jpeg_writer as JW
+    from test_jpeg_host_pair import FACTORS, _huff_src
+    src, out = _huff_src(), []
+    for k, (s, fac, dri) in enumerate(((1, FACTORS[1], 0), (1, FACTORS[1], 0), (0, FACTORS[0], 3), (4, [(1, 1)], 0))):
+        coefs, qt = O.synthetic_coefs(32, 32, s, seed=700 + k)
+        out.append(JW.encode_frame(coefs, 32, 32, fac, qt, src, restart_interval=dri))
+    return out
+
+
+@pytest.mark.parametrize("policy", ["auto", "device"])
+def test_mixed_pinned_and_pageable_batch(hjd, ctx, tuning, policy):
+    """One batch with every kind of upload: files 0 and 2 in one pinned arena
+    (raw from the caller's memory, copied last), files 1 and 3 pageable bytes
+    (destuffed on the host under `auto`, raw through the staging under
+    `device`).  The pixels are those of the four files as pageable bytes under
+    `host`, and the host's scan bytes are the sum of what each file costs when
+    decoded alone in the same form under the same policy."""
+    import torch
+    datas = _mixed_files()
+    infos = [hjd.parse(d) for d in datas]
+    assert [i.sampling for i in infos] == [hjd.YUV420, hjd.YUV420, hjd.YUV444, hjd.GRAY]
+
+    def decode(inputs, which):
+        outs = [torch.full((infos[i].height, infos[i].width), -1, dtype=torch.int32, device="cuda") for i in which]
+        with hjd.GpuDecoder(ctx, len(datas), sum(map(len, datas)) + 4096, sum(i.nblocks for i in infos)) as gd:
+            gd.decode(inputs, outs)
+            host_bytes = gd.last_bytes()["host_scan_bytes"]
+            assert all(s & ~1 == 0 for s in gd.sync())
+        return [o.cpu().numpy() for o in outs], host_bytes
+
+    tuning("HJD_DESTUFF", "host")
+    ref, _ = decode(datas, range(4))
+    tuning("HJD_DESTUFF", policy)
+    gap = bytes(24)
+    arena = hjd.pinned_bytes(gap[:5] + datas[0] + gap + datas[2] + gap)
+    o0, o2 = 5, 5 + len(datas[0]) + len(gap)
+    mixed = [arena[o0:o0 + len(datas[0])], datas[1], arena[o2:o2 + len(datas[2])], datas[3]]
+    got, host_bytes = decode(mixed, range(4))
+    for g, r in zip(got, ref):
+        np.testing.assert_array_equal(g, r)
+    alone = [decode([m], [i])[1] for i, m in enumerate(mixed)]
+    assert alone[0] == alone[2] == 0 and alone[1] > 0 and alone[3] > 0
+    assert host_bytes == sum(alone)
+    del arena
