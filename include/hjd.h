@@ -644,6 +644,96 @@ int hjd_warp_set_normalize(hjd_warp* w, const float a[3], const float b[3]);
 int hjd_warp_launch(hjd_warp* w, void* stream);
 int hjd_warp_destroy(hjd_warp* w);
 
+/*
+ * Colour (extension; the reference has none): n planar uint8 RGB images, each
+ * of its own size, each through its own affine colour map in ONE launch (two
+ * where a map reads the image's means): brightness, contrast, saturation, a
+ * hue rotation, grayscale and inversion -- the photometric half of ColorJitter
+ * / RandomGrayscale -- composed into one record per image.
+ *
+ * Source: as the resize's -- three uint8 planes R, G, B of w x h, rows
+ * src_pitch bytes apart, planes src_pitch * h apart; any pointer and any
+ * src_pitch >= w; both dimensions in 1..16384.  Output: the same w x h, as
+ * hjd_orient's: out_format HJD_OUT_RGB_PLANAR (the bytes u8),
+ * HJD_OUT_RGB_PLANAR_F16 or _F32 (fma((float)u8, a[c], b[c]),
+ * hjd_color_set_normalize, default a = 1, b = 0); every item its own dst and
+ * dst_pitch, multiples of the element size, dst_pitch >= w x the element size;
+ * planes dst_pitch * h apart.  One dword is read per plane and four pixels
+ * where src and src_pitch are multiples of 4 and the four lie inside the row,
+ * and one dword / dwordx2 / dwordx4 written where dst and dst_pitch are
+ * multiples of 4 elements and w of 4; guarded byte loads / element stores
+ * elsewhere.  Nothing outside the image's own elements is written.
+ *
+ * Definition (exact, integer).  A record is 21 int32: m[9], p[9], t[3].  m and
+ * p are row-major 3 x 3 matrices, output channel x input channel in the order
+ * R, G, B, in Q12 (4096 is 1.0), every entry in -32767..32767
+ * (HJD_COLOR_MAX_COEF); t is in Q12 grey levels, |t| <= 2^23
+ * (HJD_COLOR_MAX_OFFSET).  For an image of w x h, N = w * h, pixel (r, g, b):
+ *     S_k  = the sum of channel k's bytes over the image           (exact, < 2^36)
+ *     mq_k = (S_k * 256 + (N >> 1)) / N                            (floor: the mean in Q8)
+ *     T_c  = t[c] + ((p[c][0] mq_0 + p[c][1] mq_1 + p[c][2] mq_2 + 128) >> 8)
+ *     u8_c = clamp((m[c][0] r + m[c][1] g + m[c][2] b + T_c + 2048) >> 12, 0, 255)
+ * with arithmetic (flooring) shifts; T_c in 64 bits, once per image.  Every
+ * product of the last line fits a 24-bit multiply (|m| < 2^15, a byte < 2^8)
+ * and the line fits int32: |m x| sums to at most 3 * 32767 * 255 < 2^25,
+ * |T_c| <= 2^23 + (3 * 32767 * 65280 + 128) / 256 < 2^23 + 2^25.  The float
+ * formats are fma((float)u8, a[c], b[c]) of those bytes.
+ *
+ * Laws.  m = 4096 I with p = t = 0 is a byte-for-byte copy; m = -4096 I with
+ * t = 255 * 4096 is the inverse 255 - x; a record with p = 0 never reads the
+ * sums (and its launch has no summing kernel).
+ *
+ * Error bound.  Against the real-valued map of the integer record,
+ * y_c = (m[c] . x + p[c] . xbar) / 4096 + t[c] / 4096 with xbar = S / N, u8 is
+ * within
+ *     0.5 + 2^-13 + (sum over k of |p[c][k]| / 4096) * 2^-9
+ * of clamp(y_c, 0, 255): mq_k / 256 is within 2^-9 of xbar_k (a rounding to
+ * nearest in Q8), which p scales; the shift by 8 rounds T_c to nearest in Q12,
+ * half a unit, 2^-13 grey level; the last shift rounds to nearest, 0.5; and the
+ * clamp commutes with that rounding.  Where m, p, t are real coefficients
+ * rounded to nearest in Q12, add (3 * 255 + 3 * 255 + 1) * 2^-13.
+ *
+ * What it leaves out.  The map is composed without clamping in between: an
+ * image library that clamps after each operation agrees only while no
+ * intermediate leaves 0..255.  A hue change is a rotation about the grey axis
+ * in YIQ, not an HSV shift.  Operations that are not affine in RGB (posterize,
+ * solarize, gamma, equalize) are not records.
+ *
+ * In place: for HJD_OUT_RGB_PLANAR an item with dst == src and dst_pitch ==
+ * src_pitch is legal -- a thread reads its four pixels before it writes them
+ * and the sums are taken by an earlier launch.  Any other overlap of an output
+ * with a source or another output is the caller's error; it is not looked for.
+ * An object whose records read the sums owns a table of partial sums (n x 256
+ * x 3 uint32, allocated at create, HJD_E_NOMEM if that fails) which all its
+ * launches share: the caller orders them (the same stream, or events).
+ */
+#define HJD_COLOR_MAX_COEF 32767
+#define HJD_COLOR_MAX_OFFSET (1 << 23)
+typedef struct hjd_color_item {
+    const void* src;   /* device: plane R of the source */
+    void* dst;         /* device: plane R of the output */
+    int32_t w, h, src_pitch, dst_pitch;
+    int32_t m[9], p[9], t[3];
+    int32_t reserved;   /* 0 */
+} hjd_color_item;       /* 120 bytes */
+typedef struct hjd_color hjd_color;
+/* Validates what hjd_color_create would take.  HJD_E_INVALID (with a message)
+ * for n outside 1..2^20, a NULL items / src / dst, a dimension outside
+ * 1..16384, src_pitch < w, a bad dst_pitch or dst alignment, an entry of m or
+ * p outside +-32767, |t| > 2^23, a non-zero reserved and a non-planar or
+ * unknown format.  Host only: needs no device. */
+int hjd_color_check(const hjd_color_item* items, int n, int out_format);
+/* Validates and uploads the item table (synchronously). */
+int hjd_color_create(hjd_ctx* ctx, const hjd_color_item* items, int n, int out_format, hjd_color** out);
+/* The float formats' constants for the launches that follow (an enqueued
+ * launch keeps its own).  HJD_E_INVALID for non-finite constants and for a
+ * byte-format object. */
+int hjd_color_set_normalize(hjd_color* c, const float a[3], const float b[3]);
+/* Enqueue the colour maps of all n items on `stream` (asynchronous; one
+ * kernel, or two where a record's p is not 0). */
+int hjd_color_launch(hjd_color* c, void* stream);
+int hjd_color_destroy(hjd_color* c);
+
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */
 int hjd_idct_blocks(hjd_ctx* ctx, const int32_t* d_in, int32_t* d_out, int64_t nblocks, void* stream);

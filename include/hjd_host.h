@@ -310,6 +310,32 @@ int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, c
 int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
                            const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
                            int out_w, int out_h, int32_t out_pitch, void* stream);
+/* hjd_gdec_decode_resized_oriented / hjd_gdec_decode_warped with a colour
+ * record per frame (include/hjd.h hjd_color_item defines the 21 words m[9],
+ * p[9], t[3] and the map): image i of the batch is color(resize(orient(decode)))
+ * or color(warp(decode)), the means of a record with p != 0 being those of the
+ * resized or warped image.  orientations may be NULL in both (all 1).
+ *
+ * Built as that composition: the resize or warp launch writes planar bytes
+ * (HJD_OUT_RGB_PLANAR) into one more region of the decoder's grow-only scratch,
+ * laid out as one batch (pitch out_w rounded up to 4, images 3 * pitch * out_h
+ * apart), and the colour launch reads that region and writes d_out in the
+ * decoder's format with the decoder's constants.  Where a record's p is not 0
+ * the table of partial sums lies in the same scratch and the summing kernel
+ * runs between the two.  A call whose records are all the identity (m = 4096 I,
+ * p = t = 0) is exactly the call without colours: no region, no launch.
+ * Everything that can refuse the call -- all that the call without colours
+ * refuses, a NULL colors, an entry of m or p outside +-32767 or |t| > 2^23
+ * (HJD_E_INVALID naming the frame) -- is checked before anything is staged,
+ * allocated or enqueued. */
+int hjd_gdec_decode_resized_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                  const hjd_rect* rois, const int32_t* orientations, const int32_t* flags,
+                                  const int32_t (*colors)[21], void* d_out, int out_w, int out_h, int32_t out_pitch,
+                                  int filter, void* stream);
+int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                 const int32_t (*m)[6], const int32_t* orientations, const int32_t* flags,
+                                 const uint32_t* fills, const int32_t (*colors)[21], void* d_out, int out_w, int out_h,
+                                 int32_t out_pitch, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

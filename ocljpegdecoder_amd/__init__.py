@@ -32,6 +32,9 @@ from .backend import (  # noqa: E402
     YUV444,
     autotune_cache_clear,
     block_components,
+    Color,
+    COLOR_IDENTITY,
+    color_matrix,
     Context,
     cpu_share,
     debug_tuning,
@@ -77,5 +80,6 @@ __all__ = [
     "OUT_RGB_PLANAR_F16", "OUT_RGB_PLANAR_F32", "Resize", "RESIZE_FLIP_H", "RESIZE_BILINEAR", "RESIZE_TRIANGLE_AA", "resize_scale",
     "Orient", "oriented_roi", "oriented_size", "exif_orientation",
     "Warp", "WARP_REPLICATE", "warp_roi", "warp_orient", "warp_xform",
+    "Color", "COLOR_IDENTITY", "color_matrix",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

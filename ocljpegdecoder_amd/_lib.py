@@ -66,6 +66,17 @@ class HjdWarpItem(ctypes.Structure):
 assert ctypes.sizeof(HjdWarpItem) == 64
 
 
+class HjdColorItem(ctypes.Structure):
+    """struct hjd_color_item (include/hjd.h): one image of a colour launch."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("w", "h", "src_pitch", "dst_pitch")] + \
+               [("m", ctypes.c_int32 * 9), ("p", ctypes.c_int32 * 9), ("t", ctypes.c_int32 * 3),
+                ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(HjdColorItem) == 120
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -179,6 +190,13 @@ SIGNATURES = {
     "hjd_warp_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hjd_debug_warp_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "hjd_warp_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_color_check": (ctypes.c_int, [ctypes.POINTER(HjdColorItem), ctypes.c_int, ctypes.c_int]),
+    "hjd_color_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdColorItem), ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_color_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                               ctypes.POINTER(ctypes.c_float)]),
+    "hjd_color_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_color_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
     "hjd_debug_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -288,6 +306,14 @@ def _bind_host(lib):
         "hjd_gdec_decode_warped": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
                                                   ctypes.c_int, ctypes.POINTER(ctypes.c_int32 * 6), c_i32p, c_i32p,
                                                   c_u32p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp]),
+        "hjd_gdec_decode_resized_color": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                         ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, c_i32p,
+                                                         ctypes.POINTER(ctypes.c_int32 * 21), vp, ctypes.c_int,
+                                                         ctypes.c_int, ctypes.c_int32, ctypes.c_int, vp]),
+        "hjd_gdec_decode_warped_color": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                        ctypes.c_int, ctypes.POINTER(ctypes.c_int32 * 6), c_i32p,
+                                                        c_i32p, c_u32p, ctypes.POINTER(ctypes.c_int32 * 21), vp,
+                                                        ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -724,6 +724,174 @@ def _warp_flags(replicate, n):
     return [WARP_REPLICATE if replicate else 0] * n
 
 
+COLOR_IDENTITY = (4096, 0, 0, 0, 4096, 0, 0, 0, 4096) + (0,) * 12   # a colour record that copies: m = I, p = t = 0
+COLOR_MAX_COEF, COLOR_MAX_OFFSET = 32767, 1 << 23             # include/hjd.h HJD_COLOR_MAX_*
+_LUMA = (0.299, 0.587, 0.114)
+# RGB -> YIQ (NTSC; rows Y, I, Q: I and Q sum to 0, so greys have I = Q = 0); _color_ops inverts it
+_RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.595716, -0.274453, -0.321263), (0.211456, -0.522591, 0.311135))
+_COLOR_OPS = ("brightness", "contrast", "saturation", "hue")
+
+
+def _mat3(a, b):
+    return [[sum(a[i][k] * b[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
+
+
+def _inv3(a):
+    c = [[a[(i + 1) % 3][(j + 1) % 3] * a[(i + 2) % 3][(j + 2) % 3] - a[(i + 1) % 3][(j + 2) % 3] * a[(i + 2) % 3][(j + 1) % 3]
+          for j in range(3)] for i in range(3)]   # cofactors
+    det = sum(a[0][j] * c[0][j] for j in range(3))
+    return [[c[j][i] / det for j in range(3)] for i in range(3)]
+
+
+def _add3(a, b):
+    return [[a[i][j] + b[i][j] for j in range(3)] for i in range(3)]
+
+
+def _color(record):
+    """21 Python ints of a colour record; ValueError unless 21 int32 values (their ranges are the library's to refuse)."""
+    c = [int(v) for v in record]
+    if len(c) != 21 or any(v != f for v, f in zip(c, record)):
+        raise ValueError("a colour record is 21 integers: m[9], p[9], t[3] (Q12)")
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in c):
+        raise ValueError(f"an entry of a colour record leaves int32: {c}")
+    return c
+
+
+def _color_ops(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, gray=False, invert=False,
+              order=_COLOR_OPS, pivot="mean"):
+    """The real-valued map color_matrix() rounds: (M, P, t), 3 x 3 lists and a
+    3-list of float64 with x -> M x + P xbar + t on grey levels 0..255, xbar the
+    channel means of the image.  Pure Python."""
+    import math
+    order = tuple(order)
+    if sorted(order) != sorted(_COLOR_OPS):
+        raise ValueError(f"order must be a permutation of {_COLOR_OPS}")
+    if not (isinstance(pivot, (int, float)) or pivot == "mean"):
+        raise ValueError('pivot is "mean" or a grey level')
+    if not -0.5 <= float(hue) <= 0.5:
+        raise ValueError("hue is in turns, -0.5..0.5")
+    for name, v in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation)):
+        if not (math.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"{name} must be a finite factor >= 0")
+    eye = [[1.0 if i == j else 0.0 for j in range(3)] for i in range(3)]
+    zero = [[0.0] * 3 for _ in range(3)]
+    lum = [list(_LUMA) for _ in range(3)]           # x -> L(x) * 1
+
+    def scaled(a, f):
+        return [[f * v for v in row] for row in a]
+
+    def step(name):
+        if name == "brightness":
+            return scaled(eye, float(brightness)), zero, [0.0] * 3
+        if name == "contrast":
+            f = float(contrast)
+            if pivot == "mean":
+                return scaled(eye, f), scaled(lum, 1.0 - f), [0.0] * 3
+            return scaled(eye, f), zero, [(1.0 - f) * float(pivot)] * 3
+        if name == "saturation":
+            f = float(saturation)
+            return _add3(scaled(eye, f), scaled(lum, 1.0 - f)), zero, [0.0] * 3
+        if name == "hue":
+            a = 2.0 * math.pi * float(hue)
+            rot = [[1.0, 0.0, 0.0], [0.0, math.cos(a), -math.sin(a)], [0.0, math.sin(a), math.cos(a)]]
+            return _mat3(_inv3(_RGB_TO_YIQ), _mat3(rot, _RGB_TO_YIQ)), zero, [0.0] * 3
+        if name == "gray":
+            return lum, zero, [0.0] * 3
+        return scaled(eye, -1.0), zero, [255.0] * 3   # invert
+
+    steps = [n for n in order if {"brightness": brightness != 1.0, "contrast": contrast != 1.0,
+                                  "saturation": saturation != 1.0, "hue": hue != 0.0}[n]]
+    steps += (["gray"] if gray else []) + (["invert"] if invert else [])
+    M, P, t = eye, zero, [0.0] * 3
+    for name in steps:   # (M2, P2, t2) o (M, P, t) = (M2 M, M2 P + P2 (M + P), (M2 + P2) t + t2)
+        M2, P2, t2 = step(name)
+        MP2 = _add3(M2, P2)
+        M, P, t = (_mat3(M2, M), _add3(_mat3(M2, P), _mat3(P2, _add3(M, P))),
+                   [sum(MP2[i][k] * t[k] for k in range(3)) + t2[i] for i in range(3)])
+    return M, P, t
+
+
+def color_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, gray=False, invert=False,
+                 order=_COLOR_OPS, pivot="mean"):
+    """The 21 integers (hjd_color_item's m[9], p[9], t[3], Q12) of a colour
+    augmentation: x -> M x + P xbar + t on RGB grey levels 0..255, xbar the
+    channel means of the image the stage reads.  Pure Python, float64.
+
+    The operations, applied in `order`, then gray, then invert, each skipped
+    at its default, with L(x) = 0.299 R + 0.587 G + 0.114 B:
+
+        brightness f   x -> f x
+        contrast f     x -> f x + (1 - f) L(xbar) 1     (pivot = <number>: that grey level for L(xbar))
+        saturation f   x -> f x + (1 - f) L(x) 1
+        hue h          the rotation by 2 pi h (h in turns, -0.5..0.5) about the grey axis in YIQ
+        gray           x -> L(x) 1
+        invert         x -> 255 - x
+
+    They are composed as real-valued maps with NO clamp in between: the means
+    after a step are (M + P) xbar + t, so
+
+        (M2, P2, t2) o (M1, P1, t1) = (M2 M1, M2 P1 + P2 (M1 + P1), (M2 + P2) t1 + t2)
+
+    and only the final result is clamped to 0..255 (include/hjd.h).
+    torchvision's ColorJitter clamps after each operation, so the two agree
+    only while no intermediate saturates.  The hue map is DALI's and
+    tf.image's rotation in YIQ; it is NOT torchvision's, which shifts H in HSV.
+    Each entry is rounded to nearest in Q12 (4096 is 1.0; t in Q12 grey
+    levels); ValueError if a coefficient leaves +-32767 (about +-8.0) or an
+    offset +-2^23 (2048 grey levels), and for arguments outside their ranges."""
+    import math
+    M, P, t = _color_ops(brightness, contrast, saturation, hue, gray, invert, order, pivot)
+    flat = [v for row in M for v in row] + [v for row in P for v in row] + list(t)
+    c = [int(math.floor(v * 4096.0 + 0.5)) for v in flat]
+    if any(abs(v) > COLOR_MAX_COEF for v in c[:18]):
+        raise ValueError(f"a coefficient of m or p is outside +-{COLOR_MAX_COEF} (Q12): {c[:18]}")
+    if any(abs(v) > COLOR_MAX_OFFSET for v in c[18:]):
+        raise ValueError(f"an offset t is outside +-2^23 (Q12 grey levels): {c[18:]}")
+    return c
+
+
+class Color(_Stage):
+    """hjd_color: N planar uint8 RGB images of different sizes, each through
+    its own colour record (21 Q12 integers, color_matrix() makes them) into
+    its own output of the same size, in one launch -- two where a record reads
+    its image's channel means (include/hjd.h: exact integers, one rounding)."""
+    _prefix = "hjd_color"
+
+    def __init__(self, ctx: Context, srcs, outs, colors, normalize=None):
+        """srcs as Resize takes them.  outs: N device tensors of one dtype
+        (uint8, float16 or float32), out i shaped (3, h, w) as source i,
+        contiguous or a [..., :w] view of wider rows, or (tensor, pitch)
+        pairs -- or one (N, 3, h, w) tensor where the sizes agree.  A uint8
+        out that is its source (same tensor, same pitch) runs in place.
+        colors: N records of 21 ints.  normalize = (a, b): the float dtypes'
+        constants."""
+        super().__init__(ctx)
+        n = len(srcs)
+        if not isinstance(outs, (list, tuple)):
+            if not (outs.ndim == 4 and outs.shape[0] == n):
+                raise ValueError(f"outs must be {n} tensors or one (N, 3, h, w) tensor of {n} images")
+            outs = [outs[i] for i in range(n)]
+        if len(outs) != n or len(colors) != n:
+            raise ValueError("one output and one colour record per source")
+        items = (_lib.HjdColorItem * max(1, n))()
+        fmt = None
+        for i, (s, d) in enumerate(zip(srcs, outs)):
+            t, sp = _planes(s, i, "source", uint8=True)
+            u, dp = _planes(d, i, "output")
+            if str(u.dtype) not in _DTYPE_FORMATS or (fmt is not None and _DTYPE_FORMATS[str(u.dtype)] != fmt):
+                raise ValueError("outputs must be uint8 / float16 / float32 device tensors of one dtype")
+            fmt = _DTYPE_FORMATS[str(u.dtype)]
+            if tuple(u.shape) != tuple(t.shape):
+                raise ValueError(f"output {i} is {tuple(u.shape)}, its source {tuple(t.shape)}")
+            c = _color(colors[i])
+            self._keep += [t, u]
+            items[i] = _lib.HjdColorItem(t.data_ptr(), u.data_ptr(), int(t.shape[2]), int(t.shape[1]), int(sp), int(dp),
+                                         (ctypes.c_int32 * 9)(*c[:9]), (ctypes.c_int32 * 9)(*c[9:18]),
+                                         (ctypes.c_int32 * 3)(*c[18:]), 0)
+        self.out_format = fmt if fmt is not None else OUT_RGB_PLANAR
+        self._create("create", normalize, items, n, self.out_format)
+
+
 def worker_cpus(bus: str, gpus: Sequence[str], sysfs_root: Optional[str] = None, only_allowed: bool = False):
     """hjd_debug_worker_cpus: the host CPUs the worker pool of the GPU at PCI
     address `bus` binds to, among the GPUs `gpus` (its NUMA node's CPUs split

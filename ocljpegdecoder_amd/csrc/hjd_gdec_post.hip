@@ -1,5 +1,5 @@
 // hjd_gdec_post.hip -- the decoder calls with stages behind the pixel kernels
-// (include/hjd_host.h hjd_gdec_decode_oriented, _resized*, _warped; DESIGN.md
+// (include/hjd_host.h hjd_gdec_decode_oriented, _resized*, _warped*; DESIGN.md
 // s10).  Each entry point admits its frames (admit_frame), lays out the
 // scratch (Region) and states its stages as one PostPlan, which gdec_issue
 // writes and launches through post_write_records and post_launch.  Everything
@@ -13,6 +13,7 @@
 
 #include "hjd_host.h"
 
+using hjd_internal::ColorRecord;
 using hjd_internal::OrientRecord;
 using hjd_internal::ResizeRecord;
 using hjd_internal::set_error;
@@ -39,6 +40,24 @@ struct Region {
         dims[i].h = rows;
         offs[i] = need;
         need = hjd_internal::align_up(need + 3 * static_cast<size_t>(pitches[i]) * static_cast<size_t>(rows), 16);
+    }
+    // All of the region's images as one planar batch of w x rows: the pitch rounded up to 4, image i
+    // at i * 3 * pitch * rows (what batch_record computes from the first), the whole 16-byte aligned.
+    void add_batch(int w, int rows)
+    {
+        const size_t image = 3 * static_cast<size_t>((w + 3) & ~3) * static_cast<size_t>(rows);
+        for (size_t i = 0; i < ptrs.size(); ++i) {
+            pitches[i] = (w + 3) & ~3;
+            dims[i] = hjd_rect{0, 0, w, rows};
+            offs[i] = need + image * i;
+        }
+        need = hjd_internal::align_up(need + image * ptrs.size(), 16);
+    }
+    // One array of `bytes` bytes (a region of one "image" nobody reads as one).
+    void add_bytes(size_t bytes)
+    {
+        offs[0] = need;
+        need = hjd_internal::align_up(need + bytes, 16);
     }
     PostImages images() const { return PostImages{ptrs.data(), pitches.data(), dims.data()}; }
 };
@@ -160,6 +179,33 @@ int write_warp_records(const PostStage& s, int n, WarpRecord* recs)
     return HJD_OK;
 }
 
+// The colour kernels' records: image i of the batch s.in (the resize's or warp's planar bytes in
+// the scratch) through s.colors[i] to its place in the caller's batch.
+int write_color_records(const PostStage& s, int n, ColorRecord* recs)
+{
+    for (int i = 0; i < n; ++i) {
+        ColorRecord rec;
+        rec.src = s.in.ptrs[i];
+        rec.dst = static_cast<uint8_t*>(s.batch.ptr) +
+                  3 * static_cast<size_t>(s.batch.pitch) * static_cast<size_t>(s.batch.h) * static_cast<size_t>(i);
+        rec.w = s.batch.w;
+        rec.h = s.batch.h;
+        rec.pitch = s.in.pitches[i];
+        rec.dst_pitch = s.batch.pitch;
+        const int32_t* c = s.colors[i];   // m[9], p[9], t[3]
+        memcpy(rec.m, c, sizeof(rec.m));
+        memcpy(rec.p, c + 9, sizeof(rec.p));
+        memcpy(rec.t, c + 18, sizeof(rec.t));
+        bool uses = false;
+        int rc = hjd_internal::color_coef_check(c, c + 9, c + 18, i, &uses);
+        rec.use_sums = uses ? 1 : 0;
+        if (!rc) rc = hjd_internal::color_item_check(rec, i, s.out_format);
+        if (rc) return rc;
+        recs[i] = rec;
+    }
+    return HJD_OK;
+}
+
 }  // namespace
 
 int hjd::ent::post_write_records(hjd_gdec* g, const PostPlan& plan, int n)
@@ -173,6 +219,7 @@ int hjd::ent::post_write_records(hjd_gdec* g, const PostPlan& plan, int n)
         case PostKind::resize:
         case PostKind::resize_aa: rc = write_resize_records(s, n, static_cast<ResizeRecord*>(recs)); break;
         case PostKind::warp: rc = write_warp_records(s, n, static_cast<WarpRecord*>(recs)); break;
+        case PostKind::color: rc = write_color_records(s, n, static_cast<ColorRecord*>(recs)); break;
         }
         if (rc) return rc;
     }
@@ -202,6 +249,11 @@ int hjd::ent::post_launch(hjd_gdec* g, const PostPlan& plan, int n, hipStream_t 
         case PostKind::warp:
             rc = hjd_internal::launch_warp(g->device, static_cast<const WarpRecord*>(recs), n, s.batch.w,
                                            s.batch.h, s.batch.pitch, s.out_format, g->norm, stream);
+            break;
+        case PostKind::color:
+            rc = hjd_internal::launch_color(g->device, static_cast<const ColorRecord*>(recs), n,
+                                            hjd_internal::color_groups(s.batch.w, s.batch.h), s.sums, s.out_format,
+                                            g->norm, stream);
             break;
         }
         if (rc) return rc;
@@ -257,12 +309,55 @@ int tiles_check(int64_t tiles)
     return HJD_OK;
 }
 
-// hjd_gdec_decode_resized_filter (orientations null) and
-// hjd_gdec_decode_resized_oriented: decode to the scratch, with orientations
-// orient to a second scratch region, then the resize launches.
+// The colour records of a call: HJD_OK if every one is legal (else the refusal names the frame).
+// *any: one is not the identity (else the call is the one without colours); *sums: one reads its
+// image's sums.  n has passed the call's own check.
+int colors_check(const int32_t (*colors)[21], int n, bool* any, bool* sums)
+{
+    static const int32_t kIdentity[21] = {4096, 0, 0, 0, 4096, 0, 0, 0, 4096};
+    *any = *sums = false;
+    for (int i = 0; i < n; ++i) {
+        bool uses = false;
+        const int rc = hjd_internal::color_coef_check(colors[i], colors[i] + 9, colors[i] + 18, i, &uses);
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        *sums = *sums || uses;
+        *any = *any || memcmp(colors[i], kIdentity, sizeof(kIdentity)) != 0;
+    }
+    return HJD_OK;
+}
+
+// The scratch of a call's colour stage: `mid`, the batch the resize or warp writes in its place
+// (planar bytes), and `sums`, the table of partial sums where a record reads them.
+struct ColorScratch {
+    Region mid, sums;
+    ColorScratch(bool on, bool with_sums, int n, int out_w, int out_h)
+        : mid(on ? static_cast<size_t>(n) : 0), sums(on && with_sums ? 1 : 0)
+    {
+        if (on) mid.add_batch(out_w, out_h);
+        if (on && with_sums) sums.add_bytes(hjd_internal::color_sums_bytes(n));
+    }
+};
+
+// Put the colour stage behind `last`, the plan's resize or warp stage, which wrote the caller's batch
+// in the decoder's format: it now writes planar bytes into c.mid, and the colour stage that batch.
+void add_color_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, const int32_t (*colors)[21], int out_format,
+                     int n)
+{
+    const auto batch = last.batch;
+    last.out_format = HJD_OUT_RGB_PLANAR;
+    last.batch = {c.mid.ptrs[0], batch.w, batch.h, c.mid.pitches[0]};
+    PostStage& s = add_stage(plan, PostKind::color, c.mid.images(), out_format, sizeof(ColorRecord) * static_cast<size_t>(n));
+    s.batch = batch;
+    s.colors = colors;
+    s.sums = c.sums.ptrs.empty() ? nullptr : static_cast<uint32_t*>(c.sums.ptrs[0]);
+}
+
+// hjd_gdec_decode_resized_filter (orientations null), hjd_gdec_decode_resized_oriented and
+// hjd_gdec_decode_resized_color (colors not null): decode to the scratch, with orientations
+// orient to a second scratch region, then the resize launches, then with colours the colour launches.
 int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
-                   const int32_t* orientations, const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch,
-                   int filter, void* stream)
+                   const int32_t* orientations, const int32_t* flags, const int32_t (*colors)[21], void* d_out, int out_w,
+                   int out_h, int32_t out_pitch, int filter, void* stream)
 {
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
@@ -282,9 +377,17 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
         if (rc) return rc;
         if (!any) orientations = nullptr;   // nothing to orient: the plain resized call
     }
+    bool color_sums = false;
+    if (colors) {
+        bool any = false;
+        rc = colors_check(colors, n, &any, &color_sums);
+        if (rc) return rc;
+        if (!any) colors = nullptr;   // every record the identity: the call without colours
+    }
     // (the scratch: the crops, an oriented call's oriented crops, the antialiased filter's intermediates)
     const size_t un = static_cast<size_t>(n);
     Region crops(un), oriented(orientations ? un : 0), mids(aa ? un : 0);
+    ColorScratch cs(colors != nullptr, color_sums, n, out_w, out_h);
     const Admit admit{g->scale, false, orientations ? kCapOriented : kCapResized,
                       orientations && rois ? orient_map : nullptr, orientations};
     int64_t tiles = 0;
@@ -313,7 +416,8 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     }
     rc = tiles_check(tiles);
     if (rc) return rc;
-    rc = grow_scratch(g, {&crops, &oriented, &mids}, aa ? "crops and the resize's intermediate" : "crops");
+    rc = grow_scratch(g, {&crops, &oriented, &mids, &cs.mid, &cs.sums},
+                      aa ? "crops and the resize's intermediate" : "crops");
     if (rc) return rc;
     PostPlan plan{0, {}, pixel_tables_bytes(n, rois != nullptr, false)};   // the pixel kernels' tables: planar bytes
     PostImages in = crops.images();
@@ -329,7 +433,70 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     r.flags = flags;
     r.mids = mids.ptrs.data();
     r.max_h = max_h;
+    if (colors) add_color_stage(plan, r, cs, colors, g->out_format, n);
     return run_post(g, datas, sizes, n, stream, crops, rois != nullptr, plan);
+}
+
+// hjd_gdec_decode_warped (colors null) and hjd_gdec_decode_warped_color: decode the rectangle
+// each warp reads to the scratch, then the warp launch, then with colours the colour launches.
+int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
+                  const int32_t* orientations, const int32_t* flags, const uint32_t* fills, const int32_t (*colors)[21],
+                  void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
+{
+    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
+    if (!m) return set_error(HJD_E_INVALID, "m is NULL");
+    if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
+    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
+        return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
+                         hjd_internal::out_format_row_bytes(g->out_format));
+    if (n > g->st.caps.max_frames)
+        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
+    bool color_sums = false;
+    if (colors) {
+        bool any = false;
+        rc = colors_check(colors, n, &any, &color_sums);
+        if (rc) return rc;
+        if (!any) colors = nullptr;   // every record the identity: the call without colours
+    }
+    // per frame: the matrix on the stored image, the rectangle it reads (the
+    // crop, in the scratch), the matrix on that crop
+    const size_t un = static_cast<size_t>(n);
+    Region crops(un);
+    ColorScratch cs(colors != nullptr, color_sums, n, out_w, out_h);
+    std::vector<int32_t> mats(6 * un);
+    const WarpMap wmap{m, orientations, out_w, out_h, reinterpret_cast<int32_t(*)[6]>(mats.data())};
+    const Admit admit{g->scale, false, kCapWarped, warp_map, &wmap};
+    for (int i = 0; i < n; ++i) {
+        hjd_rect& r = crops.dims[i];
+        rc = admit_frame(admit, datas[i], sizes[i], i, nullptr, &r);
+        if (rc) return rc;
+        int32_t* mc = wmap.mats[i];
+        const int64_t tx = static_cast<int64_t>(mc[2]) - (static_cast<int64_t>(r.x) << 16);
+        const int64_t ty = static_cast<int64_t>(mc[5]) - (static_cast<int64_t>(r.y) << 16);
+        if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX)
+            return set_error(HJD_E_INVALID, "frame %d: the translation shifted to the crop at (%d, %d) leaves int32", i, r.x,
+                             r.y);
+        mc[2] = static_cast<int32_t>(tx);
+        mc[5] = static_cast<int32_t>(ty);
+        if (flags && (flags[i] & ~HJD_WARP_REPLICATE))
+            return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: HJD_WARP_REPLICATE)", i,
+                             static_cast<unsigned>(flags[i] & ~HJD_WARP_REPLICATE));
+        if (fills && fills[i] > 0xFFFFFFu)
+            return set_error(HJD_E_INVALID, "frame %d: fill 0x%x is above 0xFFFFFF (0x00RRGGBB)", i, fills[i]);
+        crops.add(i, r.w, r.h);
+    }
+    rc = grow_scratch(g, {&crops, &cs.mid, &cs.sums}, "crops");
+    if (rc) return rc;
+    PostPlan plan{0, {}, pixel_tables_bytes(n, true, false)};   // the pixel kernels' tables: planar bytes
+    PostStage& w = add_stage(plan, PostKind::warp, crops.images(), g->out_format, sizeof(WarpRecord) * un);
+    w.batch = {d_out, out_w, out_h, out_pitch};
+    w.flags = flags;
+    w.mats = wmap.mats;
+    w.fills = fills;
+    if (colors) add_color_stage(plan, w, cs, colors, g->out_format, n);
+    return run_post(g, datas, sizes, n, stream, crops, true, plan);
 }
 
 }  // namespace
@@ -384,15 +551,16 @@ int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const siz
 int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                             const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
 {
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, d_out, out_w, out_h, out_pitch, HJD_RESIZE_BILINEAR,
-                          stream);
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, d_out, out_w, out_h, out_pitch,
+                          HJD_RESIZE_BILINEAR, stream);
 }
 
 int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
                                    const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
                                    int32_t out_pitch, int filter, void* stream)
 {
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, d_out, out_w, out_h, out_pitch, filter, stream);
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, d_out, out_w, out_h, out_pitch, filter,
+                          stream);
 }
 
 int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -400,58 +568,34 @@ int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, c
                                      int out_w, int out_h, int32_t out_pitch, int filter, void* stream)
 {
     if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, d_out, out_w, out_h, out_pitch, filter, stream);
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, nullptr, d_out, out_w, out_h, out_pitch, filter,
+                          stream);
+}
+
+int hjd_gdec_decode_resized_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                  const hjd_rect* rois, const int32_t* orientations, const int32_t* flags,
+                                  const int32_t (*colors)[21], void* d_out, int out_w, int out_h, int32_t out_pitch,
+                                  int filter, void* stream)
+{
+    if (!colors) return set_error(HJD_E_INVALID, "colors is NULL");
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, d_out, out_w, out_h, out_pitch, filter,
+                          stream);
 }
 
 int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
                            const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
                            int out_w, int out_h, int32_t out_pitch, void* stream)
 {
-    if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
-    if (!m) return set_error(HJD_E_INVALID, "m is NULL");
-    if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
-    int rc = hjd_internal::resize_out_check(n, out_w, out_h, out_pitch, g->out_format);
-    if (rc) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & hjd_internal::out_format_align_mask(g->out_format))
-        return set_error(HJD_E_INVALID, "d_out must be a multiple of the element size (%d bytes)",
-                         hjd_internal::out_format_row_bytes(g->out_format));
-    if (n > g->st.caps.max_frames)
-        return set_error(HJD_E_INVALID, "batch of %d frames (capacity %d)", n, g->st.caps.max_frames);
-    // per frame: the matrix on the stored image, the rectangle it reads (the
-    // crop, in the scratch), the matrix on that crop
-    const size_t un = static_cast<size_t>(n);
-    Region crops(un);
-    std::vector<int32_t> mats(6 * un);
-    const WarpMap wmap{m, orientations, out_w, out_h, reinterpret_cast<int32_t(*)[6]>(mats.data())};
-    const Admit admit{g->scale, false, kCapWarped, warp_map, &wmap};
-    for (int i = 0; i < n; ++i) {
-        hjd_rect& r = crops.dims[i];
-        rc = admit_frame(admit, datas[i], sizes[i], i, nullptr, &r);
-        if (rc) return rc;
-        int32_t* mc = wmap.mats[i];
-        const int64_t tx = static_cast<int64_t>(mc[2]) - (static_cast<int64_t>(r.x) << 16);
-        const int64_t ty = static_cast<int64_t>(mc[5]) - (static_cast<int64_t>(r.y) << 16);
-        if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX)
-            return set_error(HJD_E_INVALID, "frame %d: the translation shifted to the crop at (%d, %d) leaves int32", i, r.x,
-                             r.y);
-        mc[2] = static_cast<int32_t>(tx);
-        mc[5] = static_cast<int32_t>(ty);
-        if (flags && (flags[i] & ~HJD_WARP_REPLICATE))
-            return set_error(HJD_E_INVALID, "frame %d: unknown flag bits 0x%x (bit 0: HJD_WARP_REPLICATE)", i,
-                             static_cast<unsigned>(flags[i] & ~HJD_WARP_REPLICATE));
-        if (fills && fills[i] > 0xFFFFFFu)
-            return set_error(HJD_E_INVALID, "frame %d: fill 0x%x is above 0xFFFFFF (0x00RRGGBB)", i, fills[i]);
-        crops.add(i, r.w, r.h);
-    }
-    rc = grow_scratch(g, {&crops}, "crops");
-    if (rc) return rc;
-    PostPlan plan{0, {}, pixel_tables_bytes(n, true, false)};   // the pixel kernels' tables: planar bytes
-    PostStage& w = add_stage(plan, PostKind::warp, crops.images(), g->out_format, sizeof(WarpRecord) * un);
-    w.batch = {d_out, out_w, out_h, out_pitch};
-    w.flags = flags;
-    w.mats = wmap.mats;
-    w.fills = fills;
-    return run_post(g, datas, sizes, n, stream, crops, true, plan);
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, nullptr, d_out, out_w, out_h, out_pitch, stream);
+}
+
+int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                 const int32_t (*m)[6], const int32_t* orientations, const int32_t* flags,
+                                 const uint32_t* fills, const int32_t (*colors)[21], void* d_out, int out_w, int out_h,
+                                 int32_t out_pitch, void* stream)
+{
+    if (!colors) return set_error(HJD_E_INVALID, "colors is NULL");
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, d_out, out_w, out_h, out_pitch, stream);
 }
 
 }  // extern "C"

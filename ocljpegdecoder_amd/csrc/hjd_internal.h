@@ -217,6 +217,7 @@ using NormRecord = hjd::NormDev;
 using ResizeRecord = hjd::ResizeDev;   // (the layout of hjd_resize_item, too)
 using OrientRecord = hjd::OrientDev;   // (of hjd_orient_item, whose reserved word is tile_begin here)
 using WarpRecord = hjd::WarpDev;       // (of hjd_warp_item)
+using ColorRecord = hjd::ColorDev;     // (of hjd_color_item, whose reserved word is use_sums here)
 // a = 1, b = 0: the C default (out = (float)u8).
 inline NormRecord norm_identity() { return NormRecord{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}}; }
 // HJD_OK, or HJD_E_INVALID (NULL or non-finite constants) with the cause in the error string.
@@ -302,6 +303,24 @@ int warp_orient(const int32_t m[6], int stored_w, int stored_h, int orientation,
 // library's choice (hjd::kWarpTiled).
 int launch_warp(int device, const WarpRecord* d_items, int n, int out_w, int out_h, int out_pitch, int out_format,
                 const NormRecord& norm, void* stream, int tiled = -1);
+
+// The colour kernels (hjd_color.hip; include/hjd.h hjd_color_*).
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: n and the
+// format; the words m[9], p[9], t[3] of one record (*uses_sums, if asked: some
+// p is not 0); and one item's side of hjd_color_check (use_sums is not looked at).
+// A caller's flat record c[21] is (c, c + 9, c + 18).
+int color_out_check(int n, int out_format);
+int color_coef_check(const int32_t m[9], const int32_t p[9], const int32_t t[3], int index, bool* uses_sums);
+int color_item_check(const ColorRecord& it, int index, int out_format);
+// Groups of one w x h image (a launch takes the largest of its images'), and
+// the bytes of the table of partial sums of n images: [n][kMaxGroups][3] uint32.
+int color_groups(int w, int h);
+constexpr size_t color_sums_bytes(int n) { return static_cast<size_t>(n) * 256 * 3 * sizeof(uint32_t); }
+// color_sum_kernel (d_sums not null: some record's use_sums is set) and
+// color_kernel over n records in device memory (no host synchronisation); the
+// records have passed the checks and carry use_sums.
+int launch_color(int device, const ColorRecord* d_items, int n, int groups, uint32_t* d_sums, int out_format,
+                 const NormRecord& norm, void* stream);
 
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe

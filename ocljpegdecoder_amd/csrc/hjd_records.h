@@ -1,6 +1,6 @@
 // hjd_records.h -- the records the stage kernels and the float formats read, one
 // declaration each for the host that writes them (hjd_internal.h) and the
-// kernels (hjd_norm.hpp, hjd_resize.hpp, hjd_orient.hpp, hjd_warp.hpp).  No HIP.
+// kernels (hjd_norm.hpp, hjd_resize.hpp, hjd_orient.hpp, hjd_warp.hpp, hjd_color.hpp).  No HIP.
 #pragma once
 #include <stdint.h>
 
@@ -44,5 +44,16 @@ struct WarpDev {
     int32_t reserved;
 };
 static_assert(sizeof(WarpDev) == 64, "WarpDev layout");
+
+// One image of the colour kernels: the layout of hjd_color_item, whose
+// reserved word the host fills with whether the record reads the image's sums.
+struct ColorDev {
+    const void* src;   // plane R; G and B follow at pitch * h
+    void* dst;         // plane R of the output; G and B follow at dst_pitch * h
+    int32_t w, h, pitch, dst_pitch;
+    int32_t m[9], p[9], t[3];   // Q12: u8 = clamp((m x + T + 2048) >> 12), T = t + ((p mq + 128) >> 8)
+    int32_t use_sums;           // some p is not 0: color_sum_kernel ran before color_kernel
+};
+static_assert(sizeof(ColorDev) == 120, "ColorDev layout");
 
 }  // namespace hjd

@@ -361,6 +361,32 @@ class GpuDecoder:
             raise ValueError("one ROI per JPEG")
         return (HjdRect * n)(*[HjdRect(*[int(v) for v in r]) for r in rois])
 
+    @staticmethod
+    def _flips(flips, n):
+        """The flips of a resized call as an int32 array, or None where it gives none."""
+        if flips is None:
+            return None
+        if len(flips) != n:
+            raise ValueError("one flip flag per JPEG")
+        return (ctypes.c_int32 * n)(*[1 if f else 0 for f in flips])
+
+    @staticmethod
+    def _warp_arrays(xforms, fills, replicate, n):
+        """(matrices, flags, fills or None) of a warped call as ctypes arrays."""
+        from .backend import _warp_flags, _xform
+        if len(xforms) != n:
+            raise ValueError("one matrix per JPEG")
+        mats = ((ctypes.c_int32 * 6) * n)(*[(ctypes.c_int32 * 6)(*_xform(x)) for x in xforms])
+        fl = (ctypes.c_int32 * n)(*_warp_flags(replicate, n))
+        fi = None
+        if fills is not None:
+            if len(fills) != n:
+                raise ValueError("one fill colour per JPEG")
+            if any(not 0 <= int(f) <= 0xFFFFFF for f in fills):
+                raise ValueError("a fill colour is 0xRRGGBB")
+            fi = (ctypes.c_uint32 * n)(*[int(f) for f in fills])
+        return mats, fl, fi
+
     def _check_batch_out(self, out, n):
         """`out` of a resized or warped call: (n, 3, Ho, Wo) in the decoder's planar format."""
         if not (out.is_cuda and out.is_contiguous() and out.ndim == 4 and out.shape[0] == n and out.shape[1] == 3):
@@ -422,11 +448,7 @@ class GpuDecoder:
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         self._check_batch_out(out, n)
-        rects, fl = self._rects(rois, n), None
-        if flips is not None:
-            if len(flips) != n:
-                raise ValueError("one flip flag per JPEG")
-            fl = (ctypes.c_int32 * n)(*[1 if f else 0 for f in flips])
+        rects, fl = self._rects(rois, n), self._flips(flips, n)
         ho, wo = int(out.shape[2]), int(out.shape[3])
         orients = self._orientations(datas, apply_exif_orientation, orientations)
         if orients is not None:
@@ -587,14 +609,7 @@ class GpuDecoder:
         if not chw:
             raise ValueError('a resized batch is planar: layout must be "chw"')
         orients = self._orientations(datas, apply_exif_orientation, orientations)
-        size = (int(size[0]), int(size[1]))
-        if min(size) < 1:
-            raise ValueError(f"size must be (h, w) with h, w >= 1, got {size}")
-        shape = (len(datas), 3) + size
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.ctx.device))
-        elif not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == shape):
-            raise ValueError(f"out must be a contiguous {dtype} device tensor {shape}")
+        out = self._batch_result(len(datas), size, dtype, out)
         return self._with_settings(scale, fmt, norm,
                                    lambda: self.decode_resized(datas, out, stream, rois=rois, flips=flips,
                                                                antialias=antialias, orientations=orients), out)
@@ -613,21 +628,10 @@ class GpuDecoder:
         the nearest pixel of the image instead.  Only the rectangle of each
         frame the warp reads is decoded, into the scratch decode_resized()
         uses, under its growth rule."""
-        from .backend import _warp_flags, _xform
         _keep, arr_d, arr_s = _byte_arrays(datas)
         n = len(datas)
         self._check_batch_out(out, n)
-        if len(xforms) != n:
-            raise ValueError("one matrix per JPEG")
-        mats = ((ctypes.c_int32 * 6) * n)(*[(ctypes.c_int32 * 6)(*_xform(x)) for x in xforms])
-        fl = (ctypes.c_int32 * n)(*_warp_flags(replicate, n))
-        fi = None
-        if fills is not None:
-            if len(fills) != n:
-                raise ValueError("one fill colour per JPEG")
-            if any(not 0 <= int(f) <= 0xFFFFFF for f in fills):
-                raise ValueError("a fill colour is 0xRRGGBB")
-            fi = (ctypes.c_uint32 * n)(*[int(f) for f in fills])
+        mats, fl, fi = self._warp_arrays(xforms, fills, replicate, n)
         orients = self._orientations(datas, apply_exif_orientation, orientations)
         ho, wo = int(out.shape[2]), int(out.shape[3])
         check(self.lib.hjd_gdec_decode_warped(self.handle, arr_d, arr_s, n, mats,
@@ -669,6 +673,85 @@ class GpuDecoder:
                                                               replicate=replicate,
                                                               apply_exif_orientation=apply_exif_orientation,
                                                               orientations=orientations), out)
+
+    @staticmethod
+    def _colors(colors, n):
+        """The colour records of a call as an int32[n][21] array."""
+        from .backend import _color
+        if colors is None or len(colors) != n:
+            raise ValueError("one colour record (21 ints, color_matrix()) per JPEG")
+        return ((ctypes.c_int32 * 21) * n)(*[(ctypes.c_int32 * 21)(*_color(c)) for c in colors])
+
+    def _batch_result(self, n, size, dtype, out):
+        """The (n, 3, h, w) tensor of a resized or warped call: `out` checked, or a new one."""
+        import torch
+        size = (int(size[0]), int(size[1]))
+        if min(size) < 1:
+            raise ValueError(f"size must be (h, w) with h, w >= 1, got {size}")
+        shape = (n, 3) + size
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.ctx.device))
+        if not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == shape):
+            raise ValueError(f"out must be a contiguous {dtype} device tensor {shape}")
+        return out
+
+    def decode_rgb_resized_color(self, datas: Sequence[bytes], size, flips=None, layout: str = "chw", out=None,
+                                 stream=None, scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None,
+                                 apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                                 antialias=False, colors=None):
+        """decode_rgb_resized with a colour record per image
+        (hjd_gdec_decode_resized_color): colors[i], 21 ints as color_matrix()
+        returns them (brightness, contrast, saturation, hue, gray, invert), is
+        applied to image i after the resize, on the GPU, before the dtype's
+        normalisation: out[i] = normalise(color(resize(orient(decode)))).  A
+        record's means (contrast about the mean) are those of the resized
+        image.  Every other parameter as decode_rgb_resized.  Records that
+        are all COLOR_IDENTITY make it exactly decode_rgb_resized."""
+        chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
+        if not chw:
+            raise ValueError('a resized batch is planar: layout must be "chw"')
+        n = len(datas)
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        cols = self._colors(colors, n)
+        out = self._batch_result(n, size, dtype, out)
+        fl = self._flips(flips, n)
+
+        def call():
+            _keep, arr_d, arr_s = _byte_arrays(datas)
+            ho, wo = int(out.shape[2]), int(out.shape[3])
+            check(self.lib.hjd_gdec_decode_resized_color(
+                self.handle, arr_d, arr_s, n, self._rects(rois, n),
+                (ctypes.c_int32 * n)(*orients) if orients is not None else None, fl, cols, out.data_ptr(), wo, ho,
+                wo * out.element_size(), 1 if antialias else 0, _stream_handle(stream)), "hjd_gdec_decode_resized_color")
+            self._n = n
+        return self._with_settings(scale, fmt, norm, call, out)
+
+    def decode_rgb_warped_color(self, datas: Sequence[bytes], size, xforms, fill=0, replicate=False, out=None,
+                                stream=None, scale: int = 1, dtype=_UINT8, mean=None, std=None,
+                                apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                                colors=None):
+        """decode_rgb_warped with a colour record per image
+        (hjd_gdec_decode_warped_color): out[i] = normalise(color(warp(decode))),
+        colors as decode_rgb_resized_color takes them (the means are those of
+        the warped image, its fill included).  Every other parameter as
+        decode_rgb_warped."""
+        _chw, dtype, fmt, norm = self._rgb_format("chw", dtype, mean, std)
+        n = len(datas)
+        mats, fl, fi = self._warp_arrays(xforms, list(fill) if isinstance(fill, (list, tuple)) else [fill] * n,
+                                         replicate, n)
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        cols = self._colors(colors, n)
+        out = self._batch_result(n, size, dtype, out)
+
+        def call():
+            _keep, arr_d, arr_s = _byte_arrays(datas)
+            ho, wo = int(out.shape[2]), int(out.shape[3])
+            check(self.lib.hjd_gdec_decode_warped_color(
+                self.handle, arr_d, arr_s, n, mats, (ctypes.c_int32 * n)(*orients) if orients is not None else None,
+                fl, fi, cols, out.data_ptr(), wo, ho, wo * out.element_size(), _stream_handle(stream)),
+                "hjd_gdec_decode_warped_color")
+            self._n = n
+        return self._with_settings(scale, fmt, norm, call, out)
 
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);

@@ -4,7 +4,8 @@ kernel source between headers and must leave the machine code alone.
     git worktree add ../parent <commit>
     python tools/isa_same.py ../parent [--branch .] [--out profiles/isa_same.json]
 
-Every unit of tools/build_native.py's HIP_SOURCES is compiled to gfx950
+Every unit of tools/build_native.py's HIP_SOURCES that both trees have (a unit
+one tree lacks is listed under "only_in" and not compared) is compiled to gfx950
 assembly from both trees (hipcc --cuda-device-only -S, the build's flags) and
 compared function by function: the instruction lines and the labels between
 them, comments and assembler directives dropped, basic-block labels renumbered
@@ -70,6 +71,10 @@ def main():
     args = ap.parse_args()
     sources = args.units.split(",") if args.units else B.HIP_SOURCES
     trees = {"parent": os.path.abspath(args.parent), "branch": os.path.abspath(args.branch)}
+    has = {tag: [u for u in sources if os.path.exists(os.path.join(tree, "ocljpegdecoder_amd", "csrc", u))]
+           for tag, tree in trees.items()}
+    only_in = {tag: [u for u in has[tag] if u not in has[other]] for tag, other in (("parent", "branch"), ("branch", "parent"))}
+    sources = [u for u in sources if u in has["parent"] and u in has["branch"]]
     tmp = args.keep or tempfile.mkdtemp(prefix="isa_same_")
     os.makedirs(tmp, exist_ok=True)
     try:
@@ -93,7 +98,8 @@ def main():
     result = {"what": "device assembly of every HIP unit, parent tree against branch tree, function by function "
                       "(instructions and labels; comments and directives dropped)",
               "arch": B.ARCH, "flags": [f for f in B.COMMON if not f.startswith("-I")],
-              "functions": sum(u["functions"] for u in units.values()), "differ": differ, "units": units}
+              "functions": sum(u["functions"] for u in units.values()), "differ": differ, "only_in": only_in,
+              "units": units}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
