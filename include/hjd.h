@@ -697,7 +697,8 @@ int hjd_warp_destroy(hjd_warp* w);
  * image library that clamps after each operation agrees only while no
  * intermediate leaves 0..255.  A hue change is a rotation about the grey axis
  * in YIQ, not an HSV shift.  Operations that are not affine in RGB (posterize,
- * solarize, gamma, equalize) are not records.
+ * solarize, gamma, equalize) are not records: they, and autocontrast, are the
+ * curves of hjd_tone below, which can run behind this stage.
  *
  * In place: for HJD_OUT_RGB_PLANAR an item with dst == src and dst_pitch ==
  * src_pitch is legal -- a thread reads its four pixels before it writes them
@@ -733,6 +734,113 @@ int hjd_color_set_normalize(hjd_color* c, const float a[3], const float b[3]);
  * kernel, or two where a record's p is not 0). */
 int hjd_color_launch(hjd_color* c, void* stream);
 int hjd_color_destroy(hjd_color* c);
+
+/*
+ * Tone curves (extension; the reference has none): n planar uint8 RGB images,
+ * each of its own size, each through its own pointwise map of a byte per
+ * channel in ONE launch (three where a map is built from the image's
+ * histogram): a 3 x 256 lookup table per image -- solarize, posterize, gamma,
+ * inversion, any curve -- optionally preceded by autocontrast or equalize, the
+ * photometric operations of RandAugment / AutoAugment / TrivialAugment that
+ * are not affine in RGB.
+ *
+ * Source and output: exactly as hjd_color's -- three uint8 planes R, G, B of
+ * w x h, rows src_pitch bytes apart, planes src_pitch * h apart, any pointer
+ * and any src_pitch >= w, both dimensions in 1..16384; the same w x h out, in
+ * HJD_OUT_RGB_PLANAR (the bytes u8), HJD_OUT_RGB_PLANAR_F16 or _F32
+ * (fma((float)u8, a[c], b[c]), hjd_tone_set_normalize, default a = 1, b = 0);
+ * every item its own dst and dst_pitch, multiples of the element size,
+ * dst_pitch >= w x the element size, planes dst_pitch * h apart; dword loads
+ * and vector stores under hjd_color's conditions, guarded byte loads and
+ * element stores elsewhere.  Nothing outside the image's own elements is
+ * written.
+ *
+ * Definition (exact, integer).  A curve is a mode and a table lut[3][256],
+ * one row per channel R, G, B.  For an image of w x h, N = w * h <= 2^28, and
+ * channel c:
+ *     h_c[v] = the number of pixels of plane c whose byte is v   (v = 0..255)
+ * over the image's own w columns of its h rows -- no padding, and not the
+ * zeros a guarded load returns past column w.  The data curve D_c:
+ *   mode 0, HJD_TONE_TABLE:  D_c[v] = v.
+ *   mode 1, HJD_TONE_AUTOCONTRAST:  lo, hi the smallest and largest v with
+ *     h_c[v] > 0.  hi == lo: D_c[v] = v.  Else D_c[v] = 0 for v <= lo, 255 for
+ *     v >= hi, and floor(255 * (v - lo) / (hi - lo)) in between.
+ *   mode 2, HJD_TONE_EQUALIZE:  last = h_c[hi], step = floor((N - last) / 255).
+ *     Fewer than two non-empty bins (hi == lo), or step == 0: D_c[v] = v.
+ *     Else D_c[v] = min(255, floor((floor(step / 2) + sum over k < v of h_c[k]) / step)).
+ *     All of it fits uint32: step / 2 + the sum < 2^27 + 2^28.
+ * The output byte is
+ *     u8_c = lut[c][ D_c[x_c] ]
+ * -- the data curve first, the table second -- and the float formats are
+ * fma((float)u8, a[c], b[c]) of those bytes.
+ *
+ * Laws.  Mode 0 with lut[c][v] = v is a byte-for-byte copy.  A mode-0 record
+ * never reads a histogram (and a launch whose records are all mode 0 is one
+ * kernel).  A histogram is a sum of integer counts, which does not depend on
+ * the order they are added in: every launch of the same images gives the same
+ * bytes.
+ *
+ * Agreement with Pillow (12.2.0, checked on the CPU by tests/test_tone_cpu.py
+ * where Pillow is installed).  ImageOps.equalize is mode 2 with the identity
+ * table, bit for bit (the step == 0 and the few-valued cases included);
+ * ImageOps.solarize and .posterize are mode-0 tables, bit for bit.
+ * ImageOps.autocontrast evaluates int(v * (255.0 / (hi - lo)) - lo * scale) in
+ * float64, which differs from the exact floor above by one grey level in
+ * 12,094 of the 2,828,800 triples (lo, hi, v), never by more: mode 1 is the
+ * exact floor, and that is the documented difference.
+ *
+ * What it leaves out.  autocontrast's `cutoff` (lo and hi are the extreme
+ * non-empty bins); sharpness and blur, which are not pointwise; and any order
+ * other than colour (hjd_color, where a caller runs it first) -> data curve ->
+ * table: a table in front of the data curve is not a record.
+ *
+ * In place: for HJD_OUT_RGB_PLANAR an item with dst == src and dst_pitch ==
+ * src_pitch is legal -- a thread reads its four pixels before it writes them
+ * and the histogram is taken by an earlier launch.  Any other overlap of an
+ * output with a source or another output is the caller's error; it is not
+ * looked for.  An object with a record of mode 1 or 2 owns a table of partial
+ * histograms (n x 16 x 3 x 256 uint32) and one of curves (n x 768 bytes),
+ * allocated at create (HJD_E_NOMEM if that fails), which all its launches
+ * share: the caller orders them (the same stream, or events).  Every launch
+ * writes what it reads of them: they are never cleared.
+ */
+enum { HJD_TONE_TABLE = 0, HJD_TONE_AUTOCONTRAST = 1, HJD_TONE_EQUALIZE = 2 };
+typedef struct hjd_tone_curve {
+    int32_t mode;       /* HJD_TONE_* */
+    int32_t reserved;   /* 0 */
+    uint8_t lut[3][256];
+} hjd_tone_curve;       /* 776 bytes */
+typedef struct hjd_tone_item {
+    const void* src;   /* device: plane R of the source */
+    void* dst;         /* device: plane R of the output */
+    int32_t w, h, src_pitch, dst_pitch;
+    hjd_tone_curve curve;
+} hjd_tone_item;       /* 808 bytes */
+typedef struct hjd_tone hjd_tone;
+/* Validates what hjd_tone_create would take.  HJD_E_INVALID (with a message)
+ * for n outside 1..2^20, a NULL items / src / dst, a dimension outside
+ * 1..16384, src_pitch < w, a bad dst_pitch or dst alignment, a mode outside
+ * 0..2, a non-zero reserved and a non-planar or unknown format.  Host only:
+ * needs no device. */
+int hjd_tone_check(const hjd_tone_item* items, int n, int out_format);
+/* Validates and uploads the item table (synchronously). */
+int hjd_tone_create(hjd_ctx* ctx, const hjd_tone_item* items, int n, int out_format, hjd_tone** out);
+/* The float formats' constants for the launches that follow (an enqueued
+ * launch keeps its own).  HJD_E_INVALID for non-finite constants and for a
+ * byte-format object. */
+int hjd_tone_set_normalize(hjd_tone* t, const float a[3], const float b[3]);
+/* Enqueue the curves of all n items on `stream` (asynchronous; one kernel, or
+ * three where a record's mode is not 0). */
+int hjd_tone_launch(hjd_tone* t, void* stream);
+int hjd_tone_destroy(hjd_tone* t);
+/* The composed table lut_out[c][v] = lut_in[c][ D_c[v] ] of a curve of `mode`
+ * on an image whose channel histograms are hist[c][.]: the arithmetic of the
+ * definition above, by the one function the device's curve-building kernel
+ * calls.  lut_in NULL: the identity table.  HJD_E_INVALID for a mode outside
+ * 0..2, a NULL hist or lut_out and a channel whose counts sum above 2^28.
+ * Host only: needs no device. */
+int hjd_tone_curve_from_histogram(int mode, const uint32_t hist[3][256], const uint8_t lut_in[3][256],
+                                  uint8_t lut_out[3][256]);
 
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */

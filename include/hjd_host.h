@@ -336,6 +336,34 @@ int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const
                                  const int32_t (*m)[6], const int32_t* orientations, const int32_t* flags,
                                  const uint32_t* fills, const int32_t (*colors)[21], void* d_out, int out_w, int out_h,
                                  int32_t out_pitch, void* stream);
+/* hjd_gdec_decode_resized_color / hjd_gdec_decode_warped_color with a tone
+ * curve per frame behind the colour record (include/hjd.h hjd_tone_curve
+ * defines the mode, the table and the map): image i of the batch is
+ * tone(color(resize(orient(decode)))) or tone(color(warp(decode))), the
+ * histogram of a curve of mode 1 or 2 being that of the image the tone stage
+ * reads: resized or warped, its fill included, and behind the colour record.
+ * colors may be NULL (no colour stage), orientations too (all 1).
+ *
+ * Built as that composition: the resize or warp launch writes planar bytes
+ * into the region of the scratch the colour calls use, a colour stage runs on
+ * that region in place, and the tone launch reads it and writes d_out in the
+ * decoder's format with the decoder's constants.  Where a curve's mode is not
+ * 0 the partial histograms (n x 16 x 3 KiB) and the composed curves (n x 768
+ * bytes) lie in the same scratch and two more kernels run in front of the tone
+ * kernel; they write all they read, so a reused scratch needs no clearing.  A
+ * call whose curves are all mode 0 with the identity table is exactly the call
+ * without tones: no region, no launch.  Everything that can refuse the call --
+ * all that the call without tones refuses, a NULL tones, a mode outside 0..2
+ * or a non-zero reserved (HJD_E_INVALID naming the frame) -- is checked before
+ * anything is staged, allocated or enqueued. */
+int hjd_gdec_decode_resized_tone(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                 const hjd_rect* rois, const int32_t* orientations, const int32_t* flags,
+                                 const int32_t (*colors)[21], const hjd_tone_curve* tones, void* d_out, int out_w,
+                                 int out_h, int32_t out_pitch, int filter, void* stream);
+int hjd_gdec_decode_warped_tone(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                const int32_t (*m)[6], const int32_t* orientations, const int32_t* flags,
+                                const uint32_t* fills, const int32_t (*colors)[21], const hjd_tone_curve* tones,
+                                void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

@@ -35,6 +35,12 @@ from .backend import (  # noqa: E402
     Color,
     COLOR_IDENTITY,
     color_matrix,
+    Tone,
+    TONE_AUTOCONTRAST,
+    TONE_EQUALIZE,
+    TONE_IDENTITY,
+    TONE_TABLE,
+    tone_curve,
     Context,
     cpu_share,
     debug_tuning,
@@ -81,5 +87,6 @@ __all__ = [
     "Orient", "oriented_roi", "oriented_size", "exif_orientation",
     "Warp", "WARP_REPLICATE", "warp_roi", "warp_orient", "warp_xform",
     "Color", "COLOR_IDENTITY", "color_matrix",
+    "Tone", "TONE_TABLE", "TONE_AUTOCONTRAST", "TONE_EQUALIZE", "TONE_IDENTITY", "tone_curve",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -77,6 +77,20 @@ class HjdColorItem(ctypes.Structure):
 assert ctypes.sizeof(HjdColorItem) == 120
 
 
+class HjdToneCurve(ctypes.Structure):
+    """struct hjd_tone_curve (include/hjd.h): a mode and a table per channel."""
+    _fields_ = [("mode", ctypes.c_int32), ("reserved", ctypes.c_int32), ("lut", (ctypes.c_uint8 * 256) * 3)]
+
+
+class HjdToneItem(ctypes.Structure):
+    """struct hjd_tone_item (include/hjd.h): one image of a tone launch."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("w", "h", "src_pitch", "dst_pitch")] + [("curve", HjdToneCurve)]
+
+
+assert ctypes.sizeof(HjdToneCurve) == 776 and ctypes.sizeof(HjdToneItem) == 808
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -197,6 +211,14 @@ SIGNATURES = {
                                                ctypes.POINTER(ctypes.c_float)]),
     "hjd_color_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hjd_color_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_tone_check": (ctypes.c_int, [ctypes.POINTER(HjdToneItem), ctypes.c_int, ctypes.c_int]),
+    "hjd_tone_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdToneItem), ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_tone_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float)]),
+    "hjd_tone_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_tone_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_tone_curve_from_histogram": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
     "hjd_debug_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -314,6 +336,16 @@ def _bind_host(lib):
                                                         ctypes.c_int, ctypes.POINTER(ctypes.c_int32 * 6), c_i32p,
                                                         c_i32p, c_u32p, ctypes.POINTER(ctypes.c_int32 * 21), vp,
                                                         ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp]),
+        "hjd_gdec_decode_resized_tone": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                        ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, c_i32p,
+                                                        ctypes.POINTER(ctypes.c_int32 * 21), ctypes.POINTER(HjdToneCurve),
+                                                        vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int,
+                                                        vp]),
+        "hjd_gdec_decode_warped_tone": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int32 * 6), c_i32p,
+                                                       c_i32p, c_u32p, ctypes.POINTER(ctypes.c_int32 * 21),
+                                                       ctypes.POINTER(HjdToneCurve), vp, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int32, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -892,6 +892,140 @@ class Color(_Stage):
         self._create("create", normalize, items, n, self.out_format)
 
 
+TONE_TABLE, TONE_AUTOCONTRAST, TONE_EQUALIZE = 0, 1, 2   # include/hjd.h HJD_TONE_*: the data curve in front of the table
+TONE_IDENTITY = np.tile(np.arange(256, dtype=np.uint8), (3, 1))   # a table that copies: lut[c][v] = v
+TONE_IDENTITY.setflags(write=False)
+_TONE_OPS = ("gamma", "posterize", "solarize")
+# struct hjd_tone_curve and struct hjd_tone_item (include/hjd.h) as numpy records
+_TONE_CURVE_FIELDS = [("mode", "<i4"), ("reserved", "<i4"), ("lut", "u1", (3, 256))]
+_TONE_CURVE_DTYPE = np.dtype(_TONE_CURVE_FIELDS)
+_TONE_ITEM_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("w", "<i4"), ("h", "<i4"), ("src_pitch", "<i4"),
+                             ("dst_pitch", "<i4")] + _TONE_CURVE_FIELDS)
+assert _TONE_CURVE_DTYPE.itemsize == 776 and _TONE_ITEM_DTYPE.itemsize == 808
+
+
+def _tone_table(table, what="a tone table"):
+    """`table` as a uint8 (3, 256) array: 256 values for all channels, or 3 x 256; ValueError unless bytes."""
+    t = np.asarray(table)
+    if t.shape not in ((256,), (3, 256)) or t.dtype.kind not in "iu":
+        raise ValueError(f"{what} is 256 or 3 x 256 integers in 0..255")
+    if t.size and (int(t.min()) < 0 or int(t.max()) > 255):
+        raise ValueError(f"{what} has an entry outside 0..255")
+    return np.ascontiguousarray(np.broadcast_to(t.astype(np.uint8), (3, 256)))
+
+
+def tone_curve(solarize=None, posterize=None, gamma=None, invert=False, table=None, order=_TONE_OPS):
+    """The uint8 (3, 256) table (hjd_tone_curve's lut) of a pointwise tone
+    augmentation, the same in the three channels unless `table` differs.  numpy.
+
+    The operations, applied in `order`, then invert, then table, each skipped
+    at its default, on a grey level v in 0..255:
+
+        gamma g       v -> floor(255 (v / 255)^g + 0.5)      (g finite and > 0, float64)
+        posterize b   v -> v with its top b bits kept          (b in 1..8; Pillow's ImageOps.posterize)
+        solarize t    v -> v if v < t else 255 - v             (t in 0..256; Pillow's ImageOps.solarize)
+        invert        v -> 255 - v
+        table         v -> table[v] or table[c][v]             (256 or 3 x 256 bytes)
+
+    Every step maps bytes to bytes, so the composition is exact: the result
+    is step_k[... step_1[v]].  With no argument it is TONE_IDENTITY.  A data
+    curve (modes=TONE_AUTOCONTRAST / TONE_EQUALIZE) runs in front of the whole
+    table, never between its steps."""
+    import math
+    order = tuple(order)
+    if sorted(order) != sorted(_TONE_OPS):
+        raise ValueError(f"order must be a permutation of {_TONE_OPS}")
+    v = np.arange(256, dtype=np.int64)
+    steps = {}
+    if gamma is not None:
+        g = float(gamma)
+        if not (math.isfinite(g) and g > 0.0):
+            raise ValueError("gamma must be a finite exponent > 0")
+        steps["gamma"] = np.floor(255.0 * (v / 255.0) ** g + 0.5).astype(np.int64)
+    if posterize is not None:
+        if int(posterize) != posterize or not 1 <= int(posterize) <= 8:
+            raise ValueError("posterize keeps 1..8 bits")
+        steps["posterize"] = v & ~((1 << (8 - int(posterize))) - 1)
+    if solarize is not None:
+        if int(solarize) != solarize or not 0 <= int(solarize) <= 256:
+            raise ValueError("solarize takes a threshold in 0..256")
+        steps["solarize"] = np.where(v < int(solarize), v, 255 - v)
+    lut = v
+    for name in order:
+        if name in steps:
+            lut = steps[name][lut]
+    if invert:
+        lut = 255 - lut
+    out = np.ascontiguousarray(np.broadcast_to(lut.astype(np.uint8), (3, 256)))
+    if table is not None:
+        out = np.take_along_axis(_tone_table(table, "table"), out.astype(np.int64), axis=1)
+    return out
+
+
+def _tone_curves(curves, modes, n, dtype=_TONE_CURVE_DTYPE):
+    """n records of `dtype` (hjd_tone_curve, or hjd_tone_item with its other fields 0) from `curves`
+    -- None (all TONE_IDENTITY), one table for all images or n tables -- and `modes` -- None (all
+    TONE_TABLE), one mode or n.  ValueError for wrong counts; the range of a mode is the library's to refuse."""
+    recs = np.zeros(max(1, n), dtype=dtype)
+    if curves is None:
+        recs["lut"][:] = TONE_IDENTITY
+    elif isinstance(curves, np.ndarray) and curves.shape in ((256,), (3, 256)):
+        recs["lut"][:] = _tone_table(curves)
+    else:
+        if len(curves) != n:
+            raise ValueError("one tone table (tone_curve()) per image, or one for all")
+        for i, c in enumerate(curves):
+            recs["lut"][i] = _tone_table(c, f"tone table {i}")
+    if modes is None:
+        modes = [TONE_TABLE] * n
+    elif isinstance(modes, (int, np.integer)):
+        modes = [int(modes)] * n
+    if len(modes) != n or any(int(m) != m or not -2 ** 31 <= int(m) < 2 ** 31 for m in modes):
+        raise ValueError("one mode (TONE_TABLE, TONE_AUTOCONTRAST, TONE_EQUALIZE) per image, or one for all")
+    recs["mode"][:n] = [int(m) for m in modes]
+    return recs
+
+
+class Tone(_Stage):
+    """hjd_tone: N planar uint8 RGB images of different sizes, each through its
+    own tone curve -- a 3 x 256 table (tone_curve() makes them), optionally
+    behind autocontrast or equalize of the image's own histogram -- into its
+    own output of the same size; one launch, three where a mode is not
+    TONE_TABLE (include/hjd.h: exact integers, u8 = lut[c][D_c[x]])."""
+    _prefix = "hjd_tone"
+
+    def __init__(self, ctx: Context, srcs, outs, curves=None, modes=None, normalize=None):
+        """srcs and outs as Color takes them (a uint8 out that is its source,
+        same tensor and pitch, runs in place).  curves: N uint8 (3, 256) or
+        (256,) tables, one for all, or None (TONE_IDENTITY).  modes: N of
+        TONE_TABLE / TONE_AUTOCONTRAST / TONE_EQUALIZE, one for all, or None
+        (TONE_TABLE).  normalize = (a, b): the float dtypes' constants."""
+        super().__init__(ctx)
+        n = len(srcs)
+        if not isinstance(outs, (list, tuple)):
+            if not (outs.ndim == 4 and outs.shape[0] == n):
+                raise ValueError(f"outs must be {n} tensors or one (N, 3, h, w) tensor of {n} images")
+            outs = [outs[i] for i in range(n)]
+        if len(outs) != n:
+            raise ValueError("one output per source")
+        items = _tone_curves(curves, modes, n, _TONE_ITEM_DTYPE)
+        fmt = None
+        for i, (s, d) in enumerate(zip(srcs, outs)):
+            t, sp = _planes(s, i, "source", uint8=True)
+            u, dp = _planes(d, i, "output")
+            if str(u.dtype) not in _DTYPE_FORMATS or (fmt is not None and _DTYPE_FORMATS[str(u.dtype)] != fmt):
+                raise ValueError("outputs must be uint8 / float16 / float32 device tensors of one dtype")
+            fmt = _DTYPE_FORMATS[str(u.dtype)]
+            if tuple(u.shape) != tuple(t.shape):
+                raise ValueError(f"output {i} is {tuple(u.shape)}, its source {tuple(t.shape)}")
+            self._keep += [t, u]
+            for name, v in (("src", t.data_ptr()), ("dst", u.data_ptr()), ("w", t.shape[2]), ("h", t.shape[1]),
+                            ("src_pitch", sp), ("dst_pitch", dp)):
+                items[name][i] = int(v)
+        self.out_format = fmt if fmt is not None else OUT_RGB_PLANAR
+        self._create("create", normalize, items.ctypes.data_as(ctypes.POINTER(_lib.HjdToneItem)), n, self.out_format)
+
+
 def worker_cpus(bus: str, gpus: Sequence[str], sysfs_root: Optional[str] = None, only_allowed: bool = False):
     """hjd_debug_worker_cpus: the host CPUs the worker pool of the GPU at PCI
     address `bus` binds to, among the GPUs `gpus` (its NUMA node's CPUs split

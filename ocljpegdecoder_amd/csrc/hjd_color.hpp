@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hjd_quad.hpp"
 #include "hjd_store.hpp"
 
 namespace hjd {
@@ -37,20 +38,6 @@ namespace hjd {
 constexpr int kColorThreads = 256;
 constexpr int kColorMaxGroups = 256;   // hjd_internal::kMaxGroups: the rows of an image in the table of sums
 constexpr int kColorRound = 2048;      // half of Q12's 4096
-
-// The four bytes of columns j0 .. j0 + 3 of the row at `row` (lowest first;
-// 0 past column w): one dword where vec, else guarded byte loads.
-__device__ __forceinline__ uint32_t color_load_quad(__attribute__((address_space(1))) const uint8_t* row, uint32_t j0,
-                                                    uint32_t w, bool vec)
-{
-    typedef __attribute__((address_space(1))) const uint32_t gcword;
-    if (vec && j0 + 4 <= w) return *(gcword*)(row + j0);
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b)
-        if (j0 + b < w) v |= static_cast<uint32_t>(row[j0 + b]) << (8 * b);
-    return v;
-}
 
 // The sum of the four bytes of v.
 __device__ __forceinline__ uint32_t color_byte_sum(uint32_t v)
@@ -88,7 +75,7 @@ __global__ __launch_bounds__(kColorThreads) void color_sum_kernel(const ColorDev
         const uint32_t i = q / qw, j0 = 4 * (q - i * qw);
         const gcbyte* row = (const gcbyte*)it.src + static_cast<int64_t>(i) * it.pitch;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] += color_byte_sum(color_load_quad(row + c * splane, j0, w, vec));
+        for (int c = 0; c < 3; ++c) s[c] += color_byte_sum(load_quad(row + c * splane, j0, w, vec));
     }
     const uint32_t wave = threadIdx.x / 64;
 #pragma unroll
@@ -153,9 +140,9 @@ __global__ __launch_bounds__(kColorThreads) void color_kernel(const ColorDev* __
         const uint32_t i = q / qw, j0 = 4 * (q - i * qw);
         // (global, not flat, addresses: the record's pointers are device memory)
         const gcbyte* row = (const gcbyte*)it.src + static_cast<int64_t>(i) * it.pitch;
-        const uint32_t r4 = color_load_quad(row, j0, w, lvec);
-        const uint32_t g4 = color_load_quad(row + splane, j0, w, lvec);
-        const uint32_t b4 = color_load_quad(row + 2 * splane, j0, w, lvec);
+        const uint32_t r4 = load_quad(row, j0, w, lvec);
+        const uint32_t g4 = load_quad(row + splane, j0, w, lvec);
+        const uint32_t b4 = load_quad(row + 2 * splane, j0, w, lvec);
         uint32_t px[4];   // 0x00RRGGBB
 #pragma unroll
         for (int k = 0; k < 4; ++k) {

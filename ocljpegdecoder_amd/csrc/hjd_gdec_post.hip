@@ -17,6 +17,7 @@ using hjd_internal::ColorRecord;
 using hjd_internal::OrientRecord;
 using hjd_internal::ResizeRecord;
 using hjd_internal::set_error;
+using hjd_internal::ToneRecord;
 using hjd_internal::WarpRecord;
 using namespace hjd::ent;
 
@@ -206,6 +207,28 @@ int write_color_records(const PostStage& s, int n, ColorRecord* recs)
     return HJD_OK;
 }
 
+// The tone kernels' records: image i of the batch s.in (planar bytes in the scratch: the resize's,
+// the warp's, or the colour stage's in their place) through s.tones[i] to its place in the caller's batch.
+int write_tone_records(const PostStage& s, int n, ToneRecord* recs)
+{
+    for (int i = 0; i < n; ++i) {
+        ToneRecord& rec = recs[i];   // (written in place: a record is 808 bytes)
+        rec.src = s.in.ptrs[i];
+        rec.dst = static_cast<uint8_t*>(s.batch.ptr) +
+                  3 * static_cast<size_t>(s.batch.pitch) * static_cast<size_t>(s.batch.h) * static_cast<size_t>(i);
+        rec.w = s.batch.w;
+        rec.h = s.batch.h;
+        rec.pitch = s.in.pitches[i];
+        rec.dst_pitch = s.batch.pitch;
+        rec.mode = s.tones[i].mode;
+        rec.reserved = s.tones[i].reserved;
+        memcpy(rec.lut, s.tones[i].lut, sizeof(rec.lut));
+        const int rc = hjd_internal::tone_item_check(rec, i, s.out_format);
+        if (rc) return rc;
+    }
+    return HJD_OK;
+}
+
 }  // namespace
 
 int hjd::ent::post_write_records(hjd_gdec* g, const PostPlan& plan, int n)
@@ -220,6 +243,7 @@ int hjd::ent::post_write_records(hjd_gdec* g, const PostPlan& plan, int n)
         case PostKind::resize_aa: rc = write_resize_records(s, n, static_cast<ResizeRecord*>(recs)); break;
         case PostKind::warp: rc = write_warp_records(s, n, static_cast<WarpRecord*>(recs)); break;
         case PostKind::color: rc = write_color_records(s, n, static_cast<ColorRecord*>(recs)); break;
+        case PostKind::tone: rc = write_tone_records(s, n, static_cast<ToneRecord*>(recs)); break;
         }
         if (rc) return rc;
     }
@@ -254,6 +278,11 @@ int hjd::ent::post_launch(hjd_gdec* g, const PostPlan& plan, int n, hipStream_t 
             rc = hjd_internal::launch_color(g->device, static_cast<const ColorRecord*>(recs), n,
                                             hjd_internal::color_groups(s.batch.w, s.batch.h), s.sums, s.out_format,
                                             g->norm, stream);
+            break;
+        case PostKind::tone:
+            rc = hjd_internal::launch_tone(g->device, static_cast<const ToneRecord*>(recs), n,
+                                           hjd_internal::color_groups(s.batch.w, s.batch.h), s.hist, s.luts, s.out_format,
+                                           g->norm, stream);
             break;
         }
         if (rc) return rc;
@@ -326,15 +355,39 @@ int colors_check(const int32_t (*colors)[21], int n, bool* any, bool* sums)
     return HJD_OK;
 }
 
-// The scratch of a call's colour stage: `mid`, the batch the resize or warp writes in its place
-// (planar bytes), and `sums`, the table of partial sums where a record reads them.
+// The tone curves of a call: HJD_OK if every one is legal (else the refusal names the frame).
+// *any: one is not mode 0 with the identity table (else the call is the one without tones);
+// *data: one's mode is not 0, so the call takes histograms.  n has passed the call's own check.
+int tones_check(const hjd_tone_curve* tones, int n, bool* any, bool* data)
+{
+    *any = *data = false;
+    for (int i = 0; i < n; ++i) {
+        const int rc = hjd_internal::tone_curve_check(tones[i].mode, tones[i].reserved, i);
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        *data = *data || tones[i].mode != HJD_TONE_TABLE;
+        bool identity = tones[i].mode == HJD_TONE_TABLE;
+        for (int k = 0; identity && k < 768; ++k) identity = tones[i].lut[k >> 8][k & 255] == (k & 255);
+        *any = *any || !identity;
+    }
+    return HJD_OK;
+}
+
+// The scratch of a call's colour and tone stages: `mid`, the batch the resize or warp writes in
+// their place (planar bytes; with both, the colour stage runs on it in place); `sums`, the colour
+// stage's table of partial sums where a record reads them; `hist` and `luts`, the tone stage's
+// partial histograms and composed curves where a mode is not 0.
 struct ColorScratch {
-    Region mid, sums;
-    ColorScratch(bool on, bool with_sums, int n, int out_w, int out_h)
-        : mid(on ? static_cast<size_t>(n) : 0), sums(on && with_sums ? 1 : 0)
+    Region mid, sums, hist, luts;
+    ColorScratch(bool colors, bool color_sums, bool tones, bool tone_data, int n, int out_w, int out_h)
+        : mid(colors || tones ? static_cast<size_t>(n) : 0), sums(colors && color_sums ? 1 : 0),
+          hist(tones && tone_data ? 1 : 0), luts(tones && tone_data ? 1 : 0)
     {
-        if (on) mid.add_batch(out_w, out_h);
-        if (on && with_sums) sums.add_bytes(hjd_internal::color_sums_bytes(n));
+        if (colors || tones) mid.add_batch(out_w, out_h);
+        if (colors && color_sums) sums.add_bytes(hjd_internal::color_sums_bytes(n));
+        if (tones && tone_data) {
+            hist.add_bytes(hjd_internal::tone_hist_bytes(n));
+            luts.add_bytes(hjd_internal::tone_luts_bytes(n));
+        }
     }
 };
 
@@ -352,12 +405,30 @@ void add_color_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, con
     s.sums = c.sums.ptrs.empty() ? nullptr : static_cast<uint32_t*>(c.sums.ptrs[0]);
 }
 
-// hjd_gdec_decode_resized_filter (orientations null), hjd_gdec_decode_resized_oriented and
-// hjd_gdec_decode_resized_color (colors not null): decode to the scratch, with orientations
-// orient to a second scratch region, then the resize launches, then with colours the colour launches.
+// Put the tone stage behind `last`, the plan's resize, warp or colour stage, which wrote the caller's
+// batch in the decoder's format: it now writes planar bytes into c.mid (a colour stage, which reads
+// c.mid, then runs in place), and the tone stage that batch.
+void add_tone_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, const hjd_tone_curve* tones, int out_format,
+                    int n)
+{
+    const auto batch = last.batch;
+    last.out_format = HJD_OUT_RGB_PLANAR;
+    last.batch = {c.mid.ptrs[0], batch.w, batch.h, c.mid.pitches[0]};
+    PostStage& s = add_stage(plan, PostKind::tone, c.mid.images(), out_format, sizeof(ToneRecord) * static_cast<size_t>(n));
+    s.batch = batch;
+    s.tones = tones;
+    s.hist = c.hist.ptrs.empty() ? nullptr : static_cast<uint32_t*>(c.hist.ptrs[0]);
+    s.luts = c.luts.ptrs.empty() ? nullptr : static_cast<uint8_t*>(c.luts.ptrs[0]);
+}
+
+// hjd_gdec_decode_resized_filter (orientations null), hjd_gdec_decode_resized_oriented,
+// hjd_gdec_decode_resized_color (colors not null) and hjd_gdec_decode_resized_tone (tones not null):
+// decode to the scratch, with orientations orient to a second scratch region, then the resize
+// launches, then with colours the colour launches, then with tones the tone launches.
 int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
-                   const int32_t* orientations, const int32_t* flags, const int32_t (*colors)[21], void* d_out, int out_w,
-                   int out_h, int32_t out_pitch, int filter, void* stream)
+                   const int32_t* orientations, const int32_t* flags, const int32_t (*colors)[21],
+                   const hjd_tone_curve* tones, void* d_out, int out_w, int out_h, int32_t out_pitch, int filter,
+                   void* stream)
 {
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
@@ -384,10 +455,17 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
         if (rc) return rc;
         if (!any) colors = nullptr;   // every record the identity: the call without colours
     }
+    bool tone_data = false;
+    if (tones) {
+        bool any = false;
+        rc = tones_check(tones, n, &any, &tone_data);
+        if (rc) return rc;
+        if (!any) tones = nullptr;   // every curve the identity: the call without tones
+    }
     // (the scratch: the crops, an oriented call's oriented crops, the antialiased filter's intermediates)
     const size_t un = static_cast<size_t>(n);
     Region crops(un), oriented(orientations ? un : 0), mids(aa ? un : 0);
-    ColorScratch cs(colors != nullptr, color_sums, n, out_w, out_h);
+    ColorScratch cs(colors != nullptr, color_sums, tones != nullptr, tone_data, n, out_w, out_h);
     const Admit admit{g->scale, false, orientations ? kCapOriented : kCapResized,
                       orientations && rois ? orient_map : nullptr, orientations};
     int64_t tiles = 0;
@@ -416,7 +494,7 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     }
     rc = tiles_check(tiles);
     if (rc) return rc;
-    rc = grow_scratch(g, {&crops, &oriented, &mids, &cs.mid, &cs.sums},
+    rc = grow_scratch(g, {&crops, &oriented, &mids, &cs.mid, &cs.sums, &cs.hist, &cs.luts},
                       aa ? "crops and the resize's intermediate" : "crops");
     if (rc) return rc;
     PostPlan plan{0, {}, pixel_tables_bytes(n, rois != nullptr, false)};   // the pixel kernels' tables: planar bytes
@@ -434,14 +512,16 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     r.mids = mids.ptrs.data();
     r.max_h = max_h;
     if (colors) add_color_stage(plan, r, cs, colors, g->out_format, n);
+    if (tones) add_tone_stage(plan, plan.stage[plan.nstages - 1], cs, tones, g->out_format, n);
     return run_post(g, datas, sizes, n, stream, crops, rois != nullptr, plan);
 }
 
-// hjd_gdec_decode_warped (colors null) and hjd_gdec_decode_warped_color: decode the rectangle
-// each warp reads to the scratch, then the warp launch, then with colours the colour launches.
+// hjd_gdec_decode_warped (colors and tones null), hjd_gdec_decode_warped_color and
+// hjd_gdec_decode_warped_tone: decode the rectangle each warp reads to the scratch, then the warp
+// launch, then with colours the colour launches, then with tones the tone launches.
 int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
                   const int32_t* orientations, const int32_t* flags, const uint32_t* fills, const int32_t (*colors)[21],
-                  void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
+                  const hjd_tone_curve* tones, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
 {
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!m) return set_error(HJD_E_INVALID, "m is NULL");
@@ -460,11 +540,18 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
         if (rc) return rc;
         if (!any) colors = nullptr;   // every record the identity: the call without colours
     }
+    bool tone_data = false;
+    if (tones) {
+        bool any = false;
+        rc = tones_check(tones, n, &any, &tone_data);
+        if (rc) return rc;
+        if (!any) tones = nullptr;   // every curve the identity: the call without tones
+    }
     // per frame: the matrix on the stored image, the rectangle it reads (the
     // crop, in the scratch), the matrix on that crop
     const size_t un = static_cast<size_t>(n);
     Region crops(un);
-    ColorScratch cs(colors != nullptr, color_sums, n, out_w, out_h);
+    ColorScratch cs(colors != nullptr, color_sums, tones != nullptr, tone_data, n, out_w, out_h);
     std::vector<int32_t> mats(6 * un);
     const WarpMap wmap{m, orientations, out_w, out_h, reinterpret_cast<int32_t(*)[6]>(mats.data())};
     const Admit admit{g->scale, false, kCapWarped, warp_map, &wmap};
@@ -487,7 +574,7 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
             return set_error(HJD_E_INVALID, "frame %d: fill 0x%x is above 0xFFFFFF (0x00RRGGBB)", i, fills[i]);
         crops.add(i, r.w, r.h);
     }
-    rc = grow_scratch(g, {&crops, &cs.mid, &cs.sums}, "crops");
+    rc = grow_scratch(g, {&crops, &cs.mid, &cs.sums, &cs.hist, &cs.luts}, "crops");
     if (rc) return rc;
     PostPlan plan{0, {}, pixel_tables_bytes(n, true, false)};   // the pixel kernels' tables: planar bytes
     PostStage& w = add_stage(plan, PostKind::warp, crops.images(), g->out_format, sizeof(WarpRecord) * un);
@@ -496,6 +583,7 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
     w.mats = wmap.mats;
     w.fills = fills;
     if (colors) add_color_stage(plan, w, cs, colors, g->out_format, n);
+    if (tones) add_tone_stage(plan, plan.stage[plan.nstages - 1], cs, tones, g->out_format, n);
     return run_post(g, datas, sizes, n, stream, crops, true, plan);
 }
 
@@ -551,7 +639,7 @@ int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const siz
 int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                             const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
 {
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, d_out, out_w, out_h, out_pitch,
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
                           HJD_RESIZE_BILINEAR, stream);
 }
 
@@ -559,8 +647,8 @@ int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, con
                                    const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
                                    int32_t out_pitch, int filter, void* stream)
 {
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, d_out, out_w, out_h, out_pitch, filter,
-                          stream);
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
+                          filter, stream);
 }
 
 int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -568,8 +656,8 @@ int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, c
                                      int out_w, int out_h, int32_t out_pitch, int filter, void* stream)
 {
     if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, nullptr, d_out, out_w, out_h, out_pitch, filter,
-                          stream);
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
+                          filter, stream);
 }
 
 int hjd_gdec_decode_resized_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -578,15 +666,26 @@ int hjd_gdec_decode_resized_color(hjd_gdec* g, const uint8_t* const* datas, cons
                                   int filter, void* stream)
 {
     if (!colors) return set_error(HJD_E_INVALID, "colors is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, d_out, out_w, out_h, out_pitch, filter,
-                          stream);
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, nullptr, d_out, out_w, out_h, out_pitch,
+                          filter, stream);
+}
+
+int hjd_gdec_decode_resized_tone(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                                 const int32_t* orientations, const int32_t* flags, const int32_t (*colors)[21],
+                                 const hjd_tone_curve* tones, void* d_out, int out_w, int out_h, int32_t out_pitch,
+                                 int filter, void* stream)
+{
+    if (!tones) return set_error(HJD_E_INVALID, "tones is NULL");
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, tones, d_out, out_w, out_h, out_pitch,
+                          filter, stream);
 }
 
 int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
                            const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
                            int out_w, int out_h, int32_t out_pitch, void* stream)
 {
-    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, nullptr, d_out, out_w, out_h, out_pitch, stream);
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
+                         stream);
 }
 
 int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -595,7 +694,18 @@ int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const
                                  int32_t out_pitch, void* stream)
 {
     if (!colors) return set_error(HJD_E_INVALID, "colors is NULL");
-    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, d_out, out_w, out_h, out_pitch, stream);
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, nullptr, d_out, out_w, out_h, out_pitch,
+                         stream);
+}
+
+int hjd_gdec_decode_warped_tone(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
+                                const int32_t* orientations, const int32_t* flags, const uint32_t* fills,
+                                const int32_t (*colors)[21], const hjd_tone_curve* tones, void* d_out, int out_w, int out_h,
+                                int32_t out_pitch, void* stream)
+{
+    if (!tones) return set_error(HJD_E_INVALID, "tones is NULL");
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, tones, d_out, out_w, out_h, out_pitch,
+                         stream);
 }
 
 }  // extern "C"

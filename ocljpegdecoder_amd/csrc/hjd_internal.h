@@ -218,6 +218,7 @@ using ResizeRecord = hjd::ResizeDev;   // (the layout of hjd_resize_item, too)
 using OrientRecord = hjd::OrientDev;   // (of hjd_orient_item, whose reserved word is tile_begin here)
 using WarpRecord = hjd::WarpDev;       // (of hjd_warp_item)
 using ColorRecord = hjd::ColorDev;     // (of hjd_color_item, whose reserved word is use_sums here)
+using ToneRecord = hjd::ToneDev;       // (of hjd_tone_item)
 // a = 1, b = 0: the C default (out = (float)u8).
 inline NormRecord norm_identity() { return NormRecord{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}}; }
 // HJD_OK, or HJD_E_INVALID (NULL or non-finite constants) with the cause in the error string.
@@ -321,6 +322,24 @@ constexpr size_t color_sums_bytes(int n) { return static_cast<size_t>(n) * 256 *
 // records have passed the checks and carry use_sums.
 int launch_color(int device, const ColorRecord* d_items, int n, int groups, uint32_t* d_sums, int out_format,
                  const NormRecord& norm, void* stream);
+
+// The tone kernels (hjd_tone.hip; include/hjd.h hjd_tone_*).
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: n and the
+// format; the mode and the reserved word of one curve; and one item's side of
+// hjd_tone_check (the table is not looked at: every table is legal).
+int tone_out_check(int n, int out_format);
+int tone_curve_check(int32_t mode, int32_t reserved, int index);
+int tone_item_check(const ToneRecord& it, int index, int out_format);
+// The bytes of the table of partial histograms of n images, [n][16][3][256]
+// uint32, and of their composed curves, [n][3][256] bytes.
+constexpr size_t tone_hist_bytes(int n) { return static_cast<size_t>(n) * 16 * 768 * sizeof(uint32_t); }
+constexpr size_t tone_luts_bytes(int n) { return static_cast<size_t>(n) * 768; }
+// tone_hist_kernel and tone_lut_kernel (d_hist and d_luts not null: some
+// record's mode is not 0) and tone_kernel over n records in device memory (no
+// host synchronisation); `groups` as color_groups gives them, the largest
+// image's; the records have passed the checks.
+int launch_tone(int device, const ToneRecord* d_items, int n, int groups, uint32_t* d_hist, uint8_t* d_luts,
+                int out_format, const NormRecord& norm, void* stream);
 
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe

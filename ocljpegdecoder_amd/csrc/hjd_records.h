@@ -1,6 +1,7 @@
 // hjd_records.h -- the records the stage kernels and the float formats read, one
 // declaration each for the host that writes them (hjd_internal.h) and the
-// kernels (hjd_norm.hpp, hjd_resize.hpp, hjd_orient.hpp, hjd_warp.hpp, hjd_color.hpp).  No HIP.
+// kernels (hjd_norm.hpp, hjd_resize.hpp, hjd_orient.hpp, hjd_warp.hpp, hjd_color.hpp,
+// hjd_tone.hpp).  No HIP.
 #pragma once
 #include <stdint.h>
 
@@ -55,5 +56,16 @@ struct ColorDev {
     int32_t use_sums;           // some p is not 0: color_sum_kernel ran before color_kernel
 };
 static_assert(sizeof(ColorDev) == 120, "ColorDev layout");
+
+// One image of the tone kernels: the layout of hjd_tone_item.
+struct ToneDev {
+    const void* src;   // plane R; G and B follow at pitch * h
+    void* dst;         // plane R of the output; G and B follow at dst_pitch * h
+    int32_t w, h, pitch, dst_pitch;
+    int32_t mode;      // 0 the table alone, 1 autocontrast, 2 equalize in front of it
+    int32_t reserved;  // 0
+    uint8_t lut[3][256];   // u8_c = lut[c][D_c[x_c]]
+};
+static_assert(sizeof(ToneDev) == 808, "ToneDev layout");
 
 }  // namespace hjd

@@ -753,6 +753,80 @@ class GpuDecoder:
             self._n = n
         return self._with_settings(scale, fmt, norm, call, out)
 
+    @staticmethod
+    def _tones(curves, modes, n):
+        """The tone curves of a call: the numpy records (kept alive by the caller) and their hjd_tone_curve pointer."""
+        from .backend import _tone_curves
+        recs = _tone_curves(curves, modes, n)
+        return recs, recs.ctypes.data_as(ctypes.POINTER(_lib.HjdToneCurve))
+
+    def decode_rgb_resized_tone(self, datas: Sequence[bytes], size, flips=None, layout: str = "chw", out=None,
+                                stream=None, scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None,
+                                apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                                antialias=False, colors=None, curves=None, modes=None):
+        """decode_rgb_resized with a tone curve per image
+        (hjd_gdec_decode_resized_tone): image i goes through the table
+        curves[i] (uint8 (3, 256) or (256,), tone_curve() makes them: solarize,
+        posterize, gamma, invert), behind the data curve modes[i] --
+        TONE_TABLE (none), TONE_AUTOCONTRAST or TONE_EQUALIZE, built on the GPU
+        from the resized image's own histogram -- after the resize and after
+        colors[i] where colors (as decode_rgb_resized_color takes them) is
+        given, before the dtype's normalisation:
+        out[i] = normalise(table(data_curve(color(resize(orient(decode)))))).
+        curves and modes may each be None (TONE_IDENTITY, TONE_TABLE) or one
+        value for all images.  Every other parameter as decode_rgb_resized.
+        Curves that are all TONE_IDENTITY in TONE_TABLE make it exactly the
+        call without them."""
+        chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
+        if not chw:
+            raise ValueError('a resized batch is planar: layout must be "chw"')
+        n = len(datas)
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        cols = self._colors(colors, n) if colors is not None else None
+        recs, tones = self._tones(curves, modes, n)
+        out = self._batch_result(n, size, dtype, out)
+        fl = self._flips(flips, n)
+
+        def call():
+            _keep, arr_d, arr_s = _byte_arrays(datas)
+            ho, wo = int(out.shape[2]), int(out.shape[3])
+            check(self.lib.hjd_gdec_decode_resized_tone(
+                self.handle, arr_d, arr_s, n, self._rects(rois, n),
+                (ctypes.c_int32 * n)(*orients) if orients is not None else None, fl, cols, tones, out.data_ptr(), wo,
+                ho, wo * out.element_size(), 1 if antialias else 0, _stream_handle(stream)),
+                "hjd_gdec_decode_resized_tone")
+            self._n = n
+        return self._with_settings(scale, fmt, norm, call, out)
+
+    def decode_rgb_warped_tone(self, datas: Sequence[bytes], size, xforms, fill=0, replicate=False, out=None,
+                               stream=None, scale: int = 1, dtype=_UINT8, mean=None, std=None,
+                               apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                               colors=None, curves=None, modes=None):
+        """decode_rgb_warped with a tone curve per image
+        (hjd_gdec_decode_warped_tone):
+        out[i] = normalise(table(data_curve(color(warp(decode))))), curves,
+        modes and colors as decode_rgb_resized_tone takes them (a histogram is
+        that of the warped image, its fill included).  Every other parameter
+        as decode_rgb_warped."""
+        _chw, dtype, fmt, norm = self._rgb_format("chw", dtype, mean, std)
+        n = len(datas)
+        mats, fl, fi = self._warp_arrays(xforms, list(fill) if isinstance(fill, (list, tuple)) else [fill] * n,
+                                         replicate, n)
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        cols = self._colors(colors, n) if colors is not None else None
+        recs, tones = self._tones(curves, modes, n)
+        out = self._batch_result(n, size, dtype, out)
+
+        def call():
+            _keep, arr_d, arr_s = _byte_arrays(datas)
+            ho, wo = int(out.shape[2]), int(out.shape[3])
+            check(self.lib.hjd_gdec_decode_warped_tone(
+                self.handle, arr_d, arr_s, n, mats, (ctypes.c_int32 * n)(*orients) if orients is not None else None,
+                fl, fi, cols, tones, out.data_ptr(), wo, ho, wo * out.element_size(), _stream_handle(stream)),
+                "hjd_gdec_decode_warped_tone")
+            self._n = n
+        return self._with_settings(scale, fmt, norm, call, out)
+
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
         returns each frame's first block."""
