@@ -790,9 +790,10 @@ int hjd_color_destroy(hjd_color* c);
  * exact floor, and that is the documented difference.
  *
  * What it leaves out.  autocontrast's `cutoff` (lo and hi are the extreme
- * non-empty bins); sharpness and blur, which are not pointwise; and any order
- * other than colour (hjd_color, where a caller runs it first) -> data curve ->
- * table: a table in front of the data curve is not a record.
+ * non-empty bins); sharpness and blur, which are not pointwise (they are the
+ * filters of hjd_conv below); and any order other than colour (hjd_color,
+ * where a caller runs it first) -> data curve -> table: a table in front of
+ * the data curve is not a record.
  *
  * In place: for HJD_OUT_RGB_PLANAR an item with dst == src and dst_pitch ==
  * src_pitch is legal -- a thread reads its four pixels before it writes them
@@ -841,6 +842,111 @@ int hjd_tone_destroy(hjd_tone* t);
  * Host only: needs no device. */
 int hjd_tone_curve_from_histogram(int mode, const uint32_t hist[3][256], const uint8_t lut_in[3][256],
                                   uint8_t lut_out[3][256]);
+
+/*
+ * Neighbourhood filters (extension; the reference has none): n planar uint8
+ * RGB images, each of its own size, each through its own small separable
+ * filter with a blend against the centre pixel, in ONE launch: sharpness (the
+ * one operation of RandAugment / AutoAugment / TrivialAugment that is not
+ * pointwise), Gaussian blur (SimCLR / BYOL / DINO: up to 23 taps), unsharp
+ * masking.
+ *
+ * Source and output: exactly as hjd_color's and hjd_tone's -- three uint8
+ * planes R, G, B of w x h, rows src_pitch bytes apart, planes src_pitch * h
+ * apart, any pointer and any src_pitch >= w, both dimensions in 1..16384; the
+ * same w x h out, in HJD_OUT_RGB_PLANAR (the bytes u8), HJD_OUT_RGB_PLANAR_F16
+ * or _F32 (fma((float)u8, a[c], b[c]), hjd_conv_set_normalize, default a = 1,
+ * b = 0); every item its own dst and dst_pitch, multiples of the element size,
+ * dst_pitch >= w x the element size, planes dst_pitch * h apart.  Nothing
+ * outside the image's own elements is written.
+ *
+ * Definition (exact, integer).  A filter is two radii rx, ry in 0..11, a
+ * border rule, two rows of Q12 taps kh[0..2 rx], kv[0..2 ry] (the entries
+ * beyond are 0; each row sums to 1..4096) and two Q12 gains a, b, |a|, |b| <=
+ * 2^20.  Per plane, x the source byte at column j of row i:
+ *     S  = sum over q = -ry..ry, p = -rx..rx of
+ *          kv[q + ry] * kh[p + rx] * X(j + p, i + q)
+ *          (<= 255 * 2^24: it fits uint32 and not int32)
+ *     T  = a * (x << 24) + b * S            (int64, |T| < 2^53)
+ *     u8 = clamp((T + 2^35) >> 36, 0, 255)  (an arithmetic shift: one rounding)
+ * What X is outside the image, by `border`:
+ *   HJD_CONV_REFLECT:  index -k -> k and n - 1 + k -> n - 1 - k (torch's
+ *     "reflect", scipy's "mirror").  Needs rx < w and ry < h.
+ *   HJD_CONV_REPLICATE:  the index is clamped to the edge.
+ *   HJD_CONV_KEEP:  a pixel with j < rx, j >= w - rx, i < ry or i >= h - ry is
+ *     copied (u8 = x); the others never read outside.  This is what Pillow's
+ *     3 x 3 filters and torchvision's adjust_sharpness do.  With 2 rx >= w or
+ *     2 ry >= h the whole image is copied.
+ *
+ * Laws.  rx = ry = 0, a = 4096, b = 0 (kh[0] = kv[0] = 4096) is the identity
+ * record: a byte-for-byte copy.  Taps that sum to 4096 on both axes with a =
+ * 0, b = 4096 give (S + 2^23) >> 24: a flat image stays flat, 255 included.
+ * Channels are independent.  Every sum is of integers: no result depends on
+ * the launch's shape or the order of the additions.
+ *
+ * Agreement with Pillow (12.2.0, checked on the CPU by tests/test_conv_cpu.py
+ * where Pillow is installed).  ImageEnhance.Sharpness(im).enhance(f) blends
+ * im with its SMOOTH filter ((box + 4 x) / 13 under KEEP): the record rx = ry
+ * = 1, taps 1024 x 3 on both axes, a = round(4096 (4 + 9 f) / 13), b =
+ * round(65536 (1 - f) / 13) is that real map f x + (1 - f) (box + 4 x) / 13
+ * with one rounding, within 0.55 grey level of it.  Pillow rounds the smoothed
+ * image and then truncates the blend, so the two differ by at most 2 for f in
+ * 0..2 (asserted); measured over f in {0, 0.1, 0.5, 1, 1.5, 1.9, 2} on random,
+ * checkerboard and 0/255 images the largest difference is 1, in 14.06 % of the
+ * pixels overall (45.8 % at worst: f = 0.1 on a checkerboard), and none at
+ * f = 0, 1 and 2.
+ *
+ * What it leaves out.  Pillow's ImageFilter.GaussianBlur, which is a repeated
+ * box blur and not this map (the taps here are torchvision's sampled
+ * Gaussian); kernels that are not "separable + centre"; radii above 11; median
+ * and rank filters.
+ *
+ * Overlap: a filter cannot run in place, so dst == src is refused; any other
+ * overlap of an output with a source or another output is the caller's error;
+ * it is not looked for.  The tiles of all items of one object, 64 x 32 pixels
+ * each, must number below 2^31.
+ */
+enum { HJD_CONV_KEEP = 0, HJD_CONV_REFLECT = 1, HJD_CONV_REPLICATE = 2 };
+#define HJD_CONV_MAX_RADIUS 11            /* 23 taps per axis */
+#define HJD_CONV_MAX_GAIN   (1 << 20)     /* |a|, |b| in Q12: up to +-256.0 */
+typedef struct hjd_conv_filter {
+    int32_t rx, ry;        /* 0..HJD_CONV_MAX_RADIUS */
+    int32_t border;        /* HJD_CONV_* */
+    int32_t a, b;          /* Q12 */
+    int32_t reserved;      /* 0 */
+    uint16_t kh[24], kv[24];   /* kh[0..2rx], kv[0..2ry]; the rest 0; each row sums to 1..4096 */
+} hjd_conv_filter;         /* 120 bytes */
+typedef struct hjd_conv_item {
+    const void* src;   /* device: plane R of the source */
+    void* dst;         /* device: plane R of the output */
+    int32_t w, h, src_pitch, dst_pitch;
+    hjd_conv_filter filter;
+} hjd_conv_item;       /* 152 bytes */
+typedef struct hjd_conv hjd_conv;
+/* Validates what hjd_conv_create would take.  HJD_E_INVALID (with a message)
+ * for n outside 1..2^20, a NULL items / src / dst, a dimension outside
+ * 1..16384, src_pitch < w, a bad dst_pitch or dst alignment, dst == src, a
+ * radius outside 0..11, a border outside 0..2, HJD_CONV_REFLECT with a radius
+ * >= the dimension, a tap row summing to 0 or above 4096, a non-zero tap
+ * beyond 2 r, |a| or |b| above 2^20, a non-zero reserved, a non-planar or
+ * unknown format, and 2^31 tiles or more in all.  Host only: needs no device. */
+int hjd_conv_check(const hjd_conv_item* items, int n, int out_format);
+/* Validates and uploads the item table (synchronously). */
+int hjd_conv_create(hjd_ctx* ctx, const hjd_conv_item* items, int n, int out_format, hjd_conv** out);
+/* The float formats' constants for the launches that follow (an enqueued
+ * launch keeps its own).  HJD_E_INVALID for non-finite constants and for a
+ * byte-format object. */
+int hjd_conv_set_normalize(hjd_conv* c, const float a[3], const float b[3]);
+/* Enqueue the filters of all n items on `stream` (asynchronous; one kernel). */
+int hjd_conv_launch(hjd_conv* c, void* stream);
+int hjd_conv_destroy(hjd_conv* c);
+/* The filter *f on one image of three planes on the host: src and dst as an
+ * item's (planes src_pitch * h and dst_pitch * h apart, uint8 out), by the two
+ * functions the device's kernel calls for the border and the finish.
+ * HJD_E_INVALID for what hjd_conv_check refuses of the filter and the sizes.
+ * Host only: needs no device. */
+int hjd_conv_apply_host(const uint8_t* src, int w, int h, int src_pitch, const hjd_conv_filter* f, uint8_t* dst,
+                        int dst_pitch);
 
 /* IDCT only (the reference's batch_idct, src/idct8x8.cl:157-166), out of
  * place: int32 natural-order dequantised blocks -> int32 samples [-256,255]. */

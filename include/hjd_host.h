@@ -364,6 +364,38 @@ int hjd_gdec_decode_warped_tone(hjd_gdec* g, const uint8_t* const* datas, const 
                                 const int32_t (*m)[6], const int32_t* orientations, const int32_t* flags,
                                 const uint32_t* fills, const int32_t (*colors)[21], const hjd_tone_curve* tones,
                                 void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream);
+/* The calls that take every optional stage: a colour record, a filter
+ * (include/hjd.h hjd_conv_filter: sharpness, Gaussian blur, unsharp masking)
+ * and a tone curve per frame, each of colors, convs and tones NULL for none.
+ * Image i of the batch is tone(conv(color(resize(orient(decode))))) or
+ * tone(conv(color(warp(decode)))) -- jitter, blur, solarize: BYOL's order --
+ * the filter's borders those of the out_w x out_h image the resize or warp
+ * wrote (its fill included), a tone curve's histogram that of the filtered
+ * image.
+ *
+ * Built as that composition: the resize or warp launch writes planar bytes
+ * into the region of the scratch the colour and tone calls use, a colour stage
+ * runs on that region in place, the filter launch reads it and writes d_out in
+ * the decoder's format with the decoder's constants -- or, where a tone stage
+ * follows, a second region of the same layout (a filter cannot run in place),
+ * which the tone launch reads.  A call whose filters are all the identity
+ * record (rx = ry = 0, a = 4096, b = 0) has no filter stage and no second
+ * region: it is exactly hjd_gdec_decode_resized_tone / _warped_tone, and with
+ * colors and tones NULL or the identity as well the call without stages.
+ * Everything that can refuse the call -- all that the call without filters
+ * refuses and all that hjd_conv_check refuses of a filter for an image of
+ * out_w x out_h, HJD_CONV_REFLECT with a radius >= out_w or out_h included
+ * (HJD_E_INVALID naming the frame) -- is checked before anything is staged,
+ * allocated or enqueued. */
+int hjd_gdec_decode_resized_aug(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                                const hjd_rect* rois, const int32_t* orientations, const int32_t* flags,
+                                const int32_t (*colors)[21], const hjd_conv_filter* convs, const hjd_tone_curve* tones,
+                                void* d_out, int out_w, int out_h, int32_t out_pitch, int filter, void* stream);
+int hjd_gdec_decode_warped_aug(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
+                               const int32_t (*m)[6], const int32_t* orientations, const int32_t* flags,
+                               const uint32_t* fills, const int32_t (*colors)[21], const hjd_conv_filter* convs,
+                               const hjd_tone_curve* tones, void* d_out, int out_w, int out_h, int32_t out_pitch,
+                               void* stream);
 /* Bytes of the most recent decode call: scan bytes the host CPU read + wrote
  * (0 when every scan was destuffed on the GPU) and bytes moved host -> device. */
 int hjd_gdec_last_bytes(hjd_gdec* g, int64_t* host_scan_bytes, int64_t* h2d_bytes);

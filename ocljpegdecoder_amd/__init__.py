@@ -41,6 +41,15 @@ from .backend import (  # noqa: E402
     TONE_IDENTITY,
     TONE_TABLE,
     tone_curve,
+    Conv,
+    CONV_IDENTITY,
+    CONV_KEEP,
+    CONV_REFLECT,
+    CONV_REPLICATE,
+    conv_filter,
+    conv_gaussian,
+    conv_sharpness,
+    conv_unsharp,
     Context,
     cpu_share,
     debug_tuning,
@@ -88,5 +97,7 @@ __all__ = [
     "Warp", "WARP_REPLICATE", "warp_roi", "warp_orient", "warp_xform",
     "Color", "COLOR_IDENTITY", "color_matrix",
     "Tone", "TONE_TABLE", "TONE_AUTOCONTRAST", "TONE_EQUALIZE", "TONE_IDENTITY", "tone_curve",
+    "Conv", "CONV_KEEP", "CONV_REFLECT", "CONV_REPLICATE", "CONV_IDENTITY", "conv_filter", "conv_sharpness", "conv_gaussian",
+    "conv_unsharp",
     "YUV444", "YUV420", "YUV422", "GRAY", "YUV411_H4V1", "YUV440", "OTHER", "block_components", "KERNEL_AUTO", "KERNEL_PERSISTENT", "KERNEL_LATENCY", "OUT_BGRX", "OUT_BGR24", "OUT_RGB24", "OUT_RGB_PLANAR", "OUT_BYTES", "default_pitch", "IN_Q16_ZIGZAG", "IN_I32_NATURAL",
 ]

@@ -91,6 +91,21 @@ class HjdToneItem(ctypes.Structure):
 assert ctypes.sizeof(HjdToneCurve) == 776 and ctypes.sizeof(HjdToneItem) == 808
 
 
+class HjdConvFilter(ctypes.Structure):
+    """struct hjd_conv_filter (include/hjd.h): radii, border, gains and two rows of taps."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rx", "ry", "border", "a", "b", "reserved")] + \
+               [("kh", ctypes.c_uint16 * 24), ("kv", ctypes.c_uint16 * 24)]
+
+
+class HjdConvItem(ctypes.Structure):
+    """struct hjd_conv_item (include/hjd.h): one image of a filter launch."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("w", "h", "src_pitch", "dst_pitch")] + [("filter", HjdConvFilter)]
+
+
+assert ctypes.sizeof(HjdConvFilter) == 120 and ctypes.sizeof(HjdConvItem) == 152
+
+
 class HjdLaunchShape(ctypes.Structure):
     """struct hjd_launch_shape (include/hjd.h)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "tasks_per_wave", "max_tasks_per_wave", "grid", "variant",
@@ -219,6 +234,15 @@ SIGNATURES = {
     "hjd_tone_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hjd_tone_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hjd_tone_curve_from_histogram": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_conv_check": (ctypes.c_int, [ctypes.POINTER(HjdConvItem), ctypes.c_int, ctypes.c_int]),
+    "hjd_conv_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HjdConvItem), ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(ctypes.c_void_p)]),
+    "hjd_conv_set_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float)]),
+    "hjd_conv_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hjd_conv_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hjd_conv_apply_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(HjdConvFilter), ctypes.c_void_p, ctypes.c_int]),
     "hjd_idct_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]),
     "hjd_debug_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -346,6 +370,16 @@ def _bind_host(lib):
                                                        c_i32p, c_u32p, ctypes.POINTER(ctypes.c_int32 * 21),
                                                        ctypes.POINTER(HjdToneCurve), vp, ctypes.c_int, ctypes.c_int,
                                                        ctypes.c_int32, vp]),
+        "hjd_gdec_decode_resized_aug": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                       ctypes.c_int, ctypes.POINTER(HjdRect), c_i32p, c_i32p,
+                                                       ctypes.POINTER(ctypes.c_int32 * 21), ctypes.POINTER(HjdConvFilter),
+                                                       ctypes.POINTER(HjdToneCurve), vp, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int32, ctypes.c_int, vp]),
+        "hjd_gdec_decode_warped_aug": (ctypes.c_int, [vp, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                                      ctypes.c_int, ctypes.POINTER(ctypes.c_int32 * 6), c_i32p,
+                                                      c_i32p, c_u32p, ctypes.POINTER(ctypes.c_int32 * 21),
+                                                      ctypes.POINTER(HjdConvFilter), ctypes.POINTER(HjdToneCurve), vp,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp]),
         "hjd_gdec_last_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "hjd_gstream_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.POINTER(vp)]),

@@ -1026,6 +1026,188 @@ class Tone(_Stage):
         self._create("create", normalize, items.ctypes.data_as(ctypes.POINTER(_lib.HjdToneItem)), n, self.out_format)
 
 
+CONV_KEEP, CONV_REFLECT, CONV_REPLICATE = 0, 1, 2   # include/hjd.h HJD_CONV_*: what a filter reads outside the image
+CONV_MAX_RADIUS, CONV_MAX_GAIN = 11, 1 << 20        # include/hjd.h HJD_CONV_MAX_*
+# struct hjd_conv_filter and struct hjd_conv_item (include/hjd.h) as numpy records
+_CONV_FILTER_FIELDS = [("rx", "<i4"), ("ry", "<i4"), ("border", "<i4"), ("a", "<i4"), ("b", "<i4"), ("reserved", "<i4"),
+                       ("kh", "<u2", (24,)), ("kv", "<u2", (24,))]
+_CONV_FILTER_DTYPE = np.dtype(_CONV_FILTER_FIELDS)
+_CONV_ITEM_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("w", "<i4"), ("h", "<i4"), ("src_pitch", "<i4"),
+                             ("dst_pitch", "<i4")] + _CONV_FILTER_FIELDS)
+assert _CONV_FILTER_DTYPE.itemsize == 120 and _CONV_ITEM_DTYPE.itemsize == 152
+
+
+def conv_filter(kh, kv, a, b, border=CONV_REFLECT):
+    """One hjd_conv_filter record (a 0-d numpy record of 120 bytes) from two
+    odd-length rows of Q12 integer taps and two Q12 integer gains:
+    u8 = clamp((a (x << 24) + b S + 2^35) >> 36), S the window under kv x kh
+    (include/hjd.h).  ValueError unless the rows are 1, 3, .. 23 integers in
+    0..4096; the other ranges are the library's to refuse."""
+    f = np.zeros((), dtype=_CONV_FILTER_DTYPE)
+    for name, radius, taps in (("kh", "rx", kh), ("kv", "ry", kv)):
+        t = [int(v) for v in taps]
+        if len(t) % 2 != 1 or len(t) > 2 * CONV_MAX_RADIUS + 1 or any(v != u or not 0 <= v <= 4096 for v, u in zip(t, taps)):
+            raise ValueError(f"{name} is 1, 3, .. {2 * CONV_MAX_RADIUS + 1} integer taps in 0..4096 (Q12)")
+        f[name][:len(t)] = t
+        f[radius] = len(t) // 2
+    for name, v in (("a", a), ("b", b), ("border", border)):
+        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f"{name} is an int32")
+        f[name] = int(v)
+    return f
+
+
+CONV_IDENTITY = conv_filter([4096], [4096], 4096, 0, CONV_KEEP)   # a filter that copies: rx = ry = 0, a = 4096, b = 0
+CONV_IDENTITY.setflags(write=False)
+
+
+def conv_sharpness(factor):
+    """The filter of a sharpness factor f >= 0 (Pillow's ImageEnhance.Sharpness,
+    torchvision's adjust_sharpness): the real map f x + (1 - f) (box + 4 x) / 13,
+    box the sum of the 3 x 3 window, with ONE rounding -- rx = ry = 1,
+    CONV_KEEP, taps (1024, 1024, 1024) on both axes, a = round(4096 (4 + 9 f) /
+    13), b = round(65536 (1 - f) / 13).  f = 0 smooths, 1 is CONV_IDENTITY, 2
+    sharpens.  Pillow rounds the smoothed image and truncates the blend: within
+    2 grey levels for f in 0..2 (include/hjd.h has what was measured)."""
+    import math
+    f = float(factor)
+    if not (math.isfinite(f) and f >= 0.0):
+        raise ValueError("factor must be a finite number >= 0")
+    if f == 1.0:
+        return CONV_IDENTITY.copy()
+    a, b = int(math.floor(4096.0 * (4.0 + 9.0 * f) / 13.0 + 0.5)), int(math.floor(65536.0 * (1.0 - f) / 13.0 + 0.5))
+    if abs(a) > CONV_MAX_GAIN or abs(b) > CONV_MAX_GAIN:
+        raise ValueError(f"factor {factor}: a gain leaves +-2^20 (Q12)")
+    return conv_filter([1024] * 3, [1024] * 3, a, b, CONV_KEEP)
+
+
+def _gaussian_real(sigma, ksize):
+    """torchvision's taps in float64: exp(-(t / sigma)^2 / 2) on linspace(-(k - 1) / 2, (k - 1) / 2, k), normalised."""
+    t = np.linspace(-(ksize - 1) / 2.0, (ksize - 1) / 2.0, ksize)
+    k = np.exp(-0.5 * (t / float(sigma)) ** 2)
+    return k / k.sum()
+
+
+def _gaussian_taps(sigma, ksize):
+    """_gaussian_real in Q12 by largest remainder, so the row sums to exactly
+    4096 (ties: nearer the centre, then the lower index); zero taps at both
+    ends trimmed symmetrically."""
+    import math
+    if not (math.isfinite(float(sigma)) and float(sigma) > 0.0):
+        raise ValueError("sigma must be a finite number > 0")
+    if ksize is None:
+        ksize = min(2 * CONV_MAX_RADIUS + 1, 2 * int(math.ceil(3.0 * float(sigma))) + 1)
+    if int(ksize) != ksize or int(ksize) % 2 != 1 or not 1 <= int(ksize) <= 2 * CONV_MAX_RADIUS + 1:
+        raise ValueError(f"ksize is odd, 1..{2 * CONV_MAX_RADIUS + 1}")
+    ksize = int(ksize)
+    scaled = _gaussian_real(sigma, ksize) * 4096.0
+    q = np.floor(scaled).astype(np.int64)
+    frac = scaled - q
+    order = sorted(range(ksize), key=lambda i: (-frac[i], abs(i - ksize // 2), i))
+    for i in order[:4096 - int(q.sum())]:
+        q[i] += 1
+    q = [int(v) for v in q]
+    assert sum(q) == 4096
+    while len(q) > 1 and q[0] == 0 and q[-1] == 0:
+        q = q[1:-1]
+    return q
+
+
+def _ksizes(ksize):
+    return tuple(ksize) if isinstance(ksize, (list, tuple)) else (ksize, ksize)
+
+
+def conv_gaussian(sigma, ksize=None, sigma_y=None, border=CONV_REFLECT):
+    """The filter of a Gaussian blur (torchvision's GaussianBlur): per axis the
+    taps exp(-(t / sigma)^2 / 2) on linspace(-(k - 1) / 2, (k - 1) / 2, k),
+    normalised, quantised to Q12 by largest remainder so each row sums to
+    exactly 4096, zero taps at both ends trimmed (the radius shrinks); a = 0,
+    b = 4096, so u8 = (S + 2^23) >> 24.  ksize: odd, 1..23, one number or (kx,
+    ky); None: 2 ceil(3 sigma) + 1, capped at 23.  sigma_y: the vertical
+    sigma (None: sigma).  This is NOT Pillow's GaussianBlur, a repeated box blur."""
+    kx, ky = _ksizes(ksize)
+    return conv_filter(_gaussian_taps(sigma, kx), _gaussian_taps(sigma if sigma_y is None else sigma_y, ky), 0, 4096, border)
+
+
+def conv_unsharp(sigma, amount, ksize=None, border=CONV_REFLECT):
+    """Unsharp masking, x + amount (x - blur(x)): conv_gaussian's taps with
+    a = round(4096 (1 + amount)), b = round(-4096 amount), one rounding."""
+    import math
+    m = float(amount)
+    if not math.isfinite(m):
+        raise ValueError("amount must be finite")
+    a, b = int(math.floor(4096.0 * (1.0 + m) + 0.5)), int(math.floor(-4096.0 * m + 0.5))
+    if abs(a) > CONV_MAX_GAIN or abs(b) > CONV_MAX_GAIN:
+        raise ValueError(f"amount {amount}: a gain leaves +-2^20 (Q12)")
+    kx, ky = _ksizes(ksize)
+    return conv_filter(_gaussian_taps(sigma, kx), _gaussian_taps(sigma, ky), a, b, border)
+
+
+def _conv_filters(filters, n, dtype=_CONV_FILTER_DTYPE):
+    """n records of `dtype` (hjd_conv_filter, or hjd_conv_item with its other fields 0) from `filters`
+    -- None (all CONV_IDENTITY), one record for all images or n records (conv_filter() and its kin make
+    them).  ValueError for wrong counts and for anything that is not such a record."""
+    recs = np.zeros(max(1, n), dtype=dtype)
+
+    def one(f, what):
+        f = np.asarray(f)
+        if f.dtype != _CONV_FILTER_DTYPE or f.shape != ():
+            raise ValueError(f"{what} is not a filter record (conv_filter(), conv_sharpness(), conv_gaussian(), "
+                             "conv_unsharp())")
+        return f
+
+    if filters is None or (isinstance(filters, np.ndarray) and filters.shape == ()):
+        f = one(CONV_IDENTITY if filters is None else filters, "filters")
+        for name, *_ in _CONV_FILTER_FIELDS:
+            recs[name][:] = f[name]
+    else:
+        if len(filters) != n:
+            raise ValueError("one filter record per image, or one for all")
+        for i, f in enumerate(filters):
+            f = one(f, f"filter {i}")
+            for name, *_ in _CONV_FILTER_FIELDS:
+                recs[name][i] = f[name]
+    return recs
+
+
+class Conv(_Stage):
+    """hjd_conv: N planar uint8 RGB images of different sizes, each through its
+    own small separable filter with a blend against the centre pixel
+    (conv_sharpness(), conv_gaussian(), conv_unsharp() make the records) into
+    its own output of the same size, in one launch (include/hjd.h: exact
+    integers, one rounding)."""
+    _prefix = "hjd_conv"
+
+    def __init__(self, ctx: Context, srcs, outs, filters=None, normalize=None):
+        """srcs and outs as Color takes them, but no out may be its source: a
+        filter cannot run in place.  filters: N filter records, one for all, or
+        None (CONV_IDENTITY).  normalize = (a, b): the float dtypes' constants."""
+        super().__init__(ctx)
+        n = len(srcs)
+        if not isinstance(outs, (list, tuple)):
+            if not (outs.ndim == 4 and outs.shape[0] == n):
+                raise ValueError(f"outs must be {n} tensors or one (N, 3, h, w) tensor of {n} images")
+            outs = [outs[i] for i in range(n)]
+        if len(outs) != n:
+            raise ValueError("one output per source")
+        items = _conv_filters(filters, n, _CONV_ITEM_DTYPE)
+        fmt = None
+        for i, (s, d) in enumerate(zip(srcs, outs)):
+            t, sp = _planes(s, i, "source", uint8=True)
+            u, dp = _planes(d, i, "output")
+            if str(u.dtype) not in _DTYPE_FORMATS or (fmt is not None and _DTYPE_FORMATS[str(u.dtype)] != fmt):
+                raise ValueError("outputs must be uint8 / float16 / float32 device tensors of one dtype")
+            fmt = _DTYPE_FORMATS[str(u.dtype)]
+            if tuple(u.shape) != tuple(t.shape):
+                raise ValueError(f"output {i} is {tuple(u.shape)}, its source {tuple(t.shape)}")
+            self._keep += [t, u]
+            for name, v in (("src", t.data_ptr()), ("dst", u.data_ptr()), ("w", t.shape[2]), ("h", t.shape[1]),
+                            ("src_pitch", sp), ("dst_pitch", dp)):
+                items[name][i] = int(v)
+        self.out_format = fmt if fmt is not None else OUT_RGB_PLANAR
+        self._create("create", normalize, items.ctypes.data_as(ctypes.POINTER(_lib.HjdConvItem)), n, self.out_format)
+
+
 def worker_cpus(bus: str, gpus: Sequence[str], sysfs_root: Optional[str] = None, only_allowed: bool = False):
     """hjd_debug_worker_cpus: the host CPUs the worker pool of the GPU at PCI
     address `bus` binds to, among the GPUs `gpus` (its NUMA node's CPUs split

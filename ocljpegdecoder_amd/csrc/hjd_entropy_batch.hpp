@@ -92,15 +92,16 @@ inline Caps make_caps(int max_frames, int64_t max_scan_bytes, int64_t max_blocks
     // (the ResizeRecords: a resized call's records follow the pixel kernel's
     // tables, two per frame with the antialiased filter; an oriented call's
     // OrientRecords lie between the two; a warped call's WarpRecords take
-    // their place; a colour call's ColorRecords and a tone call's ToneRecords
-    // follow either)
+    // their place; a colour call's ColorRecords, a filter call's ConvRecords
+    // and a tone call's ToneRecords follow either, in that order)
     const size_t per_frame = (sizeof(EntFrame) + sizeof(HuffLut) * kMaxTables + 8) * kMaxScans + 192 * 4 +
                              sizeof(RawFrame) + 4 + 2 * sizeof(hjd_internal::ResizeRecord) +
                              sizeof(hjd_internal::OrientRecord) + sizeof(hjd_internal::WarpRecord) +
-                             sizeof(hjd_internal::ColorRecord) + sizeof(hjd_internal::ToneRecord);
+                             sizeof(hjd_internal::ColorRecord) + sizeof(hjd_internal::ConvRecord) +
+                             sizeof(hjd_internal::ToneRecord);
     // + the pixel kernel's frame tables at their largest (a ROI call in a float format)
     c.hdr_cap = align_up(per_frame * max_frames + 4 * static_cast<size_t>(c.max_segs + c.max_wgs + c.max_tiles) +
-                             pixel_tables_bytes(max_frames, true, true) + 10 * kAlign, kAlign);
+                             pixel_tables_bytes(max_frames, true, true) + 11 * kAlign, kAlign);
     c.data = c.hdr_cap;
     return c;
 }

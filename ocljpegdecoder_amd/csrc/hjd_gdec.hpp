@@ -53,8 +53,9 @@ struct hjd_gdec {
     uint32_t* d_tiles = nullptr;        // destuff scratch [3][max_tiles]
     uint8_t* d_crops = nullptr;         // the scratch of a call with stages (hjd_gdec_post.hip): the crops the pixel
                                         // kernels write, then what one stage hands the next (oriented crops, the
-                                        // antialiased filter's intermediates, the batch the colour and tone stages read,
-                                        // the colour stage's partial sums, the tone stage's histograms and curves);
+                                        // antialiased filter's intermediates, the batch the colour, filter and tone stages
+                                        // read, the filter stage's batch for a tone stage behind it, the colour
+                                        // stage's partial sums, the tone stage's histograms and curves);
     size_t crops_bytes = 0;             // grow-only, (re)allocated by a call that needs more, behind the previous call
     bool spec = false;                  // speculative sync (latency decoders: ent_spec/cand/sync_spec kernels)
     hjd::ent::SpecRec* d_spec = nullptr;   // [max_subs][kMaxBpm]
@@ -115,13 +116,13 @@ struct PostImages {
 // One stage: its kind's launch (resize_aa: its two) over one record per image.  It reads `in` -- the
 // images the pixel kernels wrote (the call's d_outs, HJD_OUT_RGB_PLANAR in the decoder's scratch), or
 // the previous stage's outputs -- and knows no more of what preceded it.
-enum class PostKind { orient, resize, resize_aa, warp, color, tone };
+enum class PostKind { orient, resize, resize_aa, warp, color, conv, tone };
 struct PostStage {
     PostKind kind;
     PostImages in;
     int out_format;                // the decoder's, or (a stage follows) HJD_OUT_RGB_PLANAR
     PostImages out;                // orient: image i to out.ptrs[i] at out.pitches[i]
-    struct { void* ptr; int w, h, pitch; } batch;   // resize, warp, color, tone: image i to ptr + i * 3 * pitch * h
+    struct { void* ptr; int w, h, pitch; } batch;   // resize, warp, color, conv, tone: image i to ptr + i * 3 * pitch * h
     const int32_t* orientations;   // orient: per image, 1..8
     const int32_t* flags;          // resize, warp: per image, or null
     void* const* mids;             // resize_aa: image i's intermediate (hjd_resize_aa.hpp) in the scratch
@@ -131,17 +132,19 @@ struct PostStage {
     int max_h;                     // resize_aa: the tallest input, which sizes the horizontal launch
     const int32_t (*colors)[21];   // color: per image, m[9] p[9] t[3] (include/hjd.h)
     uint32_t* sums;                // color: the table of partial sums in the scratch, or null (every p is 0)
+    const hjd_conv_filter* convs;  // conv: per image (include/hjd.h)
     const hjd_tone_curve* tones;   // tone: per image (include/hjd.h)
     uint32_t* hist;                // tone: the tables of partial histograms and of composed curves in the scratch,
     uint8_t* luts;                 // or null (every mode is 0)
     size_t recs_off, recs_bytes;   // its records in the batch header, from H.recs
 };
 
-// The stages of a call in launch order (orient -> resize or resize_aa -> color -> tone, or
-// warp -> color -> tone, each optional), built once by its entry point.  Their records follow the pixel kernels' tables, each stage's at a 16-byte aligned offset.
+// The stages of a call in launch order (orient -> resize or resize_aa -> color -> conv -> tone, or
+// warp -> color -> conv -> tone, each optional), built once by its entry point.  Their records follow the pixel
+// kernels' tables, each stage's at a 16-byte aligned offset.
 struct PostPlan {
     int nstages;
-    PostStage stage[4];
+    PostStage stage[5];
     size_t recs_bytes;             // the tables and every stage's records (Staging::assemble)
 };
 

@@ -14,6 +14,7 @@
 #include "hjd_host.h"
 
 using hjd_internal::ColorRecord;
+using hjd_internal::ConvRecord;
 using hjd_internal::OrientRecord;
 using hjd_internal::ResizeRecord;
 using hjd_internal::set_error;
@@ -207,8 +208,36 @@ int write_color_records(const PostStage& s, int n, ColorRecord* recs)
     return HJD_OK;
 }
 
+// The filter kernel's records: image i of the batch s.in (planar bytes in the scratch: the resize's,
+// the warp's, or the colour stage's in their place) through s.convs[i] to its place in s.batch (the
+// caller's, or with a tone stage behind a second batch in the scratch), its tiles behind image i - 1's.
+int write_conv_records(const PostStage& s, int n, ConvRecord* recs)
+{
+    int64_t tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        ConvRecord rec;
+        rec.src = s.in.ptrs[i];
+        rec.dst = static_cast<uint8_t*>(s.batch.ptr) +
+                  3 * static_cast<size_t>(s.batch.pitch) * static_cast<size_t>(s.batch.h) * static_cast<size_t>(i);
+        rec.w = s.batch.w;
+        rec.h = s.batch.h;
+        rec.pitch = s.in.pitches[i];
+        rec.dst_pitch = s.batch.pitch;
+        static_assert(sizeof(hjd_conv_filter) == sizeof(ConvRecord) - offsetof(ConvRecord, rx),
+                      "the filter is the record's tail");
+        memcpy(&rec.rx, &s.convs[i], sizeof(hjd_conv_filter));
+        rec.tile_begin = static_cast<uint32_t>(tiles);   // (the filter's reserved word, 0: convs_check)
+        const int rc = hjd_internal::conv_item_check(rec, i, s.out_format);
+        if (rc) return rc;
+        tiles += hjd_internal::conv_tiles(rec.w, rec.h);
+        recs[i] = rec;
+    }
+    return HJD_OK;
+}
+
 // The tone kernels' records: image i of the batch s.in (planar bytes in the scratch: the resize's,
-// the warp's, or the colour stage's in their place) through s.tones[i] to its place in the caller's batch.
+// the warp's, the colour stage's in their place, or the filter stage's) through s.tones[i] to its place in the
+// caller's batch.
 int write_tone_records(const PostStage& s, int n, ToneRecord* recs)
 {
     for (int i = 0; i < n; ++i) {
@@ -243,6 +272,7 @@ int hjd::ent::post_write_records(hjd_gdec* g, const PostPlan& plan, int n)
         case PostKind::resize_aa: rc = write_resize_records(s, n, static_cast<ResizeRecord*>(recs)); break;
         case PostKind::warp: rc = write_warp_records(s, n, static_cast<WarpRecord*>(recs)); break;
         case PostKind::color: rc = write_color_records(s, n, static_cast<ColorRecord*>(recs)); break;
+        case PostKind::conv: rc = write_conv_records(s, n, static_cast<ConvRecord*>(recs)); break;
         case PostKind::tone: rc = write_tone_records(s, n, static_cast<ToneRecord*>(recs)); break;
         }
         if (rc) return rc;
@@ -278,6 +308,11 @@ int hjd::ent::post_launch(hjd_gdec* g, const PostPlan& plan, int n, hipStream_t 
             rc = hjd_internal::launch_color(g->device, static_cast<const ColorRecord*>(recs), n,
                                             hjd_internal::color_groups(s.batch.w, s.batch.h), s.sums, s.out_format,
                                             g->norm, stream);
+            break;
+        case PostKind::conv:
+            rc = hjd_internal::launch_conv(g->device, static_cast<const ConvRecord*>(recs), n,
+                                           n * hjd_internal::conv_tiles(s.batch.w, s.batch.h), s.out_format, g->norm,
+                                           stream);
             break;
         case PostKind::tone:
             rc = hjd_internal::launch_tone(g->device, static_cast<const ToneRecord*>(recs), n,
@@ -372,17 +407,43 @@ int tones_check(const hjd_tone_curve* tones, int n, bool* any, bool* data)
     return HJD_OK;
 }
 
-// The scratch of a call's colour and tone stages: `mid`, the batch the resize or warp writes in
-// their place (planar bytes; with both, the colour stage runs on it in place); `sums`, the colour
-// stage's table of partial sums where a record reads them; `hist` and `luts`, the tone stage's
-// partial histograms and composed curves where a mode is not 0.
+// The filters of a call, for its batch of out_w x out_h images: HJD_OK if every one is legal (else the
+// refusal names the frame) and their tiles fit a launch.  *any: one is not the identity record (else
+// the call is the one without filters).  n has passed the call's own check.
+int convs_check(const hjd_conv_filter* convs, int n, int out_w, int out_h, bool* any)
+{
+    *any = false;
+    for (int i = 0; i < n; ++i) {
+        ConvRecord rec;
+        memset(&rec, 0, sizeof(rec));
+        rec.w = out_w;
+        rec.h = out_h;
+        memcpy(&rec.rx, &convs[i], sizeof(hjd_conv_filter));
+        int rc = hjd_internal::conv_filter_check(rec, i);
+        if (!rc && convs[i].reserved) rc = set_error(HJD_E_INVALID, "conv item %d: reserved must be 0", i);
+        if (rc) return set_error(rc, "frame %d: %s", i, std::string(hjd_last_error()).c_str());
+        *any = *any || !hjd_internal::conv_is_identity(rec);
+    }
+    const int64_t tiles = n * hjd_internal::conv_tiles(out_w, out_h);
+    if (*any && tiles > hjd_internal::kConvMaxTiles)
+        return set_error(HJD_E_INVALID, "the batch has %lld tiles of 64 x 32 in all (at most %lld per call)",
+                         static_cast<long long>(tiles), static_cast<long long>(hjd_internal::kConvMaxTiles));
+    return HJD_OK;
+}
+
+// The scratch of a call's colour, filter and tone stages: `mid`, the batch the resize or warp writes in
+// their place (planar bytes; a colour stage with another behind it runs on it in place); `mid2`, a
+// second batch of that layout, which the filter stage writes where a tone stage follows (a filter
+// cannot run in place); `sums`, the colour stage's table of partial sums where a record reads them;
+// `hist` and `luts`, the tone stage's partial histograms and composed curves where a mode is not 0.
 struct ColorScratch {
-    Region mid, sums, hist, luts;
-    ColorScratch(bool colors, bool color_sums, bool tones, bool tone_data, int n, int out_w, int out_h)
-        : mid(colors || tones ? static_cast<size_t>(n) : 0), sums(colors && color_sums ? 1 : 0),
-          hist(tones && tone_data ? 1 : 0), luts(tones && tone_data ? 1 : 0)
+    Region mid, mid2, sums, hist, luts;
+    ColorScratch(bool colors, bool color_sums, bool convs, bool tones, bool tone_data, int n, int out_w, int out_h)
+        : mid(colors || convs || tones ? static_cast<size_t>(n) : 0), mid2(convs && tones ? static_cast<size_t>(n) : 0),
+          sums(colors && color_sums ? 1 : 0), hist(tones && tone_data ? 1 : 0), luts(tones && tone_data ? 1 : 0)
     {
-        if (colors || tones) mid.add_batch(out_w, out_h);
+        if (colors || convs || tones) mid.add_batch(out_w, out_h);
+        if (convs && tones) mid2.add_batch(out_w, out_h);
         if (colors && color_sums) sums.add_bytes(hjd_internal::color_sums_bytes(n));
         if (tones && tone_data) {
             hist.add_bytes(hjd_internal::tone_hist_bytes(n));
@@ -405,16 +466,32 @@ void add_color_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, con
     s.sums = c.sums.ptrs.empty() ? nullptr : static_cast<uint32_t*>(c.sums.ptrs[0]);
 }
 
-// Put the tone stage behind `last`, the plan's resize, warp or colour stage, which wrote the caller's
+// Put the filter stage behind `last`, the plan's resize, warp or colour stage, which wrote the caller's
 // batch in the decoder's format: it now writes planar bytes into c.mid (a colour stage, which reads
-// c.mid, then runs in place), and the tone stage that batch.
-void add_tone_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, const hjd_tone_curve* tones, int out_format,
+// c.mid, then runs in place), and the filter stage that batch.
+void add_conv_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, const hjd_conv_filter* convs, int out_format,
                     int n)
 {
     const auto batch = last.batch;
     last.out_format = HJD_OUT_RGB_PLANAR;
     last.batch = {c.mid.ptrs[0], batch.w, batch.h, c.mid.pitches[0]};
-    PostStage& s = add_stage(plan, PostKind::tone, c.mid.images(), out_format, sizeof(ToneRecord) * static_cast<size_t>(n));
+    PostStage& s = add_stage(plan, PostKind::conv, c.mid.images(), out_format, sizeof(ConvRecord) * static_cast<size_t>(n));
+    s.batch = batch;
+    s.convs = convs;
+}
+
+// Put the tone stage behind `last`, the plan's resize, warp, colour or filter stage, which wrote the
+// caller's batch in the decoder's format: it now writes planar bytes into `via` -- c.mid (a colour
+// stage, which reads c.mid, then runs in place), or behind a filter stage, which reads c.mid, c.mid2
+// -- and the tone stage that batch.
+void add_tone_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, const hjd_tone_curve* tones, int out_format,
+                    int n)
+{
+    const Region& via = last.kind == PostKind::conv ? c.mid2 : c.mid;
+    const auto batch = last.batch;
+    last.out_format = HJD_OUT_RGB_PLANAR;
+    last.batch = {via.ptrs[0], batch.w, batch.h, via.pitches[0]};
+    PostStage& s = add_stage(plan, PostKind::tone, via.images(), out_format, sizeof(ToneRecord) * static_cast<size_t>(n));
     s.batch = batch;
     s.tones = tones;
     s.hist = c.hist.ptrs.empty() ? nullptr : static_cast<uint32_t*>(c.hist.ptrs[0]);
@@ -422,13 +499,14 @@ void add_tone_stage(PostPlan& plan, PostStage& last, const ColorScratch& c, cons
 }
 
 // hjd_gdec_decode_resized_filter (orientations null), hjd_gdec_decode_resized_oriented,
-// hjd_gdec_decode_resized_color (colors not null) and hjd_gdec_decode_resized_tone (tones not null):
-// decode to the scratch, with orientations orient to a second scratch region, then the resize
-// launches, then with colours the colour launches, then with tones the tone launches.
+// hjd_gdec_decode_resized_color (colors not null), hjd_gdec_decode_resized_tone (tones not null) and
+// hjd_gdec_decode_resized_aug (any of colors, convs and tones): decode to the scratch, with
+// orientations orient to a second scratch region, then the resize launches, then with colours the
+// colour launches, then with filters the filter launch, then with tones the tone launches.
 int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                    const int32_t* orientations, const int32_t* flags, const int32_t (*colors)[21],
-                   const hjd_tone_curve* tones, void* d_out, int out_w, int out_h, int32_t out_pitch, int filter,
-                   void* stream)
+                   const hjd_conv_filter* convs, const hjd_tone_curve* tones, void* d_out, int out_w, int out_h,
+                   int32_t out_pitch, int filter, void* stream)
 {
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!d_out) return set_error(HJD_E_INVALID, "d_out is NULL");
@@ -455,6 +533,12 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
         if (rc) return rc;
         if (!any) colors = nullptr;   // every record the identity: the call without colours
     }
+    if (convs) {
+        bool any = false;
+        rc = convs_check(convs, n, out_w, out_h, &any);
+        if (rc) return rc;
+        if (!any) convs = nullptr;   // every record the identity: the call without filters
+    }
     bool tone_data = false;
     if (tones) {
         bool any = false;
@@ -465,7 +549,7 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     // (the scratch: the crops, an oriented call's oriented crops, the antialiased filter's intermediates)
     const size_t un = static_cast<size_t>(n);
     Region crops(un), oriented(orientations ? un : 0), mids(aa ? un : 0);
-    ColorScratch cs(colors != nullptr, color_sums, tones != nullptr, tone_data, n, out_w, out_h);
+    ColorScratch cs(colors != nullptr, color_sums, convs != nullptr, tones != nullptr, tone_data, n, out_w, out_h);
     const Admit admit{g->scale, false, orientations ? kCapOriented : kCapResized,
                       orientations && rois ? orient_map : nullptr, orientations};
     int64_t tiles = 0;
@@ -494,7 +578,7 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     }
     rc = tiles_check(tiles);
     if (rc) return rc;
-    rc = grow_scratch(g, {&crops, &oriented, &mids, &cs.mid, &cs.sums, &cs.hist, &cs.luts},
+    rc = grow_scratch(g, {&crops, &oriented, &mids, &cs.mid, &cs.mid2, &cs.sums, &cs.hist, &cs.luts},
                       aa ? "crops and the resize's intermediate" : "crops");
     if (rc) return rc;
     PostPlan plan{0, {}, pixel_tables_bytes(n, rois != nullptr, false)};   // the pixel kernels' tables: planar bytes
@@ -512,16 +596,18 @@ int decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes
     r.mids = mids.ptrs.data();
     r.max_h = max_h;
     if (colors) add_color_stage(plan, r, cs, colors, g->out_format, n);
+    if (convs) add_conv_stage(plan, plan.stage[plan.nstages - 1], cs, convs, g->out_format, n);
     if (tones) add_tone_stage(plan, plan.stage[plan.nstages - 1], cs, tones, g->out_format, n);
     return run_post(g, datas, sizes, n, stream, crops, rois != nullptr, plan);
 }
 
-// hjd_gdec_decode_warped (colors and tones null), hjd_gdec_decode_warped_color and
-// hjd_gdec_decode_warped_tone: decode the rectangle each warp reads to the scratch, then the warp
-// launch, then with colours the colour launches, then with tones the tone launches.
+// hjd_gdec_decode_warped (colors, convs and tones null), hjd_gdec_decode_warped_color, _tone and
+// _aug: decode the rectangle each warp reads to the scratch, then the warp launch, then with colours
+// the colour launches, then with filters the filter launch, then with tones the tone launches.
 int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
                   const int32_t* orientations, const int32_t* flags, const uint32_t* fills, const int32_t (*colors)[21],
-                  const hjd_tone_curve* tones, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
+                  const hjd_conv_filter* convs, const hjd_tone_curve* tones, void* d_out, int out_w, int out_h,
+                  int32_t out_pitch, void* stream)
 {
     if (!g || !datas || !sizes) return set_error(HJD_E_INVALID, "NULL argument");
     if (!m) return set_error(HJD_E_INVALID, "m is NULL");
@@ -540,6 +626,12 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
         if (rc) return rc;
         if (!any) colors = nullptr;   // every record the identity: the call without colours
     }
+    if (convs) {
+        bool any = false;
+        rc = convs_check(convs, n, out_w, out_h, &any);
+        if (rc) return rc;
+        if (!any) convs = nullptr;   // every record the identity: the call without filters
+    }
     bool tone_data = false;
     if (tones) {
         bool any = false;
@@ -551,7 +643,7 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
     // crop, in the scratch), the matrix on that crop
     const size_t un = static_cast<size_t>(n);
     Region crops(un);
-    ColorScratch cs(colors != nullptr, color_sums, tones != nullptr, tone_data, n, out_w, out_h);
+    ColorScratch cs(colors != nullptr, color_sums, convs != nullptr, tones != nullptr, tone_data, n, out_w, out_h);
     std::vector<int32_t> mats(6 * un);
     const WarpMap wmap{m, orientations, out_w, out_h, reinterpret_cast<int32_t(*)[6]>(mats.data())};
     const Admit admit{g->scale, false, kCapWarped, warp_map, &wmap};
@@ -574,7 +666,7 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
             return set_error(HJD_E_INVALID, "frame %d: fill 0x%x is above 0xFFFFFF (0x00RRGGBB)", i, fills[i]);
         crops.add(i, r.w, r.h);
     }
-    rc = grow_scratch(g, {&crops, &cs.mid, &cs.sums, &cs.hist, &cs.luts}, "crops");
+    rc = grow_scratch(g, {&crops, &cs.mid, &cs.mid2, &cs.sums, &cs.hist, &cs.luts}, "crops");
     if (rc) return rc;
     PostPlan plan{0, {}, pixel_tables_bytes(n, true, false)};   // the pixel kernels' tables: planar bytes
     PostStage& w = add_stage(plan, PostKind::warp, crops.images(), g->out_format, sizeof(WarpRecord) * un);
@@ -583,6 +675,7 @@ int decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes,
     w.mats = wmap.mats;
     w.fills = fills;
     if (colors) add_color_stage(plan, w, cs, colors, g->out_format, n);
+    if (convs) add_conv_stage(plan, plan.stage[plan.nstages - 1], cs, convs, g->out_format, n);
     if (tones) add_tone_stage(plan, plan.stage[plan.nstages - 1], cs, tones, g->out_format, n);
     return run_post(g, datas, sizes, n, stream, crops, true, plan);
 }
@@ -639,16 +732,16 @@ int hjd_gdec_decode_oriented(hjd_gdec* g, const uint8_t* const* datas, const siz
 int hjd_gdec_decode_resized(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
                             const int32_t* flags, void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
 {
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
-                          HJD_RESIZE_BILINEAR, stream);
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, nullptr, nullptr, d_out, out_w, out_h,
+                          out_pitch, HJD_RESIZE_BILINEAR, stream);
 }
 
 int hjd_gdec_decode_resized_filter(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
                                    const hjd_rect* rois, const int32_t* flags, void* d_out, int out_w, int out_h,
                                    int32_t out_pitch, int filter, void* stream)
 {
-    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
-                          filter, stream);
+    return decode_resized(g, datas, sizes, n, rois, nullptr, flags, nullptr, nullptr, nullptr, d_out, out_w, out_h,
+                          out_pitch, filter, stream);
 }
 
 int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -656,8 +749,8 @@ int hjd_gdec_decode_resized_oriented(hjd_gdec* g, const uint8_t* const* datas, c
                                      int out_w, int out_h, int32_t out_pitch, int filter, void* stream)
 {
     if (!orientations) return set_error(HJD_E_INVALID, "orientations is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
-                          filter, stream);
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, nullptr, nullptr, nullptr, d_out, out_w, out_h,
+                          out_pitch, filter, stream);
 }
 
 int hjd_gdec_decode_resized_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -666,8 +759,8 @@ int hjd_gdec_decode_resized_color(hjd_gdec* g, const uint8_t* const* datas, cons
                                   int filter, void* stream)
 {
     if (!colors) return set_error(HJD_E_INVALID, "colors is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, nullptr, d_out, out_w, out_h, out_pitch,
-                          filter, stream);
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, nullptr, nullptr, d_out, out_w, out_h,
+                          out_pitch, filter, stream);
 }
 
 int hjd_gdec_decode_resized_tone(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
@@ -676,16 +769,16 @@ int hjd_gdec_decode_resized_tone(hjd_gdec* g, const uint8_t* const* datas, const
                                  int filter, void* stream)
 {
     if (!tones) return set_error(HJD_E_INVALID, "tones is NULL");
-    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, tones, d_out, out_w, out_h, out_pitch,
-                          filter, stream);
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, nullptr, tones, d_out, out_w, out_h,
+                          out_pitch, filter, stream);
 }
 
 int hjd_gdec_decode_warped(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
                            const int32_t* orientations, const int32_t* flags, const uint32_t* fills, void* d_out,
                            int out_w, int out_h, int32_t out_pitch, void* stream)
 {
-    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, nullptr, nullptr, d_out, out_w, out_h, out_pitch,
-                         stream);
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, nullptr, nullptr, nullptr, d_out, out_w, out_h,
+                         out_pitch, stream);
 }
 
 int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n,
@@ -694,8 +787,8 @@ int hjd_gdec_decode_warped_color(hjd_gdec* g, const uint8_t* const* datas, const
                                  int32_t out_pitch, void* stream)
 {
     if (!colors) return set_error(HJD_E_INVALID, "colors is NULL");
-    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, nullptr, d_out, out_w, out_h, out_pitch,
-                         stream);
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, nullptr, nullptr, d_out, out_w, out_h,
+                         out_pitch, stream);
 }
 
 int hjd_gdec_decode_warped_tone(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
@@ -704,8 +797,26 @@ int hjd_gdec_decode_warped_tone(hjd_gdec* g, const uint8_t* const* datas, const 
                                 int32_t out_pitch, void* stream)
 {
     if (!tones) return set_error(HJD_E_INVALID, "tones is NULL");
-    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, tones, d_out, out_w, out_h, out_pitch,
-                         stream);
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, nullptr, tones, d_out, out_w, out_h,
+                         out_pitch, stream);
+}
+
+int hjd_gdec_decode_resized_aug(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const hjd_rect* rois,
+                                const int32_t* orientations, const int32_t* flags, const int32_t (*colors)[21],
+                                const hjd_conv_filter* convs, const hjd_tone_curve* tones, void* d_out, int out_w, int out_h,
+                                int32_t out_pitch, int filter, void* stream)
+{
+    return decode_resized(g, datas, sizes, n, rois, orientations, flags, colors, convs, tones, d_out, out_w, out_h,
+                          out_pitch, filter, stream);
+}
+
+int hjd_gdec_decode_warped_aug(hjd_gdec* g, const uint8_t* const* datas, const size_t* sizes, int n, const int32_t (*m)[6],
+                               const int32_t* orientations, const int32_t* flags, const uint32_t* fills,
+                               const int32_t (*colors)[21], const hjd_conv_filter* convs, const hjd_tone_curve* tones,
+                               void* d_out, int out_w, int out_h, int32_t out_pitch, void* stream)
+{
+    return decode_warped(g, datas, sizes, n, m, orientations, flags, fills, colors, convs, tones, d_out, out_w, out_h,
+                         out_pitch, stream);
 }
 
 }  // extern "C"

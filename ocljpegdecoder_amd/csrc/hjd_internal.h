@@ -219,6 +219,7 @@ using OrientRecord = hjd::OrientDev;   // (of hjd_orient_item, whose reserved wo
 using WarpRecord = hjd::WarpDev;       // (of hjd_warp_item)
 using ColorRecord = hjd::ColorDev;     // (of hjd_color_item, whose reserved word is use_sums here)
 using ToneRecord = hjd::ToneDev;       // (of hjd_tone_item)
+using ConvRecord = hjd::ConvDev;       // (of hjd_conv_item, whose filter's reserved word is tile_begin here)
 // a = 1, b = 0: the C default (out = (float)u8).
 inline NormRecord norm_identity() { return NormRecord{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}}; }
 // HJD_OK, or HJD_E_INVALID (NULL or non-finite constants) with the cause in the error string.
@@ -340,6 +341,25 @@ constexpr size_t tone_luts_bytes(int n) { return static_cast<size_t>(n) * 768; }
 // image's; the records have passed the checks.
 int launch_tone(int device, const ToneRecord* d_items, int n, int groups, uint32_t* d_hist, uint8_t* d_luts,
                 int out_format, const NormRecord& norm, void* stream);
+
+// The filter kernel (hjd_conv.hip; include/hjd.h hjd_conv_*).
+constexpr int64_t kConvMaxTiles = INT32_MAX;   // tiles per launch (the grid)
+// Tiles (workgroups) of one w x h image: 64 x 32 pixels of the three planes each.
+inline int64_t conv_tiles(int w, int h) { return static_cast<int64_t>((w + 63) / 64) * ((h + 31) / 32); }
+// HJD_OK, or HJD_E_INVALID with the cause in the error string: n and the
+// format; the filter of one record for an image of w x h (its radii, border,
+// taps and gains; `reserved` is the caller's word, looked at by hjd_conv_check
+// alone); and one item's side of hjd_conv_check (tile_begin is not looked at).
+int conv_out_check(int n, int out_format);
+int conv_filter_check(const ConvRecord& it, int index);
+int conv_item_check(const ConvRecord& it, int index, int out_format);
+// The identity record (include/hjd.h): it copies byte for byte.
+inline bool conv_is_identity(const ConvRecord& it) { return it.rx == 0 && it.ry == 0 && it.a == 4096 && it.b == 0; }
+// One conv_kernel launch over n records in device memory, `tiles` their tile
+// total (no host synchronisation); the records have passed the checks and
+// carry their tile_begin prefix.
+int launch_conv(int device, const ConvRecord* d_items, int n, int64_t tiles, int out_format, const NormRecord& norm,
+                void* stream);
 
 // Parsed header of one sequential scan as the GPU entropy path needs it
 // (jpeg_host.cpp).  File-level fields (width .. nblocks, out_bpm, qt) describe

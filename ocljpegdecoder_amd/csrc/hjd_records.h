@@ -1,7 +1,7 @@
 // hjd_records.h -- the records the stage kernels and the float formats read, one
 // declaration each for the host that writes them (hjd_internal.h) and the
 // kernels (hjd_norm.hpp, hjd_resize.hpp, hjd_orient.hpp, hjd_warp.hpp, hjd_color.hpp,
-// hjd_tone.hpp).  No HIP.
+// hjd_tone.hpp, hjd_conv.hpp).  No HIP.
 #pragma once
 #include <stdint.h>
 
@@ -67,5 +67,19 @@ struct ToneDev {
     uint8_t lut[3][256];   // u8_c = lut[c][D_c[x_c]]
 };
 static_assert(sizeof(ToneDev) == 808, "ToneDev layout");
+
+// One image of the filter kernel: the layout of hjd_conv_item, whose filter's
+// reserved word the host fills with the image's first tile.
+struct ConvDev {
+    const void* src;   // plane R; G and B follow at pitch * h
+    void* dst;         // plane R of the output; G and B follow at dst_pitch * h
+    int32_t w, h, pitch, dst_pitch;
+    int32_t rx, ry;    // 0..11: 2 r + 1 taps per axis
+    int32_t border;    // 0 keep, 1 reflect, 2 replicate
+    int32_t a, b;      // Q12: u8 = clamp((a (x << 24) + b S + 2^35) >> 36)
+    uint32_t tile_begin;
+    uint16_t kh[24], kv[24];   // Q12 taps, 0 beyond 2 r
+};
+static_assert(sizeof(ConvDev) == 152, "ConvDev layout");
 
 }  // namespace hjd

@@ -827,6 +827,81 @@ class GpuDecoder:
             self._n = n
         return self._with_settings(scale, fmt, norm, call, out)
 
+    @staticmethod
+    def _convs(convs, n):
+        """The filters of a call: the numpy records (kept alive by the caller) and their hjd_conv_filter pointer."""
+        from .backend import _conv_filters
+        recs = _conv_filters(convs, n)
+        return recs, recs.ctypes.data_as(ctypes.POINTER(_lib.HjdConvFilter))
+
+    def decode_rgb_resized_aug(self, datas: Sequence[bytes], size, flips=None, layout: str = "chw", out=None,
+                               stream=None, scale: int = 1, rois=None, dtype=_UINT8, mean=None, std=None,
+                               apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                               antialias=False, colors=None, convs=None, curves=None, modes=None):
+        """decode_rgb_resized with every optional stage
+        (hjd_gdec_decode_resized_aug): a colour record (colors, as
+        decode_rgb_resized_color takes them), a filter (convs: one record per
+        image or one for all, as conv_sharpness(), conv_gaussian() and
+        conv_unsharp() make them) and a tone curve (curves and modes, as
+        decode_rgb_resized_tone takes them) per image, in that order -- jitter,
+        blur, solarize -- before the dtype's normalisation:
+        out[i] = normalise(tone(conv(color(resize(orient(decode)))))).
+        A filter's borders are those of the resized image, a histogram is that
+        of the filtered one.  Each of colors, convs and (curves, modes) may be
+        None: no such stage.  Every other parameter as decode_rgb_resized;
+        with all three None, or the identity, it is exactly that call."""
+        chw, dtype, fmt, norm = self._rgb_format(layout, dtype, mean, std)
+        if not chw:
+            raise ValueError('a resized batch is planar: layout must be "chw"')
+        n = len(datas)
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        cols = self._colors(colors, n) if colors is not None else None
+        crecs, cvs = self._convs(convs, n) if convs is not None else (None, None)
+        trecs, tones = self._tones(curves, modes, n) if curves is not None or modes is not None else (None, None)
+        out = self._batch_result(n, size, dtype, out)
+        fl = self._flips(flips, n)
+
+        def call():
+            _keep, arr_d, arr_s = _byte_arrays(datas)
+            ho, wo = int(out.shape[2]), int(out.shape[3])
+            check(self.lib.hjd_gdec_decode_resized_aug(
+                self.handle, arr_d, arr_s, n, self._rects(rois, n),
+                (ctypes.c_int32 * n)(*orients) if orients is not None else None, fl, cols, cvs, tones, out.data_ptr(), wo,
+                ho, wo * out.element_size(), 1 if antialias else 0, _stream_handle(stream)),
+                "hjd_gdec_decode_resized_aug")
+            self._n = n
+        return self._with_settings(scale, fmt, norm, call, out)
+
+    def decode_rgb_warped_aug(self, datas: Sequence[bytes], size, xforms, fill=0, replicate=False, out=None,
+                              stream=None, scale: int = 1, dtype=_UINT8, mean=None, std=None,
+                              apply_exif_orientation: bool = False, orientations: Optional[Sequence[int]] = None,
+                              colors=None, convs=None, curves=None, modes=None):
+        """decode_rgb_warped with every optional stage
+        (hjd_gdec_decode_warped_aug):
+        out[i] = normalise(tone(conv(color(warp(decode))))), colors, convs,
+        curves and modes as decode_rgb_resized_aug takes them (a filter's
+        borders are those of the warped image, its fill included).  Every
+        other parameter as decode_rgb_warped."""
+        _chw, dtype, fmt, norm = self._rgb_format("chw", dtype, mean, std)
+        n = len(datas)
+        mats, fl, fi = self._warp_arrays(xforms, list(fill) if isinstance(fill, (list, tuple)) else [fill] * n,
+                                         replicate, n)
+        orients = self._orientations(datas, apply_exif_orientation, orientations)
+        cols = self._colors(colors, n) if colors is not None else None
+        crecs, cvs = self._convs(convs, n) if convs is not None else (None, None)
+        trecs, tones = self._tones(curves, modes, n) if curves is not None or modes is not None else (None, None)
+        out = self._batch_result(n, size, dtype, out)
+
+        def call():
+            _keep, arr_d, arr_s = _byte_arrays(datas)
+            ho, wo = int(out.shape[2]), int(out.shape[3])
+            check(self.lib.hjd_gdec_decode_warped_aug(
+                self.handle, arr_d, arr_s, n, mats, (ctypes.c_int32 * n)(*orients) if orients is not None else None,
+                fl, fi, cols, cvs, tones, out.data_ptr(), wo, ho, wo * out.element_size(), _stream_handle(stream)),
+                "hjd_gdec_decode_warped_aug")
+            self._n = n
+        return self._with_settings(scale, fmt, norm, call, out)
+
     def decode_coefs(self, datas: Sequence[bytes], coefs, stream=None) -> List[int]:
         """Entropy decode only into `coefs` (int16 device tensor, [blocks][64]);
         returns each frame's first block."""

@@ -28,7 +28,7 @@ ARCH = os.environ.get("HJD_ARCH", "gfx950")
 
 HIP_SOURCES = ["hjd_runtime.hip", "idct_compat.hip", "stream_pipeline.hip", "hjd_entropy.hip", "hjd_gdec.hip",
                "hjd_gdec_post.hip", "hjd_gstream.hip", "numa_affinity.hip", "hjd_probe.hip", "hjd_resize.hip",
-               "hjd_orient.hip", "hjd_warp.hip", "hjd_color.hip", "hjd_tone.hip"]
+               "hjd_orient.hip", "hjd_warp.hip", "hjd_color.hip", "hjd_tone.hip", "hjd_conv.hip"]
 # no __global__ function and no HIP call: plain C++
 CXX_SOURCES = ["jpeg_host.cpp", "hjd_entropy_prep.cpp", "hjd_entropy_emulate.cpp"]
 
